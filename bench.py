@@ -25,8 +25,16 @@ line.  Under an external torchrun WORLD_SIZE must equal --gpus.  Any mismatch (W
 fewer visible GPUs than ranks) exits 2 without printing a line, so an N-GPU line is never a 1-GPU run.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with "roofline" (HBM-bound:
-28 algorithmic bytes per placement; the kernel is latency-bound, see "limiter") and
-"cpu_baseline" (the naive CPU oracle, rank 0, N=1, with the host's core count and CPU model).
+28 algorithmic bytes per placement; the kernel is latency-bound, see "limiter").
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds what takes work of
+its own: "cpu_baseline" (the naive CPU oracle, rank 0, N=1, with the host's core count and CPU
+model), "diagnostics" (one more run of the counting build) and the measured HBM traffic of a
+separate PMC pass (profiles/) in "roofline"; without --full those fields are null.
+
+--dump-outputs DIR writes what the last timed step computed (Engine.placements(), and on c5 the
+trading records) as DIR/<name>.npy in float64: every element, or past DUMP_BYTES a fixed seeded sample
+whose indices are <name>_index.npy.  The inputs are seeded, so two builds can be compared file by file.
 """
 from __future__ import annotations
 
@@ -85,7 +93,12 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every usable host cpu: the affinity set capped by the cgroup CPU quota (SURVEY §8d: "
                          "OpenMP over clusters on all host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline, the decision-loop "
+                         "diagnostics (one more run of the counting build) and the PMC traffic of profiles/")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--slot-pool", type=int, default=0,
                     help="c5: running slots per cluster / 64 (0 = the engine's default, 4 x nodes)")
     ap.add_argument("--comm", action="store_true",
@@ -101,6 +114,9 @@ def parse():
                          "(SURVEY §8d, 28 B/placement); 'fused' = synthesised inside the placement kernel "
                          "(SURVEY §8f row 3, 12 B/placement)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    a.cpu = a.full and not a.no_cpu_baseline
     defaults = {  # (clusters, jobs per cluster, cpu sample clusters)
         "c4": (4096, 16384, 4096),
         "c3": (1024, 65536, 1024),
@@ -188,6 +204,41 @@ def cpu_baseline_c5(args, lam, sample_jobs):
     }
 
 
+DUMP_BYTES = 8 << 20  # one dumped array with its index file (at most 5 arrays a run: 40 MiB of the 64)
+DUMP_SEED = 0x4D4353
+
+
+def _dump_array(path_stem, a):
+    """a (1-D, plain or records) as float64 .npy: whole, or past DUMP_BYTES a fixed seeded sample of
+    its rows together with their indices."""
+    import numpy as np
+
+    fields = [f for f in a.dtype.names or () if f != "pad"]
+    rows = DUMP_BYTES // (8 * (max(len(fields), 1) + 1))  # + 1: the index column
+    if len(a) > rows:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, len(a), rows))
+        np.save(path_stem + "_index.npy", idx.astype(np.float64))
+        a = a[idx]
+    if fields:  # records: one column per field
+        a = np.stack([a[f].astype(np.float64) for f in fields], axis=1) if len(a) else np.zeros((0, len(fields)))
+    np.save(path_stem + ".npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_outputs(args, eng, world, rank, records=()):
+    """--dump-outputs: the placements of the run just made (and the named record readers of a
+    trading engine), one file per array; ranks of a multi-GPU run add their rank to the name."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    node, start, fin = eng.placements()
+    out = {"node": node, "start": start, "finish": fin}
+    for name in records:
+        out[name] = getattr(eng, name)()
+    for name, a in out.items():
+        _dump_array(os.path.join(args.dump_outputs, name + tag), a)
+
+
 def main_c5_delay(args, world, rank, local_rank):
     """C5 with DELAY schedulers: args.clusters cluster_small replicas with the
     reference client's arrivals, Delay loops + traders with real contracts in lock-step.  The system
@@ -238,13 +289,14 @@ def main_c5_delay(args, world, rank, local_rank):
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_max, decided_all = aggregate(elapsed, decided, device=dev)
+    dump_outputs(args, eng, world, rank, records=("contracts", "foreign"))
     ts = eng.trade_stats()
     tr = eng.contracts()
     if rank == 0:
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         achieved = decided / args.steps * BYTES_PER_PLACEMENT / avg_kernel_s / 1e9
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             sys.path.insert(0, os.path.join(REPO, "tests"))
             import oracle_ref as O
             from mcs_amd.engine import gen_streams_host
@@ -379,6 +431,7 @@ def main_c5(args, world, rank, local_rank):
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_max, decided_all = aggregate(elapsed, decided, device=dev)
+    dump_outputs(args, eng, world, rank, records=("lent", "trades"))
     ts = eng.trade_stats()
     _, lent_all = aggregate(0.0, ts["lent_runs"], device=dev)
     if rank == 0:
@@ -386,7 +439,7 @@ def main_c5(args, world, rank, local_rank):
         per_launch = decided / args.steps
         achieved = per_launch * BYTES_PER_PLACEMENT / avg_kernel_s / 1e9
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             cpu = cpu_baseline_c5(args, lam, max(1, min(args.jobs_per_cluster, 8192)))
         out = {
             "metric": "trading-system job decisions/sec (placed locally or borrowed) at 64 clusters x 256 nodes",
@@ -574,6 +627,37 @@ def cpu_baseline(args, wl, n_threads, sample_clusters=None):
     }
 
 
+def batch_diagnostics(eng, wl, n_jobs, delay, handed_over):
+    """--full, outside the timed region: per-cluster decision-loop diagnostics, from one more run of
+    the counting build (the hand-scheduled loop skips its pass / release counters otherwise)."""
+    os.environ["MCS_FIFO_DIAG"] = "1"
+    try:
+        eng.run()
+    finally:
+        os.environ.pop("MCS_FIFO_DIAG", None)
+    cs = eng.cluster_stats()
+    diag = {
+        "loop_passes_per_job": float(cs["iterations"].sum()) / max(n_jobs, 1),
+        "release_scans_per_job": float(cs["release_scans"].sum()) / max(n_jobs, 1),
+        "waited_frac": float(cs["waited"].sum()) / max(n_jobs, 1),
+        "peak_running_max": int(cs["peak_running"].max()),
+        "slot_pool": int(cs["pool"].max()),
+        "clusters_per_gpu": wl.per,
+    }
+    if delay:
+        ds = eng.delay_stats()
+        diag.pop("waited_frac")
+        diag["delay_iterations_per_job"] = diag.pop("loop_passes_per_job")
+        diag["level1_moved_frac"] = float(ds["moved_l1"].sum()) / max(n_jobs, 1)
+        # clusters the hand-scheduled loop handed to delay_kernel (re-run from t = 0, both launches in
+        # kernel_ms; the engine names both kernels then): Level1 past its LDS slice, the clock range
+        # after a move, or a runaway guard of the loop
+        diag["clusters_handed_to_delay_kernel"] = handed_over
+        diag["level1_peak_max"] = int(ds["peak_l1"].max())
+        diag["avg_wait_s"] = float(ds["total_wait_ms"].sum()) / max(float(ds["jobs_count"].sum()), 1.0) / 1e3
+    return diag
+
+
 def main_batch(args, world, rank, local_rank):
     import torch
     import torch.distributed as dist
@@ -625,50 +709,27 @@ def main_batch(args, world, rank, local_rank):
 
     elapsed_max, placed_all = aggregate(elapsed, placed, device=dev)
     kernel_name = eng.last_kernel  # the placement kernel these timings belong to
-    # outside the timed region: per-cluster decision-loop diagnostics, from one more run of the
-    # counting build (the hand-scheduled loop skips its pass / release counters otherwise)
-    os.environ["MCS_FIFO_DIAG"] = "1"
-    try:
-        eng.run()
-    finally:
-        os.environ.pop("MCS_FIFO_DIAG", None)
-    cs = eng.cluster_stats()
-    diag = {
-        "loop_passes_per_job": float(cs["iterations"].sum()) / max(n_jobs, 1),
-        "release_scans_per_job": float(cs["release_scans"].sum()) / max(n_jobs, 1),
-        "waited_frac": float(cs["waited"].sum()) / max(n_jobs, 1),
-        "peak_running_max": int(cs["peak_running"].max()),
-        "slot_pool": int(cs["pool"].max()),
-        "clusters_per_gpu": wl.per,
-    }
-    if delay:
-        ds = eng.delay_stats()
-        diag.pop("waited_frac")
-        diag["delay_iterations_per_job"] = diag.pop("loop_passes_per_job")
-        diag["level1_moved_frac"] = float(ds["moved_l1"].sum()) / max(n_jobs, 1)
-        # clusters the hand-scheduled loop handed to delay_kernel (re-run from t = 0, both launches in
-        # kernel_ms; the engine names both kernels then): Level1 past its LDS slice, the clock range
-        # after a move, or a runaway guard of the loop
-        diag["clusters_handed_to_delay_kernel"] = handed_over
-        diag["level1_peak_max"] = int(ds["peak_l1"].max())
-        diag["avg_wait_s"] = float(ds["total_wait_ms"].sum()) / max(float(ds["jobs_count"].sum()), 1.0) / 1e3
+    dump_outputs(args, eng, world, rank)
+    diag = batch_diagnostics(eng, wl, n_jobs, delay, handed_over) if args.full else None
 
     if rank == 0:
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         placements_per_launch = placed / args.steps  # this rank
         achieved = placements_per_launch * bpp / avg_kernel_s / 1e9
         traffic = None
-        try:
-            with open(args.traffic_json) as f:
-                tj = json.load(f)
-            if (tj.get("clusters"), tj.get("nodes"), tj.get("jobs_per_cluster"), tj.get("policy", "fifo"),
-                    tj.get("gen", "stream"), tj.get("config", "c4"), tj.get("lam", 0.0), tj.get("max_dur", 600)) == \
-                    (wl.per, args.nodes, wl.J, args.policy, args.gen, args.config, args.lam, args.max_dur):
-                traffic = tj.get("hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            pass
+        if args.full:  # the traffic a separate PMC pass of this shape measured, if profiles/ holds one
+            try:
+                with open(args.traffic_json) as f:
+                    tj = json.load(f)
+                if (tj.get("clusters"), tj.get("nodes"), tj.get("jobs_per_cluster"), tj.get("policy", "fifo"),
+                        tj.get("gen", "stream"), tj.get("config", "c4"), tj.get("lam", 0.0),
+                        tj.get("max_dur", 600)) == \
+                        (wl.per, args.nodes, wl.J, args.policy, args.gen, args.config, args.lam, args.max_dur):
+                    traffic = tj.get("hbm_bytes_per_launch")
+            except (OSError, ValueError):
+                pass
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             n_thr = args.cpu_threads or usable_cpus()
             if args.config == "c2":
                 n_thr = 1  # one cluster: the oracle is one serial loop
@@ -711,7 +772,7 @@ def main_batch(args, world, rank, local_rank):
             },
             "roofline": {
                 "bound": "hbm",
-                "limiter": limiter_text(traffic, placements_per_launch * bpp),
+                "limiter": limiter_text(traffic, placements_per_launch * bpp) if args.full else LIMITER,
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",

@@ -138,3 +138,51 @@ def test_parent_maps_no_gpu_runtime(tmp_path):
     assert "python" in text  # the dump is real
     for bad in ("/dev/kfd", "libamdhip64", "libtorch", "libhsa-runtime"):
         assert bad not in text, bad
+
+
+# ---- bench.py --full / --dump-outputs (host side) ----------------------------------------------
+def test_plain_run_skips_the_extras_and_full_restores_them(monkeypatch):
+    bench, a = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1"], monkeypatch)
+    assert not a.full and not a.cpu and a.dump_outputs is None and a.steps == 3
+    _, a = _bench(["--full"], monkeypatch)
+    assert a.full and a.cpu
+    _, a = _bench(["--full", "--no-cpu-baseline"], monkeypatch)
+    assert a.full and not a.cpu
+
+
+def test_dump_outputs_whole_sampled_and_records(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files, whole up to DUMP_BYTES, beyond it the same seeded sample (with
+    its indices) on every call; record arrays become one column per field."""
+    import numpy as np
+
+    bench, a = _bench(["--dump-outputs", str(tmp_path / "d")], monkeypatch)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 16)  # 64 rows of value + index
+    n = 1000
+    node = np.arange(n, dtype=np.int32) - 1
+    start = (np.arange(n, dtype=np.uint64) * 4294967 % (1 << 32)).astype(np.uint32)  # past float32's 2^24
+    rec = np.zeros(5, np.dtype([("t", "<u4"), ("winner", "<i4"), ("pad", "<u4")]))
+    rec["t"], rec["winner"] = np.arange(5), -1
+
+    class Eng:
+        def placements(self):
+            return node, start, start + 1
+
+        def trades(self):
+            return rec
+
+    bench.dump_outputs(a, Eng(), 1, 0, records=("trades",))
+    d = tmp_path / "d"
+    idx = np.load(d / "node_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) <= 64 and (np.diff(idx) > 0).all()
+    for name, src in (("node", node), ("start", start), ("finish", start + 1)):
+        got = np.load(d / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, src[idx.astype(np.int64)].astype(np.float64))
+        assert np.array_equal(np.load(d / f"{name}_index.npy"), idx)
+    t = np.load(d / "trades.npy")
+    assert t.shape == (5, 2) and np.array_equal(t[:, 0], np.arange(5)) and (t[:, 1] == -1).all()
+    assert not (d / "trades_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", n * 16)  # at the limit: the whole array, no index file
+    a.dump_outputs = str(tmp_path / "e")
+    bench.dump_outputs(a, Eng(), 2, 1)
+    assert np.array_equal(np.load(tmp_path / "e" / "node_rank1.npy"), node.astype(np.float64))
+    assert not (tmp_path / "e" / "node_rank1_index.npy").exists()

@@ -39,18 +39,18 @@ benches)
         timeout -k 10 600 python bench.py $b > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err"
         rc=$?; echo "bench $i ($b) rc=$rc"; head -c 300 "$OUT/bench_$i.json"; echo; fatal $rc || exit $rc
     done <<LIST
-${BENCHES:---gpus 1 --steps 20 --warmup 5
---clusters 2048 --steps 10 --warmup 2 --no-cpu-baseline
---clusters 1024 --steps 10 --warmup 2 --no-cpu-baseline
---clusters 512 --steps 10 --warmup 2 --no-cpu-baseline
---config c3 --steps 5 --warmup 1
---config c2 --steps 3 --warmup 1
---policy delay --steps 5 --warmup 1
---policy delay --lam 0.95 --max-dur 972 --steps 5 --warmup 1
---gen fused --steps 10 --warmup 2
---config c5 --steps 1 --warmup 1
---config c5 --comm --steps 1 --warmup 1
---config c5 --policy delay --steps 1 --warmup 1}
+${BENCHES:---gpus 1 --steps 20 --warmup 5 --full
+--clusters 2048 --steps 10 --warmup 2 --no-cpu-baseline --full
+--clusters 1024 --steps 10 --warmup 2 --no-cpu-baseline --full
+--clusters 512 --steps 10 --warmup 2 --no-cpu-baseline --full
+--config c3 --steps 5 --warmup 1 --full
+--config c2 --steps 3 --warmup 1 --full
+--policy delay --steps 5 --warmup 1 --full
+--policy delay --lam 0.95 --max-dur 972 --steps 5 --warmup 1 --full
+--gen fused --steps 10 --warmup 2 --full
+--config c5 --steps 1 --warmup 1 --full
+--config c5 --comm --steps 1 --warmup 1 --full
+--config c5 --policy delay --steps 1 --warmup 1 --full}
 LIST
     ;;
 prof)
