@@ -601,19 +601,10 @@ int mcs_run(mcs_engine* e, uint32_t t_end_s, mcs_stats* stats) {
     /* DELAY: the hand-scheduled loop first (mcs_delay_asm.hip); clusters that reach Level1 re-run on
      * delay_kernel */
     bool dasm = delay && mcs::delay_asm_eligible(npl, pool, a.guard_ok, e->gen.on);
-    switch (delay ? (dasm ? -2 : -1) : mcs::fifo_asm_form(a, npl, pool, false)) {
-        case -2: e->last_kernel = "mcs::delay_asm_kernel"; break;
-        case -1: e->last_kernel = "mcs::delay_kernel"; break;
-        case 22: e->last_kernel = "mcs::fifo_asm_kernel<16, true, 4, 8, look>"; break;
-        case 21: e->last_kernel = "mcs::fifo_duo_kernel"; break;
-        case 20: e->last_kernel = "mcs::fifo_asm_fused_kernel<1, 2>"; break;
-        case 19: e->last_kernel = "mcs::fifo_asm_fused_kernel<4, 8>"; break;
-        case 18: e->last_kernel = "mcs::fifo_asm_kernel<16, true, 1, 2>"; break;
-        case 17: e->last_kernel = "mcs::fifo_asm_kernel<16, true, 4, 8>"; break;
-        case 16: e->last_kernel = "mcs::fifo_asm_kernel<16, false, 4, 8>"; break;
-        case 32: e->last_kernel = "mcs::fifo_asm_kernel<32, false, 4, 8>"; break;
-        default: e->last_kernel = "mcs::fifo_kernel"; break;
-    }
+    if (delay)
+        e->last_kernel = dasm ? "mcs::delay_asm_kernel" : "mcs::delay_kernel";
+    else
+        e->last_kernel = mcs::fifo_form_name(mcs::fifo_asm_form(a, npl, pool, false));
     mcs::Totals tot{};
     uint32_t handed = 0;
     for (;;) {

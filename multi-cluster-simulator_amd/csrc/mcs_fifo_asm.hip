@@ -50,7 +50,7 @@ namespace mcs {
 namespace {
 
 #ifdef MCS_STAMPS
-__device__ unsigned long long g_fa_stamps[5];  // [4]: the duo loop's header re-reads
+__device__ unsigned long long g_fa_stamps[4];
 #endif
 
 #include "mcs_fa_macros.h"
@@ -191,7 +191,7 @@ __device__ unsigned long long g_fa_stamps[5];  // [4]: the duo loop's header re-
     "mcsfa_bend_%=:\n\t" MCS_FA_T0                                                               \
     "s_max_u32 s81, s81, s80\n\t"                                                                 \
     "s_cmp_gt_u32 s81, " MCS_FA_POOLMAX##W "\n\t"                                                 \
-    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t" MCS_FA_BENDCHK##W                                       \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_add_u32 s76, s57, s47\n\t"                                                                 \
     "s_cmp_ge_u32 s76, s42\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_exit_%=\n\t"                                                            \
@@ -862,214 +862,79 @@ __global__ __launch_bounds__(64) void fifo_asm_fused_kernel(FifoArgs a) {
     fa_finish<NPL, P>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
 }
 
-// ---- the duo loop: a decision wave and a release wave per cluster (low occupancy) -----------------
-// Under strong sharding a GPU holds few clusters (512 of C4's 4096 at N = 8: two waves per CU), so
-// each cluster's decision chain runs alone on its SIMD and the release scans (8 slot rows, the
-// payload adds, a node reload and a wave minimum: ~35 % of a lone wave's cycles) sit on that chain.
-// Here a second wave of the workgroup, on an otherwise idle SIMD, holds the running slots and keeps
-// the release of the next finish second ready as a packet (MCS_FH_LOOP); the decision wave
-// (MCS_FA_LOOP(16D)) posts each commit to it and applies a packet with four packed adds.  Same
-// decisions and results as W16R, bit for bit.
-struct DuoLds {
-    uint32_t ring[128][4];  // posts {kx, finish, payload, seq}
-    uint32_t hdr[4];        // {e1, e2, posts taken, slots at e1 (bit 31: overflow)}
-    uint32_t ack, done, pad[2];
-    uint32_t delta[4 * kWave];  // the packet: released {cores | mem << 16} per node, [chunk][lane]
-    uint32_t nodes[4 * kWave];  // the node words, read once by the decision wave
-};
-
-template <bool DIAG>
-__global__ __launch_bounds__(2 * kWave) void fifo_duo_kernel(FifoArgs a) {
-    const uint32_t item = blockIdx.x;
-    const uint32_t ci = a.cluster_list ? a.cluster_list[item] : item;
-    const uint32_t lane = threadIdx.x & (kWave - 1u), wave = threadIdx.x / kWave;
-    __shared__ DuoLds L;
-
-    constexpr uint32_t kGuard = 0x8000u, kClamp = kGuard - 1u;
-    const uint32_t n0 = a.node_off[ci];
-    const uint32_t N = a.node_off[ci + 1] - n0;
-    const uint64_t j0 = a.job_off[ci];
-    const uint32_t J = (uint32_t)(a.job_off[ci + 1] - j0);
-    if (wave == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t node = lane * 4u + c;
-            uint2 v = make_uint2(kClamp, kClamp);  // padding: never fits
-            if (node < N) {
-                v = a.node_free0[n0 + node];
-                v.x += kGuard;
-                v.y += kGuard;
-            }
-            L.nodes[c * kWave + lane] = v.x | (v.y << 16);
-            L.delta[c * kWave + lane] = 0u;
-        }
-    } else {
-        L.ring[lane][3] = kEmpty;  // (no post has this seq yet)
-        L.ring[lane + kWave][3] = kEmpty;
-        if (lane == 0) {
-            L.hdr[0] = kEmpty;
-            L.hdr[1] = kEmpty;
-            L.hdr[2] = 0u;
-            L.hdr[3] = 0u;
-            L.ack = 0u;  // (finish seconds are >= 1)
-            L.done = 0u;
-        }
-    }
-    __syncthreads();
-    const uint32_t rb = lds_addr(&L.ring[0][0]);
-    const uint32_t hb = lds_addr(&L.hdr[0]);
-    const uint32_t dl = lds_addr(&L.delta[0]) + lane * 4u;
-
-    if (wave == 1) {
-        // the release wave: polls until the decision wave is done (bounded: 64 polls per job)
-        const uint64_t pb = 64ull * J + (1ull << 20);
-        const uint32_t hbound = pb > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)pb;
-        const uint32_t db = lds_addr(&L.delta[0]);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-        asm volatile(MCS_FH_LOOP
-                     :
-                     : [hb] "s"(hbound), [db] "s"(db), [rb] "v"(rb), [dl] "v"(dl), [hdr] "v"(hb)
-                     : MCS_FH_CLOBBERS);
-#pragma clang diagnostic pop
-        return;
-    }
-
-    const uint4* jobs = a.jobs + j0;
-    int32_t* o_node = a.out_node + j0;
-    uint32_t* o_start = a.out_start + j0;
-    uint32_t* o_finish = a.out_finish + j0;
-    uint4 cur = jobs[lane];  // batch 0 (the array has kJobPad records of slack)
-    cur.z = cur.z < kClamp ? cur.z : kClamp;
-    cur.w = cur.w < kClamp ? cur.w : kClamp;
-    cur.z |= cur.w << 16;
-
-    const uint32_t v_pay = 0u;  // (no LDS slot rows)
-    const uint32_t v_nb = lds_addr(&L.nodes[0]) + lane * 4u;
-    const uint32_t v_nbase = rb;  // (v109: the ring base)
-    const uint32_t sel0 = 0x0b0a0908u, sel1 = 0u;
-
-    uint32_t t = 0, r = 0, flags = 0, have_w = 0;
-    uint32_t frm = 0u, lmin = kEmpty;
-    uint32_t used = 0, peak = 0, waited = 0, n_slow = 0, n_rel = 0;
-    uint32_t on = 0, os = 0, of = 0;
-#ifdef MCS_STAMPS
-    uint32_t st0 = 0, st1 = 0, st2 = 0, st3 = 0, spins = 0;
-#define MCS_FD_STAMP_OUTS MCS_FA_STAMP_OUTS, [spins] "=s"(spins)
-#define MCS_FD_SPINOUT "\n\ts_mov_b32 %[spins], s85"
-#else
-#define MCS_FD_STAMP_OUTS
-#define MCS_FD_SPINOUT ""
-#endif
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-    if constexpr (DIAG)
-        asm volatile(MCS_FA_LOOP(16D, D1) MCS_FD_SPINOUT
-                     : [t] "+s"(t), [r] "+s"(r), [flags] "+s"(flags), [hw] "+s"(have_w), [used] "+s"(used),
-                       [peak] "+s"(peak), [waited] "+s"(waited), [nslow] "+s"(n_slow), [nrel] "+s"(n_rel),
-                       [on] "+v"(on), [os] "+v"(os), [of] "+v"(of), [frm] "+v"(frm), [lmin] "+v"(lmin)
-                       MCS_FD_STAMP_OUTS
-                     : [J] "s"(J), [jobs] "s"(jobs), [onp] "s"(o_node), [osp] "s"(o_start), [ofp] "s"(o_finish),
-                       [c0] "v"(cur.x), [c1] "v"(cur.y), [c2] "v"(cur.z), [c3] "v"(cur.w), [pay] "v"(v_pay),
-                       [nb] "v"(v_nb), [nbase] "v"(v_nbase), [lane] "v"(lane), [sel0] "s"(sel0),
-                       [sel1] "s"(sel1), [dl] "v"(dl), [hdr] "v"(hb), [fdl] "i"(MCS_FLAG_DEADLOCK),
-                       [fck] "i"(MCS_FLAG_CLOCK_OVERFLOW), [fov] "i"(MCS_FLAG_OVERFLOW)
-                     : MCS_FD_CLOBBERS);
-    else
-        asm volatile(MCS_FA_LOOP(16D, D0) MCS_FD_SPINOUT
-                     : [t] "+s"(t), [r] "+s"(r), [flags] "+s"(flags), [hw] "+s"(have_w), [used] "+s"(used),
-                       [peak] "+s"(peak), [waited] "+s"(waited), [nslow] "+s"(n_slow), [nrel] "+s"(n_rel),
-                       [on] "+v"(on), [os] "+v"(os), [of] "+v"(of), [frm] "+v"(frm), [lmin] "+v"(lmin)
-                       MCS_FD_STAMP_OUTS
-                     : [J] "s"(J), [jobs] "s"(jobs), [onp] "s"(o_node), [osp] "s"(o_start), [ofp] "s"(o_finish),
-                       [c0] "v"(cur.x), [c1] "v"(cur.y), [c2] "v"(cur.z), [c3] "v"(cur.w), [pay] "v"(v_pay),
-                       [nb] "v"(v_nb), [nbase] "v"(v_nbase), [lane] "v"(lane), [sel0] "s"(sel0),
-                       [sel1] "s"(sel1), [dl] "v"(dl), [hdr] "v"(hb), [fdl] "i"(MCS_FLAG_DEADLOCK),
-                       [fck] "i"(MCS_FLAG_CLOCK_OVERFLOW), [fov] "i"(MCS_FLAG_OVERFLOW)
-                     : MCS_FD_CLOBBERS);
-#pragma clang diagnostic pop
-    // the release wave stops polling
-    if (lane == 0) __hip_atomic_store(&L.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef MCS_STAMPS
-    if (lane == 0) {
-        atomicAdd(&g_fa_stamps[0], (unsigned long long)st0);
-        atomicAdd(&g_fa_stamps[1], (unsigned long long)st1);
-        atomicAdd(&g_fa_stamps[2], (unsigned long long)st2);
-        atomicAdd(&g_fa_stamps[3], (unsigned long long)st3);
-        atomicAdd(&g_fa_stamps[4], (unsigned long long)spins);
-    }
-#endif
-#undef MCS_FD_STAMP_OUTS
-#undef MCS_FD_SPINOUT
-    fa_finish<4, 8>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
-}
-
 }  // namespace
 
-// Form codes: 22 = W16R's one-job lookahead loop (W16L), 21 = W16R's duo loop (a decision and a release wave per cluster, small grids),
-// 17 = W16R and 18 = W16S (where the 16-bit format fits), 16 = W16 with LDS slots,
-// 32 = W32, 19 / 20 = W16R / W16S on a fused job stream, 0 = the compiled kernel.  MCS_FIFO_ASM=0
-// turns the hand-scheduled loop off, =16 / =32 force a form (A/B timing, the variant tests; neither
-// has a small-cluster shape nor a fused one).
-int fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor) {
+// The form a run takes (FifoForm, mcs_internal.h).  MCS_FIFO_ASM=0 turns the hand-scheduled loop
+// off, =16 / =32 force a form (A/B timing, the variant tests; neither has a small-cluster shape nor
+// a fused one).
+FifoForm fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor) {
     const char* env = getenv("MCS_FIFO_ASM");
     const int want = env ? atoi(env) : 1;
     // the loop's two shapes: 129-256 node clusters with 8 slot rows (C4) and at most 64 nodes with 2
     // rows (C1-C3); other shapes and pools keep the compiled kernel
     // (records and results are addressed by 32-bit offsets from the cluster's base: at most
     // kAsmMaxJobs jobs per cluster, guard_ok bit 2)
-    if (want == 0 || hor || !(a.guard_ok & 4u)) return 0;
+    if (want == 0 || hor || !(a.guard_ok & 4u)) return kFormCompiled;
     // a fused job stream: the W16 register-slot shapes with GenStream at the batch ends
     if (a.gen.on) {
-        if (want == 16 || want == 32 || !(a.guard_ok & 2u)) return 0;
-        return npl == 1 && pool == 2 ? 20 : npl == 4 && pool == 8 ? 19 : 0;
+        if (want == 16 || want == 32 || !(a.guard_ok & 2u)) return kFormCompiled;
+        return npl == 1 && pool == 2 ? kFormW16SFused : npl == 4 && pool == 8 ? kFormW16RFused : kFormCompiled;
     }
-    if (npl == 1 && pool == 2) return (a.guard_ok & 2u) && want != 16 && want != 32 ? 18 : 0;
-    if (npl != 4 || pool != 8) return 0;
+    if (npl == 1 && pool == 2) return (a.guard_ok & 2u) && want != 16 && want != 32 ? kFormW16S : kFormCompiled;
+    if (npl != 4 || pool != 8) return kFormCompiled;
     // register slots: one LDS round trip per release instead of 2 + rows; measured faster than LDS
     // slots at every occupancy from 1 to 16 cluster waves per CU
     if ((a.guard_ok & 2u) && want != 32) {
-        if (want == 16) return 16;
-        // small grids (a strong shard: at most 4 cluster waves per CU) run the duo loop, whose
-        // release wave takes an otherwise idle SIMD; MCS_FIFO_DUO=0|1 forces either
-        const char* duo = getenv("MCS_FIFO_DUO");
-        const bool d = duo ? atoi(duo) != 0 : a.n_items <= kDuoMaxItems;
-        if (d) return 21;
+        if (want == 16) return kFormW16;
         // the one-job lookahead loop (W16L) for grids of at most kLookMaxItems clusters (one cluster
         // wave per SIMD and fewer); MCS_FIFO_LOOK=0|1 forces either
         const char* look = getenv("MCS_FIFO_LOOK");
         const bool l = look ? atoi(look) != 0 : a.n_items <= kLookMaxItems;
-        return l ? 22 : 17;
+        return l ? kFormW16L : kFormW16R;
     }
-    return (a.guard_ok & 1u) ? 32 : 0;
+    return (a.guard_ok & 1u) ? kFormW32 : kFormCompiled;
 }
 
 bool fifo_asm_eligible(const FifoArgs& a, int npl, int pool, bool hor) {
-    return fifo_asm_form(a, npl, pool, hor) != 0;
+    return fifo_asm_form(a, npl, pool, hor) != kFormCompiled;
 }
 
 template <bool DIAG>
-static hipError_t launch_form(const FifoArgs& a, int form, hipStream_t s) {
+static hipError_t launch_form(const FifoArgs& a, FifoForm form, hipStream_t s) {
     switch (form) {
-        case 20: hipLaunchKernelGGL((fifo_asm_fused_kernel<1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
-        case 19: hipLaunchKernelGGL((fifo_asm_fused_kernel<4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
-        case 18: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
-        case 21: hipLaunchKernelGGL((fifo_duo_kernel<DIAG>), dim3(a.n_items), dim3(2 * kWave), 0, s, a); break;
-        case 17: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16SFused: hipLaunchKernelGGL((fifo_asm_fused_kernel<1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16RFused: hipLaunchKernelGGL((fifo_asm_fused_kernel<4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16S: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16R: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
 #ifndef MCS_STAMPS
-        case 22: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG, true>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16L: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG, true>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
 #endif
-        case 16: hipLaunchKernelGGL((fifo_asm_kernel<16, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
-        case 32: hipLaunchKernelGGL((fifo_asm_kernel<32, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16: hipLaunchKernelGGL((fifo_asm_kernel<16, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW32: hipLaunchKernelGGL((fifo_asm_kernel<32, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
+// the name mcs_last_kernel reports for a form: launch_form's template arguments (without DIAG)
+const char* fifo_form_name(FifoForm form) {
+    switch (form) {
+        case kFormW16SFused: return "mcs::fifo_asm_fused_kernel<1, 2>";
+        case kFormW16RFused: return "mcs::fifo_asm_fused_kernel<4, 8>";
+        case kFormW16S: return "mcs::fifo_asm_kernel<16, true, 1, 2>";
+        case kFormW16R: return "mcs::fifo_asm_kernel<16, true, 4, 8>";
+        case kFormW16L: return "mcs::fifo_asm_kernel<16, true, 4, 8, look>";
+        case kFormW16: return "mcs::fifo_asm_kernel<16, false, 4, 8>";
+        case kFormW32: return "mcs::fifo_asm_kernel<32, false, 4, 8>";
+        case kFormCompiled: break;
+    }
+    return "mcs::fifo_kernel";
+}
+
 // MCS_FIFO_DIAG=1: the counting build (mcs_cluster_stats.iterations / release_scans); otherwise
 // those two fields hold the decisions and 0
 hipError_t launch_fifo_asm(const FifoArgs& a, int npl, int pool, hipStream_t s) {
-    const int form = fifo_asm_form(a, npl, pool, false);
+    const FifoForm form = fifo_asm_form(a, npl, pool, false);
     const char* env = getenv("MCS_FIFO_DIAG");
     return env && atoi(env) != 0 ? launch_form<true>(a, form, s) : launch_form<false>(a, form, s);
 }
@@ -1080,7 +945,7 @@ hipError_t launch_fifo_asm(const FifoArgs& a, int npl, int pool, hipStream_t s) 
 // the probe build's segment cycles (releases, failed fits, batch ends, whole loop), summed over the
 // clusters of the launches since the last call; read and reset
 extern "C" int mcs_debug_fa_stamps(unsigned long long* out) {
-    unsigned long long z[5] = {0, 0, 0, 0, 0};
+    unsigned long long z[4] = {0, 0, 0, 0};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mcs::g_fa_stamps), sizeof(z)) != hipSuccess) return -1;
     return hipMemcpyToSymbol(HIP_SYMBOL(mcs::g_fa_stamps), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }

@@ -18,9 +18,6 @@ constexpr int kWave = 64;
 constexpr int kMaxNpl = 16;   // nodes per lane -> at most 1024 nodes per cluster in ABI v1
 constexpr int kMaxPool = 32;  // running-slot registers per lane -> 2048 slots per cluster
 constexpr uint32_t kAsmMaxJobs = (1u << 28) - 128u;  // hand-scheduled loop: 32-bit record offsets
-// grids up to this many clusters would pick the duo loop by default: none (measured 1.5x slower than
-// W16R at 512-2048 clusters; MCS_FIFO_DUO=1 runs it)
-constexpr uint32_t kDuoMaxItems = 0u;
 // the W16L lookahead loop: picked for grids of at most this many clusters (0: only MCS_FIFO_LOOK=1)
 constexpr uint32_t kLookMaxItems = 0u;
 constexpr uint32_t kJobPad = 128;  // records of slack after the job array (unmasked batch loads)
@@ -149,7 +146,19 @@ bool fifo_variant_exists(int npl, int pool);
 // the hand-scheduled decision loop (mcs_fifo_asm.hip): NPL 4 / P 8 or NPL 1 / P 2, streamed
 // batch runs; MCS_FIFO_ASM=0 turns it off
 bool fifo_asm_eligible(const FifoArgs& a, int npl, int pool, bool hor);
-int fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor);  // 22, 21, 20, 19, 18, 17, 16, 32 or 0
+// the kernel a FIFO batch run takes (the numbers are the form codes of DESIGN.md and profiles/)
+enum FifoForm : int {
+    kFormCompiled = 0,    // fifo_kernel (mcs_kernels.hip)
+    kFormW16 = 16,        // 16-bit node format, running slots in LDS (MCS_FIFO_ASM=16 only)
+    kFormW16R = 17,       // 16-bit node format, running slots in registers: NPL 4 / P 8
+    kFormW16S = 18,       // W16R for clusters of at most 64 nodes: NPL 1 / P 2
+    kFormW16RFused = 19,  // W16R / W16S on a fused job stream
+    kFormW16SFused = 20,
+    kFormW16L = 22,       // W16R with a one-job lookahead (MCS_FIFO_LOOK=1 only)
+    kFormW32 = 32,        // 32-bit node format, running slots in LDS
+};
+FifoForm fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor);
+const char* fifo_form_name(FifoForm form);  // what mcs_last_kernel reports for it
 hipError_t launch_fifo_asm(const FifoArgs& a, int npl, int pool, hipStream_t s);
 hipError_t launch_gen_attrs(uint4* jobs, const uint64_t* job_off, const uint32_t* max_c,
                             const uint32_t* max_m, uint32_t n_clusters, uint64_t seed,

@@ -20,23 +20,18 @@ KATS = load_kats()
 
 
 W16R = "mcs::fifo_asm_kernel<16, true, 4, 8>"
-DUO = "mcs::fifo_duo_kernel"
 LOOK = "mcs::fifo_asm_kernel<16, true, 4, 8, look>"
 
 
 def w16r_form(n_clusters):
     """The kernel the engine picks for a streamed 129-256-node launch of n_clusters in the 16-bit
-    format: W16R, the duo loop (a decision and a release wave per cluster) under MCS_FIFO_DUO=1, or
-    the one-job lookahead loop W16L under MCS_FIFO_LOOK=1 (no grid picks either by default:
-    kDuoMaxItems = kLookMaxItems = 0)."""
-    if os.environ.get("MCS_FIFO_DUO") == "1":
-        return DUO
+    format: W16R, or the one-job lookahead loop W16L under MCS_FIFO_LOOK=1 (no grid picks it by
+    default: kLookMaxItems = 0)."""
     return LOOK if os.environ.get("MCS_FIFO_LOOK") == "1" else W16R
 
 
 def set_form(monkeypatch, form):
-    """form: "0" W16R, "1" the duo loop, "look" the lookahead loop (the parametrisations below)."""
-    monkeypatch.setenv("MCS_FIFO_DUO", "1" if form == "1" else "0")
+    """form: "0" W16R, "look" the lookahead loop (the parametrisations below)."""
     monkeypatch.setenv("MCS_FIFO_LOOK", "1" if form == "look" else "0")
 
 def run_engine(eng, arrays, streams):
@@ -315,8 +310,8 @@ def test_heterogeneous_cluster_sizes(engine):
 
 @pytest.mark.parametrize("sizes", [[0, 1, 5, 63, 64, 65, 130, 200, 256], [0, 1, 2, 5, 33, 63, 64]],
                          ids=["asm_4x8", "asm_1x2"])
-@pytest.mark.parametrize("duo", ["0", "1", "look"])
-def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, duo, monkeypatch):
+@pytest.mark.parametrize("form", ["0", "look"])
+def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, form, monkeypatch):
     """Clusters of many sizes in one launch of each hand-scheduled loop shape (the largest picks it:
     129-256 nodes -> 4 chunks x 8 slot rows, <= 64 nodes -> 1 chunk x 2 rows): padding nodes, an
     empty cluster (its first job deadlocks), partial JSON availability, zero-duration jobs."""
@@ -339,7 +334,7 @@ def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, duo, monkeypa
     arrays = pack_clusters(clusters)
     off = np.arange(len(parts) + 1, dtype=np.uint64) * J
     s = JobStreams(*(np.concatenate([p[f] for p in parts]) for f in range(4)), off)
-    set_form(monkeypatch, duo)
+    set_form(monkeypatch, form)
     node, start, fin, st, cs = run_engine(engine, arrays, s)
     if max(sizes) > 64:
         assert engine.last_kernel == w16r_form(len(sizes))
@@ -349,12 +344,12 @@ def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, duo, monkeypa
     assert cs[0]["flags"] & L.MCS_FLAG_DEADLOCK  # zero nodes: the first job never fits
 
 
-@pytest.mark.parametrize("nodes,duo", [(256, "0"), (256, "1"), (256, "look"), (5, "0")])
-def test_hand_scheduled_diag_build(nodes, duo, monkeypatch):
+@pytest.mark.parametrize("nodes,form", [(256, "0"), (256, "look"), (5, "0")])
+def test_hand_scheduled_diag_build(nodes, form, monkeypatch):
     """MCS_FIFO_DIAG=1 launches the counting build of the hand-scheduled loop: the same placements
     and per-cluster results, plus the pass and release-scan counters (which the production build
     leaves at the decision count and 0)."""
-    set_form(monkeypatch, duo)
+    set_form(monkeypatch, form)
     arrays, streams, _ = seeded_workload("n256" if nodes == 256 else "small", 64, 3000)
     res = {}
     for diag in ("0", "1"):
@@ -375,7 +370,7 @@ def test_hand_scheduled_diag_build(nodes, duo, monkeypatch):
     assert_parity(arrays, streams, *res["1"][:3], c1)
 
 
-@pytest.mark.parametrize("shape", ["w16s", "w16r", "duo", "look", "w32"])
+@pytest.mark.parametrize("shape", ["w16s", "w16r", "look", "w32"])
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
 def test_hand_scheduled_fuzz(engine, shape, seed, monkeypatch):
     """Randomised clusters and streams through each hand-scheduled loop form, bit-exact against the
@@ -383,10 +378,10 @@ def test_hand_scheduled_fuzz(engine, shape, seed, monkeypatch):
     availability, bursts of simultaneous arrivals, zero-duration and zero-resource jobs, requests
     equal to a node's free value, and one request per cluster that fits no node (a head-of-line
     deadlock at a random point of the stream)."""
-    set_form(monkeypatch, {"duo": "1", "look": "look"}.get(shape, "0"))
-    arrays, s = fuzz_workload("w16r" if shape in ("duo", "look") else shape, seed)
+    set_form(monkeypatch, "look" if shape == "look" else "0")
+    arrays, s = fuzz_workload("w16r" if shape == "look" else shape, seed)
     node, start, fin, st, cs = run_engine(engine, arrays, s)
-    want = {"w16s": "mcs::fifo_asm_kernel<16, true, 1, 2>", "w16r": W16R, "duo": DUO, "look": LOOK,
+    want = {"w16s": "mcs::fifo_asm_kernel<16, true, 1, 2>", "w16r": W16R, "look": LOOK,
             "w32": "mcs::fifo_asm_kernel<32, false, 4, 8>"}[shape]
     if st.escalations == 0:
         assert engine.last_kernel == want
@@ -522,17 +517,16 @@ def test_every_kernel_variant(policy):
             # clusters), with LDS slots (MCS_FIFO_ASM=16) and its 32-bit one (=32; =0 turns the loop
             # off), and the compiled kernel's two (the low-occupancy one is picked for small grids;
             # MCS_FIFO_LAT forces either)
-            # (and the duo loop, MCS_FIFO_DUO=1, the register-slot form's two-wave variant)
-            for fused, lat, asm, duo in ((False, "1", "0", None), (False, "0", "0", None), (False, None, "1", "0"),
-                                         (False, None, "1", "1"), (False, None, "1", "look"),
+            # (and the lookahead loop, MCS_FIFO_LOOK=1, the register-slot form's W16L variant)
+            for fused, lat, asm, form in ((False, "1", "0", None), (False, "0", "0", None), (False, None, "1", "0"),
+                                         (False, None, "1", "look"),
                                          (False, None, "16", None), (False, None, "32", None),
                                          (True, None, None, None)):
                 if policy == "DELAY" and lat == "0":
                     continue
                 if policy == "DELAY" and asm in ("1", "16", "32"):
                     continue
-                env = {"MCS_FIFO_LAT": lat, "MCS_FIFO_ASM": asm, "MCS_FIFO_DUO": "0" if duo == "look" else duo,
-                       "MCS_FIFO_LOOK": "1" if duo == "look" else None}
+                env = {"MCS_FIFO_LAT": lat, "MCS_FIFO_ASM": asm, "MCS_FIFO_LOOK": "1" if form == "look" else None}
                 old = {k: os.environ.get(k) for k in env}
                 for k, v in env.items():
                     if v is not None:
@@ -550,7 +544,7 @@ def test_every_kernel_variant(policy):
                             os.environ.pop(k, None)
                         else:
                             os.environ[k] = v
-                tag = f"nodes {nn} pool {pool} fused {fused} lat {lat} asm {asm} duo {duo}"
+                tag = f"nodes {nn} pool {pool} fused {fused} lat {lat} asm {asm} form {form}"
                 np.testing.assert_array_equal(node, oracle[0], err_msg=tag)
                 np.testing.assert_array_equal(start, oracle[1], err_msg=tag)
                 np.testing.assert_array_equal(fin, oracle[2], err_msg=tag)
