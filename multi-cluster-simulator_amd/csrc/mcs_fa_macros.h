@@ -15,9 +15,13 @@
 //                                                                                              s_mov s96 + s_nop 0
 //  SDWA / op_sel write preserving the other word     1     MCS_FA_FIT16: v80/v81 (WORD_1,      v_cmp_lt s[60:61] + v_ffbl v117
 //    -> VALU reads that VGPR (DstSelForwarding)            UNUSED_PRESERVE) -> v_perm          between (found by measurement,
-//                                                                                              tools/asm_debug.py)
+//                                                                                              tools/asm_debug.py); MCS_FA_FIT16Q:
+//                                                                                              s_add s55 (one wait state, after
+//                                                                                              the v81 write the v_perm reads)
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
-//    uses it as the lane select                            written                             from s_add/s_mov)
+//    uses it as the lane select                            written                             from s_add/s_mov; REPICK16Q's
+//                                                                                              v_cmp writes s[58:59], which only
+//                                                                                              SALU reads: interlocked)
 //  SALU writes M0 -> v_writelane with an M0 lane     1*    result writes at a Level0 decision  >= 1 other instruction between
 //    select (*not in the ISA table; kept anyway)           (HEAD, ZEROKX)                      (s_add s80 / s_ff1, s_lshl3_add)
 //                                                          DELAY G list (MCS_FD_ENUM: m0 =     s_add s86 between
@@ -35,9 +39,12 @@
 //    rewritten
 //  VALU writes SGPR -> VMEM reads it (address/      5     none: the store/load bases s[64:71]   -
 //    soffset)                                              are SALU-written
-//  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / COMMIT16 / INSERT16R     (the indexed moves sit between
-//                                                                                              on and off; no non-indexed VALU
-//                                                                                              read inside a region)
+//  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16Q / COMMIT16 /   (the indexed moves sit between
+//                                                          INSERT16R                           on and off; no non-indexed VALU
+//                                                                                              read inside a region: REPICK16Q,
+//                                                                                              entered from inside DECIDE16Q's,
+//                                                                                              turns the mode off before its
+//                                                                                              VALU and on again to return)
 // A reorder that moves a consumer next to its producer in the table must add the s_nop.
 
 // progress-based wave priority at each batch end: the fewer of its jobs a wave has decided, the higher
@@ -76,6 +83,8 @@
 // Register map of the loop (all fixed; listed as clobbers).
 //   s40 t     s41 min(64, J - cb)  s42 J   s43 have_w  s44 flags  s45 arr   s46 dur
 //   s47 cursor's lane in the batch (r - cb)  s48 (W16: {cores|mem<<16}) / s[48:49] cores, mem
+//   (W16 forms but W16Q: s49 = 0x100;  W16Q: s49 current slot row R, s[58:59] its free lanes not
+//   yet handed out, s86 the re-pick's starting row;  W16L / fused: s58, s59 their own, see there)
 //   s50 fl   s51 byte mask of fl   s52 8 * chunk   s53 register index of the chunk
 //   s[54:55] kx, finish   s56 next clock   s57 cb   s[60:61] lanes with a free row
 //   s[62:63] one-lane exec masks   s[64:65] jobs  s[66:67] out_node  s[68:69] out_start
@@ -451,6 +460,113 @@
 #define MCS_FA_NODEIDX32 MCS_FA_NODEIDX
 #define MCS_FA_NODEIDX16 MCS_FA_NODEIDX
 #define MCS_FA_NODEIDX16R MCS_FA_NODEIDX
+
+// ---- W16Q: W16R with the insert's slot handed out from a scalar lane mask (streamed loop only) -----
+// Any free slot serves an insert (a release scans every row, and the node adds commute), so the
+// insert does not look for the lowest lane's lowest free row.  It keeps a current row s49 (R, 0-7)
+// and the lanes whose row R is free and not yet handed out in s[58:59] (CUR): an insert takes CUR's
+// lowest lane with scalar instructions only — no v_cmp / v_ffbl of v89 in the fit test, no v_readlane
+// of the row, no v_xor.  v89 stays the truth for the other rows; bit R of v89 means "row R freed by
+// a release since it became current" (the release bodies are W16R's).  When CUR runs out the insert
+// branches out of line to the re-pick (MCS_FA_REPICK16Q), which takes the next row p = R+1 ... R+8
+// (mod 8) with a free lane: CUR = the lanes with bit p of v89, R = p, bit p cleared.  No such row:
+// the pool is full, CUR stays 0 and the insert runs under an empty exec (peak > 64*8 at the batch
+// end, as W16R).  Only an empty CUR is ever abandoned, so nothing is folded back into v89.
+// Entry: R = 0, CUR = every lane, bit 0 of v89 clear.  The release scan leaves s49 and s[58:59]
+// alone (it clobbers s[50:55], s[60:63], s[86:91]).  s49 = 0x100 and v89's sentinel bit 8 are not
+// used by this form.
+// The fit test is MCS_FA_FIT16 with the pass's finish (s_add s55) as the instruction between the
+// last SDWA-preserve write and the v_perm (hazard table, row 2), so the loop body's own is empty.
+#define MCS_FA_FIT16Q                                                                             \
+    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
+    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
+    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
+    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
+    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "s_add_u32 s55, s40, s46\n\t" /* finish; the wait state the v_perm's read of v81 needs */    \
+    "v_perm_b32 v86, v81, v80, s72\n\t"
+#define MCS_FA_FINISH16Q ""
+#define MCS_FA_ANYFIT16Q MCS_FA_ANYFIT
+#define MCS_FA_REC16Q MCS_FA_REC16
+#define MCS_FA_TAKE16Q MCS_FA_TAKE16
+#define MCS_FA_RELOAD16Q MCS_FA_RELOAD16
+#define MCS_FA_ZEROKX16Q MCS_FA_ZEROKX
+#define MCS_FA_POOLMAX16Q "64*8"
+#define MCS_FA_NODEIDX16Q MCS_FA_NODEIDX
+#define MCS_FA_SCAN16Q MCS_FA_SCAN16R
+#define MCS_FA_SCANEND16Q MCS_FA_SCANEND
+#define MCS_FA_INIT16Q                                                                            \
+    "s_mov_b32 s49, 0\n\t"                                                                       \
+    "s_mov_b64 s[58:59], -1\n\t"                                                                 \
+    "v_mov_b32 v89, 0xfe\n\t"                                                                    \
+    "v_mov_b32 v32, -1\n\t"                                                                      \
+    "v_mov_b32 v33, -1\n\t"                                                                      \
+    "v_mov_b32 v34, -1\n\t"                                                                      \
+    "v_mov_b32 v35, -1\n\t"                                                                      \
+    "v_mov_b32 v36, -1\n\t"                                                                      \
+    "v_mov_b32 v37, -1\n\t"                                                                      \
+    "v_mov_b32 v38, -1\n\t"                                                                      \
+    "v_mov_b32 v39, -1\n\t"
+// MCS_FA_DECIDE16R's single register-index region; the insert lane is CUR's lowest (s_ff1 of an
+// empty CUR is -1: the shift then gives a bit the AND drops), SCC of the AND = a slot exists
+#define MCS_FA_DECIDE16Q                                                                          \
+    "v_readlane_b32 s51, v86, s50\n\t"                                                            \
+    "s_ff1_i32_b64 s85, s[58:59]\n\t"                                                             \
+    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
+    "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
+    "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
+    "s_lshl3_add_u32 s54, s52, s50\n\t"                                                           \
+    "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
+    "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
+    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
+    "s_and_b64 exec, s[62:63], s[58:59]\n\t"                                                      \
+    "s_cbranch_scc0 mcsfa_rp_%=\n"                                                                \
+    "mcsfa_ins_%=:\n\t"                                                                           \
+    "s_andn2_b64 s[58:59], s[58:59], s[62:63]\n\t" /* the slot is handed out */                  \
+    "s_lshl2_add_u32 s87, s54, s73\n\t"                                                           \
+    "s_set_gpr_idx_idx s49\n\t"                                                                   \
+    "v_mov_b32 v32, s55\n\t" /* the slot: finish, payload, node address (SGPR sources) */        \
+    "v_mov_b32 v40, s48\n\t"                                                                      \
+    "v_mov_b32 v48, s87\n\t"                                                                      \
+    "s_set_gpr_idx_off\n\t"
+// the re-pick (out of line, entered inside the register-index region with exec empty; returns into
+// it with exec = the insert lane, s[62:63] its mask, CUR and R the new row's).  s86 = the row it
+// started from, s76 / v120 temps.
+#define MCS_FA_REPICK16Q                                                                          \
+    "mcsfa_rp_%=:\n\t"                                                                            \
+    "s_set_gpr_idx_off\n\t"                                                                       \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_mov_b32 s86, s49\n"                                                                        \
+    "mcsfa_rpl_%=:\n\t"                                                                           \
+    "s_add_u32 s49, s49, 1\n\t"                                                                   \
+    "s_and_b32 s49, s49, 7\n\t"                                                                   \
+    "s_lshl_b32 s76, 1, s49\n\t"                                                                  \
+    "v_and_b32 v120, s76, v89\n\t"                                                                \
+    "v_cmp_ne_u32_e64 s[58:59], 0, v120\n\t"                                                      \
+    "s_cmp_lg_u64 s[58:59], 0\n\t"                                                                \
+    "s_cbranch_scc1 mcsfa_rpf_%=\n\t"                                                             \
+    "s_cmp_lg_u32 s49, s86\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_rpl_%=\n\t"                                                             \
+    "s_mov_b64 s[62:63], 0\n\t" /* every row empty: the pool is full (R is back at its start) */ \
+    "s_branch mcsfa_rpe_%=\n"                                                                     \
+    "mcsfa_rpf_%=:\n\t"                                                                           \
+    "v_xor_b32 v89, v120, v89\n\t" /* bit R clear in every lane: the row's free lanes are CUR */ \
+    "s_ff1_i32_b64 s85, s[58:59]\n\t"                                                             \
+    "s_lshl_b64 s[62:63], 1, s85\n"                                                               \
+    "mcsfa_rpe_%=:\n\t"                                                                           \
+    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
+    "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
+    "s_branch mcsfa_ins_%=\n"
+#define MCS_FA_RBODY16Q MCS_FA_RBODY16R MCS_FA_REPICK16Q
+
+// the pass's finish time t + duration, after the fit test (W16Q: inside its fit test)
+#define MCS_FA_FINISH32 "s_add_u32 s55, s40, s46\n\t"
+#define MCS_FA_FINISH16 MCS_FA_FINISH32
+#define MCS_FA_FINISH16R MCS_FA_FINISH32
+#define MCS_FA_FINISH16S MCS_FA_FINISH32
 
 // ---- W16S: W16R for clusters of at most 64 nodes (one chunk, node = lane) and 2 slot rows --------
 // (cluster_small / cluster_big: C1-C3).  The fit bit is bit 15 of one SDWA AND; no chunk pick, and

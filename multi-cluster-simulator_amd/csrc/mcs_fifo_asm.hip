@@ -26,7 +26,9 @@
 //   * Slot insert under exec = the lowest lane with a free row (s_ff1 of the free-row lanes,
 //     ANDed back with them); a full pool leaves exec empty and is caught by peak > 64*P at the
 //     batch end (the cluster is re-run with a bigger pool by the engine, as for the compiled
-//     kernel).  The counters (used, peak, waited, passes) are scalar.
+//     kernel).  The counters (used, peak, waited, passes) are scalar.  The streamed W16R loop takes
+//     any free slot instead: the next lane of a current slot row, from a scalar mask (W16Q,
+//     mcs_fa_macros.h), with the same full-pool rule.
 //   * The cursor's lane in the batch lives in m0 for the result batch writes (v_writelane) and
 //     in s47 for the record broadcasts (v_readlane).
 //   * Release at a clock advance: every slot row's expiry lane mask is computed before the first
@@ -101,8 +103,7 @@ __device__ unsigned long long g_fa_stamps[4];
     /* ---- one pass = one decision (scheduler.go:216-296) ---- */                               \
     "mcsfa_inner_%=:\n\t"                                                                         \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W                           \
-    "s_add_u32 s55, s40, s46\n\t"                                                                 \
+    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W MCS_FA_FINISH##W          \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
     "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
@@ -713,7 +714,8 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
 
     uint32_t t = 0, r = 0, flags = 0, have_w = 0;
     // free slot rows of the lane (W16 forms: plus the sentinel bit 8, so the lowest free row of a
-    // full lane reads as 8, a register index still in range)
+    // full lane reads as 8, a register index still in range; the streamed W16R loop sets its own,
+    // MCS_FA_INIT16Q)
     uint32_t frm = (1u << P) - 1u + (W == 16 ? 0x100u : 0u), lmin = kEmpty;
     uint32_t used = 0, peak = 0, waited = 0, n_slow = 0, n_rel = 0;
     uint32_t on = 0, os = 0, of = 0;
@@ -746,9 +748,9 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     else if constexpr (NPL == 1)
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16S, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16S, D0) MCS_FA_OPERANDS);
-    else if constexpr (RS)
-        if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16R, D1) MCS_FA_OPERANDS);
-        else asm volatile(MCS_FA_LOOP(16R, D0) MCS_FA_OPERANDS);
+    else if constexpr (RS)  // (the streamed W16R loop hands out its slots by rows: W16Q)
+        if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16Q, D1) MCS_FA_OPERANDS);
+        else asm volatile(MCS_FA_LOOP(16Q, D0) MCS_FA_OPERANDS);
     else
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16, D0) MCS_FA_OPERANDS);
