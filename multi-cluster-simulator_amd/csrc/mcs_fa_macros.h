@@ -12,12 +12,18 @@
 //  hazard (CDNA3/gfx950)                           needs  where it occurs                     covered by
 //  VALU writes VGPR -> DPP reads it                  2     every DPP min/max chain (SCANEND,   s_nop 1 between the steps; before
 //                                                          the DELAY filter)                   the first: s_nop 1, or (DELAY rel)
-//                                                                                              s_mov s96 + s_nop 0
+//                                                                                              s_mov s96 + s_nop 0;
+//                                                          MCS_FA_SCANEND16Q                   two fit-test / pass-head
+//                                                                                              instructions in every gap (none
+//                                                                                              writes v120); before the first:
+//                                                                                              s_waitcnt + 2 v_pk_sub
 //  SDWA / op_sel write preserving the other word     1     MCS_FA_FIT16: v80/v81 (WORD_1,      v_cmp_lt s[60:61] + v_ffbl v117
 //    -> VALU reads that VGPR (DstSelForwarding)            UNUSED_PRESERVE) -> v_perm          between (found by measurement,
 //                                                                                              tools/asm_debug.py); MCS_FA_FIT16Q:
 //                                                                                              s_add s55 (one wait state, after
-//                                                                                              the v81 write the v_perm reads)
+//                                                                                              the v81 write the v_perm reads);
+//                                                                                              MCS_FA_SCANEND16Q: a DPP step and
+//                                                                                              the s_add s55 between
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
 //    uses it as the lane select                            written                             from s_add/s_mov; REPICK16Q's
 //                                                                                              v_cmp writes s[58:59], which only
@@ -27,7 +33,9 @@
 //                                                          DELAY G list (MCS_FD_ENUM: m0 =     s_add s86 between
 //                                                          cursor -> v_writelane v113/v118)
 //  VALU writes VGPR -> v_readlane / v_readfirstlane  1     DECIDE16R / ZEROKX read v86, v117;  >= 3 instructions between every
-//    reads it (gfx950)                                     REC16 after TAKE16; SCANEND v120     pair; SCANEND: s_nop 1
+//    reads it (gfx950)                                     REC16 after TAKE16; SCANEND v120     pair; SCANEND: s_nop 1;
+//                                                          SCANEND16Q v120; ZROUTE16Q v87      SCANEND16Q: s_cselect + s_cmp;
+//                                                          (written at the batch's TAKE16Q)    v87: a batch's passes apart
 //                                                          DELAY G pass (r04): v_cndmask v113  >= 6 (GTEST's scalar prologue)
 //                                                          -> GTEST's v_readlane v113; v123
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
@@ -40,8 +48,8 @@
 //  VALU writes SGPR -> VMEM reads it (address/      5     none: the store/load bases s[64:71]   -
 //    soffset)                                              are SALU-written
 //  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16Q / COMMIT16 /   (the indexed moves sit between
-//                                                          INSERT16R                           on and off; no non-indexed VALU
-//                                                                                              read inside a region: REPICK16Q,
+//                                                          INSERT16R (none is open in a        on and off; no non-indexed VALU
+//                                                          release scan or its tail)           read inside a region: REPICK16Q,
 //                                                                                              entered from inside DECIDE16Q's,
 //                                                                                              turns the mode off before its
 //                                                                                              VALU and on again to return)
@@ -95,6 +103,7 @@
 //   release: row expiry masks in s[50:55], s[60:63], s[86:91]
 //   v[64:71] nodes (W32: pairs {C, M} per chunk; W16: v64-v67)   v[72:79] fit-test differences
 //   v80-v86 fit bits / byte mask   (release: finish rows in v[72:87])
+//   (W16Q: v87 the batch's true arrival column; v94 holds 0xffffffff for its zero-duration jobs)
 //   v89 free rows  v90 earliest finish  v91-92 result batch (kx, start; finish = start + dur at
 //   the store)
 //   v[94:97] records  v[98:101] next records   v107 slot column  v108 node column  v109 node base
@@ -425,6 +434,23 @@
     "s_set_gpr_idx_off\n\t"                                                                       \
     "s_lshl_b32 s76, 1, s86\n\t"                                                                  \
     "v_xor_b32 v89, s76, v89\n\t" /* the row is taken */
+// the decision's test for a zero-duration job (s50 = the fitting lane), the hook at the head of
+// mcsfa_arrive and the out-of-line code after the release bodies: W16Q's zero-duration route
+#define MCS_FA_ZTEST                                                                              \
+    "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_zero_%=\n\t"
+#define MCS_FA_ZTEST32 MCS_FA_ZTEST
+#define MCS_FA_ZTEST16 MCS_FA_ZTEST
+#define MCS_FA_ZTEST16R MCS_FA_ZTEST
+#define MCS_FA_ZTEST16S MCS_FA_ZTEST
+#define MCS_FA_ARRIVE32 ""
+#define MCS_FA_ARRIVE16 ""
+#define MCS_FA_ARRIVE16R ""
+#define MCS_FA_ARRIVE16S ""
+#define MCS_FA_ZROUTE32(D) ""
+#define MCS_FA_ZROUTE16(D) ""
+#define MCS_FA_ZROUTE16R(D) ""
+#define MCS_FA_ZROUTE16S(D) ""
 // lanes with a fit into vcc
 #define MCS_FA_ANYFIT "v_cmp_ne_u32_e32 vcc, 0, v86\n\t"
 #define MCS_FA_ANYFIT32 MCS_FA_ANYFIT
@@ -491,14 +517,126 @@
 #define MCS_FA_FINISH16Q ""
 #define MCS_FA_ANYFIT16Q MCS_FA_ANYFIT
 #define MCS_FA_REC16Q MCS_FA_REC16
-#define MCS_FA_TAKE16Q MCS_FA_TAKE16
-#define MCS_FA_RELOAD16Q MCS_FA_RELOAD16
-#define MCS_FA_ZEROKX16Q MCS_FA_ZEROKX
+// Zero-duration jobs (1 in 600 of the reference's streams) leave the common pass through the test
+// it runs anyway: when a batch is taken, the arrival column v94 gets 0xffffffff in the lanes of
+// zero-duration jobs (the true arrivals stay in v87), so the head's arrival test sends such a job to
+// mcsfa_arrive, which tells it apart by that arrival and takes it out of line (MCS_FA_ZROUTE16Q):
+// the true arrival's test, the fit test, and then mcsfa_nofit or mcsfa_zero.  A retry after a release
+// comes back the same way.  The pass itself has no duration test.  (The clock never reaches
+// 0xffffffff in this loop and no arrival is 0xffffffff: the host bounds last arrival + sum(dur + 1)
+// below it, and streams without that bound run the compiled kernel.  A non-zero job carrying that
+// arrival would still sleep to it as before.)
+#define MCS_FA_ZMASK16Q(SRC)                                                                      \
+    "v_mov_b32 v87, " SRC "\n\t"                                                                  \
+    "v_cmp_eq_u32_e32 vcc, 0, v95\n\t"                                                            \
+    "v_cndmask_b32_e32 v94, " SRC ", v111, vcc\n\t" /* (v111 = -1) */
+#define MCS_FA_TAKE16Q                                                                            \
+    "v_mov_b32 v95, v99\n\t"                                                                      \
+    "v_min_u32 v96, 0x7fff, v100\n\t"                                                             \
+    "v_min_u32 v97, 0x7fff, v101\n\t"                                                             \
+    "v_lshl_or_b32 v96, v97, 16, v96\n\t" MCS_FA_ZMASK16Q("v98")
+#define MCS_FA_ZTEST16Q ""
+#define MCS_FA_ARRIVE16Q                                                                          \
+    "s_cmp_eq_u32 s45, -1\n\t"                                                                    \
+    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"
+#define MCS_FA_ZROUTE16Q(D)                                                                       \
+    "mcsfa_zarr_%=:\n\t"                                                                          \
+    "v_readlane_b32 s76, v87, s47\n\t" /* the true arrival */                                    \
+    "s_cmp_lg_u32 s46, 0\n\t"                                                                     \
+    "s_cselect_b32 s76, s45, s76\n\t" /* (a non-zero job: the arrival it carries) */             \
+    "s_cmp_gt_u32 s76, s40\n\t"                                                                   \
+    "s_cbranch_scc0 mcsfa_zfit_%=\n\t"                                                            \
+    "s_mov_b32 s40, s76\n\t" /* not arrived: sleep to it */                                      \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_branch mcsfa_adv_%=\n"                                                                     \
+    "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT                                             \
+    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
+    "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
+    "s_branch mcsfa_zero_%=\n"
+// The LDS node copy of this form is one 16-byte word per lane, chunk c of lane l at base + 16 * l +
+// 4 * c (v108 = base + 16 * lane, 16-byte aligned): the scan refreshes it with one ds_write_b128 of
+// v[64:67] and reloads it with one ds_read_b128.  The decision's kx (s54) is then the node index
+// lane * 4 + chunk itself: the slot's node address is still base + 4 * kx, and the result batch is
+// stored without a conversion (fa_finish: KXNODE).
+#define MCS_FA_RELOAD16Q "ds_read_b128 v[64:67], v108\n\t"
+#define MCS_FA_ZEROKX16Q                                                                          \
+    "v_readlane_b32 s51, v86, s50\n\t"                                                           \
+    "s_mov_b32 m0, s47\n\t"                                                                      \
+    "s_ff1_i32_b32 s52, s51\n\t"                                                                 \
+    "s_lshr_b32 s53, s52, 3\n\t"                                                                 \
+    "s_lshl2_add_u32 s54, s50, s53\n\t"
 #define MCS_FA_POOLMAX16Q "64*8"
-#define MCS_FA_NODEIDX16Q MCS_FA_NODEIDX
-#define MCS_FA_SCAN16Q MCS_FA_SCAN16R
-#define MCS_FA_SCANEND16Q MCS_FA_SCANEND
-#define MCS_FA_INIT16Q                                                                            \
+#define MCS_FA_NODEIDX16Q "v_mov_b32 v126, v91\n\t"
+#define MCS_FA_SCAN16Q                                                                            \
+    /* the LDS node copy is refreshed from the registers first (commits do not touch it) */       \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b32 s75, 0\n\t"                                                                       \
+    "v_cmp_ge_u32_e64 s[50:51], s40, v32\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[52:53], s40, v33\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[54:55], s40, v34\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[60:61], s40, v35\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[62:63], s40, v36\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[86:87], s40, v37\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[88:89], s40, v38\n\t"                                                    \
+    "v_cmp_ge_u32_e64 s[90:91], s40, v39\n\t"                                                    \
+    MCS_FR_ROW(0, "s[50:51]", "v32", "v40", "v48") MCS_FR_ROW(1, "s[52:53]", "v33", "v41", "v49")  \
+    MCS_FR_ROW(2, "s[54:55]", "v34", "v42", "v50") MCS_FR_ROW(3, "s[60:61]", "v35", "v43", "v51")  \
+    MCS_FR_ROW(4, "s[62:63]", "v36", "v44", "v52") MCS_FR_ROW(5, "s[86:87]", "v37", "v45", "v53")  \
+    MCS_FR_ROW(6, "s[88:89]", "v38", "v46", "v54") MCS_FR_ROW(7, "s[90:91]", "v39", "v47", "v55")  \
+    "s_mov_b64 exec, -1\n\t"                                                                     \
+    "s_sub_u32 s80, s80, s75\n\t" MCS_FA_RELOAD16Q                                              \
+    /* the lane's earliest remaining finish (released rows now hold -1) */                     \
+    "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
+    "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \
+    "v_min3_u32 v90, v90, v37, v38\n\t"                                                          \
+    "v_min_u32 v90, v90, v39\n\t"
+// The end of this form's scan carries the head job's fit test (MCS_FA_FIT16Q, MCS_FA_ANYFIT) and the
+// pass-head tests in the wait states of the DPP minimum, two instructions per gap where the shared
+// MCS_FA_SCANEND has an s_nop 1: the node reload is waited for right after the lane-minimum tree
+// (the v_mov of the chain is issued under it), and every gap instruction writes registers the chain
+// does not read.  With a head job in the batch that has arrived (s47 < s41 and s45 <= t: after every
+// failed fit and every arrival advance) the scan enters the pass at mcsfa_fitted, after the fit
+// test.  Otherwise (no job left in the batch or the pass bound, or a head that has not arrived after
+// a placed WaitQueue head's sleep: s76 = -1 or a later arrival, a zero-duration job's 0xffffffff
+// included) the fit test's results are dropped (temporaries only: v72-v75, v80, v81, v86, vcc, s55)
+// and the scan ends as the shared one, at the loop's own continuation.  The same instructions are
+// issued either way, so there is one tail.  Hazards (table above): every DPP step reads v120 two
+// instructions after its write; the v_perm reads v81 two instructions (a DPP step, s_add) after
+// the SDWA write preserving its low word; v_readlane reads v120 two scalar instructions after the
+// last DPP step; no register-index region is open.
+#ifdef MCS_STAMPS
+#define MCS_FA_FITTED16Q "mcsfa_fts_%="
+#define MCS_FA_FITSTUB16Q "mcsfa_fts_%=:\n\t" MCS_FA_T1("s94") "s_branch mcsfa_fitted_%=\n"
+#else
+#define MCS_FA_FITTED16Q "mcsfa_fitted_%="
+#define MCS_FA_FITSTUB16Q ""
+#endif
+#define MCS_FA_SCANEND16Q                                                                         \
+    "v_mov_b32 v120, v90\n\t"                                                                     \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
+    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
+    "v_min_u32_dpp v120, v120, v120 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
+    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
+    "v_min_u32_dpp v120, v120, v120 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_min_u32_dpp v120, v120, v120 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_min_u32_dpp v120, v120, v120 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "s_add_u32 s55, s40, s46\n\t" /* finish */                                                   \
+    "v_perm_b32 v86, v81, v80, s72\n\t"                                                           \
+    "v_min_u32_dpp v120, v120, v120 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                  \
+    MCS_FA_ANYFIT                                                                                 \
+    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
+    "v_min_u32_dpp v120, v120, v120 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                  \
+    "s_cselect_b32 s76, s45, -1\n\t" /* the head's arrival; none: never */                       \
+    "s_cmp_le_u32 s76, s40\n\t"                                                                   \
+    "v_readlane_b32 s77, v120, 63\n\t"                                                            \
+    "s_cbranch_scc1 " MCS_FA_FITTED16Q "\n\t"
+#define MCS_FA_INIT16Q MCS_FA_ZMASK16Q("v94") /* (batch 0) */                                     \
     "s_mov_b32 s49, 0\n\t"                                                                       \
     "s_mov_b64 s[58:59], -1\n\t"                                                                 \
     "v_mov_b32 v89, 0xfe\n\t"                                                                    \
@@ -518,7 +656,7 @@
     "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
     "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
     "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
-    "s_lshl3_add_u32 s54, s52, s50\n\t"                                                           \
+    "s_lshl2_add_u32 s54, s50, s53\n\t" /* kx = the node index, lane * 4 + chunk */             \
     "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
     "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
     "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
@@ -560,7 +698,7 @@
     "s_mov_b64 exec, s[62:63]\n\t"                                                                \
     "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
     "s_branch mcsfa_ins_%=\n"
-#define MCS_FA_RBODY16Q MCS_FA_RBODY16R MCS_FA_REPICK16Q
+#define MCS_FA_RBODY16Q MCS_FA_RBODY16R MCS_FA_REPICK16Q MCS_FA_FITSTUB16Q
 
 // the pass's finish time t + duration, after the fit test (W16Q: inside its fit test)
 #define MCS_FA_FINISH32 "s_add_u32 s55, s40, s46\n\t"

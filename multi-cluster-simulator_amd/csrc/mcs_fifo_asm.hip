@@ -36,7 +36,10 @@
 //     payloads back under exec = that mask.  The slot's node word is the node's LDS address.
 //   * The ready head's arrival/clock checks and the WaitQueue bookkeeping follow fifo_kernel line
 //     by line (see the comments there); the result batch keeps the node's LDS index
-//     (chunk * 64 + lane) and converts it to the node index when it is stored.
+//     (chunk * 64 + lane) and converts it to the node index when it is stored.  The streamed
+//     W16R loop (W16Q) keeps its LDS node copy as one 16-byte word per lane, so its index is the
+//     node index itself; its release scan carries the head job's fit test in the DPP wait states,
+//     and its zero-duration jobs leave the pass through the arrival test (mcs_fa_macros.h).
 //
 // Hazards (wait states are not inserted by the compiler inside asm): DPP reads a VGPR 2 states
 // after its write (s_nop 1), v_readlane reads a VGPR at least 1 instruction after its write, m0
@@ -103,11 +106,11 @@ __device__ unsigned long long g_fa_stamps[4];
     /* ---- one pass = one decision (scheduler.go:216-296) ---- */                               \
     "mcsfa_inner_%=:\n\t"                                                                         \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W MCS_FA_FINISH##W          \
+    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W MCS_FA_FINISH##W "\n"    \
+    "mcsfa_fitted_%=:\n\t" /* (W16Q's release scan enters here, the fit test done in its tail) */ \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_zero_%=\n\t"                                                            \
+    MCS_FA_ZTEST##W /* a zero-duration job: mcsfa_zero (W16Q: by way of mcsfa_arrive) */           \
     MCS_FA_DECIDE##W                                                                              \
     "s_min_u32 s77, s77, s55\n\t" /* the wave's earliest finish */                                \
     "s_mov_b64 exec, -1\n\t"                                                                      \
@@ -140,7 +143,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "s_branch mcsfa_placed_%=\n"                                                                  \
                                                                                                   \
-    "mcsfa_arrive_%=:\n\t"                                                                        \
+    "mcsfa_arrive_%=:\n\t" MCS_FA_ARRIVE##W                                                      \
     "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
     MCS_FA_CNTS_##D                                                                               \
     "s_branch mcsfa_adv_%=\n"                                                                     \
@@ -175,7 +178,7 @@ __device__ unsigned long long g_fa_stamps[4];
     /* (loopend's test, so the usual continuation is one taken branch) */                        \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W                                                 \
+    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W MCS_FA_ZROUTE##W(D)                             \
                                                                                                   \
     "mcsfa_deadlock_%=:\n\t"                                                                      \
     "s_or_b32 s44, s44, %[fdl]\n\t"                                                               \
@@ -600,7 +603,8 @@ __device__ unsigned long long g_fa_stamps[4];
 // are stored in the loop), the undecided rows after a deadlock or a clock overflow, and the
 // cluster's statistics.  A peak above the pool means a skipped insert: the engine re-runs the
 // cluster with a larger pool.
-template <int NPL, int P>
+// (KXNODE: the result registers hold the node index itself, not chunk * 64 + lane)
+template <int NPL, int P, bool KXNODE = false>
 __device__ __forceinline__ void fa_finish(const FifoArgs& a, uint32_t ci, uint32_t lane, uint32_t J, uint32_t t,
                                           uint32_t r, uint32_t flags, uint32_t waited, uint32_t peak,
                                           uint32_t n_slow, uint32_t n_rel, uint32_t on, uint32_t os, uint32_t of,
@@ -611,7 +615,7 @@ __device__ __forceinline__ void fa_finish(const FifoArgs& a, uint32_t ci, uint32
         if (r > 0u) {  // the batch holding the last decision (earlier ones are stored)
             const uint32_t i = ((r - 1u) & ~63u) + lane;
             if (i < r) {
-                o_node[i] = (int32_t)(NPL == 1 ? on : (on & 63u) * NPL + (on >> 6));
+                o_node[i] = (int32_t)(NPL == 1 || KXNODE ? on : (on & 63u) * NPL + (on >> 6));
                 o_start[i] = os;
                 o_finish[i] = of;
             }
@@ -656,6 +660,8 @@ __device__ __forceinline__ void fa_finish(const FifoArgs& a, uint32_t ci, uint32
 // (DIAG: count the passes without a decision and the release scans into mcs_cluster_stats; the
 // production launches skip them, 1.6 % of the C4 loop)
 // (LOOK: the W16L lookahead loop, W16R's shape only)
+// (the streamed W16R loop, W16Q: LDS holds the node words alone, [64] lanes x [4] chunks, one 16-byte
+// word per lane; its kx is the node index)
 template <int W, bool RS, int NPL, int P, bool DIAG, bool LOOK = false>
 __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     static_assert(W == 16 || !RS, "register slots: 16-bit node format only");
@@ -665,8 +671,8 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     const uint32_t ci = a.cluster_list ? a.cluster_list[item] : item;
     const uint32_t lane = threadIdx.x;
 
-    __shared__ uint64_t lds[NPL * kWave + 2 * P * kWave];
-    uint64_t* const pay_nf = lds + NPL * kWave + P * kWave;
+    constexpr bool QF = W == 16 && RS && NPL == 4 && !LOOK;  // the W16Q macro set
+    __shared__ alignas(QF ? 16 : 8) uint64_t lds[QF ? NPL * kWave / 2 : NPL * kWave + 2 * P * kWave];
 
     constexpr uint32_t kGuard = W == 32 ? 0x80000000u : 0x8000u;
     constexpr uint32_t kClamp = kGuard - 1u;  // request clamp and padding value
@@ -684,9 +690,10 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
         if constexpr (W == 32)
             lds[c * kWave + lane] = (uint64_t)v.x | ((uint64_t)v.y << 32);
         else
-            reinterpret_cast<uint32_t*>(lds)[c * kWave + lane] = v.x | (v.y << 16);
+            reinterpret_cast<uint32_t*>(lds)[QF ? node : c * kWave + lane] = v.x | (v.y << 16);
     }
     if constexpr (!RS) {
+        uint64_t* const pay_nf = lds + NPL * kWave + P * kWave;
 #pragma unroll
         for (int p = 0; p < P; ++p) pay_nf[p * kWave + lane] = (uint64_t)kEmpty << 32;
     }
@@ -705,8 +712,8 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     __syncthreads();  // (one wave: orders the LDS initialisation before the node reads in the asm)
 
     const uint32_t base = lds_addr(lds);
-    const uint32_t v_pay = base + 2048u + lane * 8u;
-    const uint32_t v_nb = base + lane * (W / 4u);
+    const uint32_t v_pay = QF ? 0u : base + 2048u + lane * 8u;  // (W16Q: no LDS slot rows)
+    const uint32_t v_nb = base + lane * (QF ? 16u : W / 4u);
     const uint32_t v_nbase = base;
     // perm selectors: W32 gathers chunk pairs 0/1 and 2/3, W16 all four chunks at once
     const uint32_t sel0 = W == 32 ? 0x0c0c0b09u : NPL == 1 ? 0x7fffu : 0x0b0a0908u;
@@ -767,7 +774,12 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
         atomicAdd(&g_fa_stamps[3], (unsigned long long)st3);
     }
 #endif
-    fa_finish<NPL, P>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
+    // W16Q marks a zero-duration job by the arrival 0xffffffff, which is only safe while the clock
+    // stays below it (the host's bound): a clock that got there anyway hands the cluster to the
+    // compiled kernel, like a pool overflow
+    if constexpr (QF)
+        if (t == 0xffffffffu) flags |= MCS_FLAG_OVERFLOW;
+    fa_finish<NPL, P, QF>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
 }
 
 typedef uint32_t mcs_u32x8 __attribute__((ext_vector_type(8)));
