@@ -310,6 +310,37 @@ typedef struct mcs_cluster_state {
 int mcs_cluster_states(mcs_engine* eng, uint32_t t_s, mcs_cluster_state* out, uint32_t n_clusters,
                        double* kernel_ms);
 
+/* ---- the ClusterState time series: the whole Start stream in one call ----------------------- */
+/* One sample of the telemetry the reference produces over time: traderServer.Start sends a
+ * ClusterState every 5 s (trader_server.go:24-47), RunMetrics samples every 5 s (metrics.go:25-30).
+ * queued is the _jobs_in_queue counter of the DELAY path: it rises at "/delay" ingestion
+ * (server.go:75) and falls at each placement (scheduler.go:320,348).  The engine reports it with
+ * this one definition under FIFO as well; the reference never moves the counter under FIFO.
+ * A zero-duration job is queued on [arrival, start) and never running; an unplaced job stays queued
+ * for every t_k >= arrival.  average_wait_time is not part of a sample, as it is not part of
+ * mcs_cluster_state: WaitTime depends on each pending job's last attempt, so it is not a function
+ * of the placements at t. */
+typedef struct mcs_cluster_sample {   /* 16 B */
+    float cores_utilization;          /* as mcs_cluster_state, at t_k                        */
+    float memory_utilization;
+    uint32_t running;                 /* jobs with start <= t_k < finish                      */
+    uint32_t queued;                  /* jobs with arrival <= t_k that have not started by t_k:
+                                         start > t_k, or never placed (MCS_NODE_UNPLACED)     */
+} mcs_cluster_sample;
+
+/* Every sample t_k = t0_s + k * period_s, k < n_samples, of every cluster from one pass over the
+ * last FIFO/DELAY run's placements: sample k is bit for bit what mcs_cluster_states(eng, t_k)
+ * returns for cores_utilization, memory_utilization and running (float32 sums in node order).
+ * out[c * n_samples + k] is cluster c at t_k.  first (may be NULL) receives the full record at t0_s:
+ * the stream's first message, the only one that carries the totals (trader_server.go:28-34).
+ * The preconditions are those of mcs_cluster_states (MCS_E_STATE before a run, after a trading run,
+ * after mcs_append_jobs).  MCS_E_INVALID: period_s == 0, n_samples == 0, out == NULL, n_clusters
+ * above the engine's count, or a last sample past 0xFFFFFFFE.  kernel_ms (may be NULL) receives
+ * the summed device time of the launches. */
+int mcs_cluster_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                             mcs_cluster_sample* out, mcs_cluster_state* first, uint32_t n_clusters,
+                             double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

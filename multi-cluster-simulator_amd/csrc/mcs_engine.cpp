@@ -856,4 +856,76 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
     return MCS_OK;
 }
 
+int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                             mcs_cluster_sample* out, mcs_cluster_state* first, uint32_t n_clusters,
+                             double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
+    if (e->trade_run || e->dtrade_run)
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading");
+    if (e->segmented)
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
+    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
+    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
+    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
+        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    double total_ms = 0.0;
+    if (first) {  // the stream's first message: the single record at t0_s
+        double ms = 0.0;
+        if (int st = mcs_cluster_states(e, t0_s, first, n_clusters, &ms)) return st;
+        total_ms += ms;
+    }
+    if (n_clusters == 0) {
+        if (kernel_ms) *kernel_ms = total_ms;
+        return MCS_OK;
+    }
+    // samples per launch: the device buffer stays within 256 MiB (MCS_SERIES_CHUNK overrides the count)
+    uint64_t chunk = (256ull << 20) / (sizeof(mcs_cluster_sample) * (uint64_t)n_clusters);
+    if (const char* env = getenv("MCS_SERIES_CHUNK"))
+        if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_samples) chunk = n_samples;
+    mcs_cluster_sample* d_out = nullptr;
+    uint2* d_summ = nullptr;
+    hipError_t st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_cluster_sample));
+    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(e->total_jobs, e->C) * sizeof(uint2));
+    mcs::SeriesArgs a{};
+    a.s.node_off = e->d_node_off;
+    a.s.cap = e->d_cap;
+    a.s.free0 = e->d_free0;
+    a.s.jobs = e->d_jobs;
+    a.s.job_off = e->d_job_off;
+    a.s.out_node = e->d_out_node;
+    a.s.out_start = e->d_out_start;
+    a.s.out_finish = e->d_out_finish;
+    a.s.n_clusters = n_clusters;
+    a.summ = d_summ;
+    a.out = d_out;
+    a.period = period_s;
+    a.magic = period_s > 1 ? ~0ull / period_s + 1ull : 0ull;
+    for (uint64_t k0 = 0; st == hipSuccess && k0 < n_samples; k0 += chunk) {
+        const uint32_t nk = (uint32_t)(n_samples - k0 < chunk ? n_samples - k0 : chunk);
+        a.t0 = (uint32_t)(t0_s + k0 * period_s);
+        a.n_samples = nk;
+        st = hipEventRecord(e->ev0, e->stream);
+        if (st == hipSuccess && k0 == 0) st = mcs::launch_series_summary(a, e->stream);
+        if (st == hipSuccess) st = mcs::launch_state_series(a, e->max_n ? e->max_n : 1, e->stream);
+        if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
+        total_ms += ms;
+        if (st == hipSuccess)  // the chunk's columns of every cluster's row
+            st = hipMemcpy2D(out + k0, (size_t)n_samples * sizeof(mcs_cluster_sample), d_out,
+                             (size_t)nk * sizeof(mcs_cluster_sample), (size_t)nk * sizeof(mcs_cluster_sample),
+                             n_clusters, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_out);
+    (void)hipFree(d_summ);
+    if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("cluster state series: ") + hipGetErrorString(st));
+    if (kernel_ms) *kernel_ms = total_ms;
+    return MCS_OK;
+}
+
 }  // extern "C"

@@ -137,6 +137,33 @@ struct StateArgs {  // the ClusterState reduction over a run's placements (mcs_s
 };
 hipError_t launch_state(const StateArgs& a, uint32_t max_n, hipStream_t s);  // mcs_state.hip
 
+// The ClusterState time series (mcs_state.hip, series_kernel): samples t0 + k * period, k < n_samples.
+struct SeriesArgs {
+    StateArgs s;              // the run's placements; s.out and s.t are not used
+    uint2* summ;              // {arrival_min, end_max} per batch of kSeriesBatch jobs, series_summ_size() pairs
+    mcs_cluster_sample* out;  // [s.n_clusters][n_samples], cluster-major
+    uint32_t t0, period, n_samples;
+    unsigned long long magic; // ceil(2^64 / period) for period >= 2: x / period = hi64(x * magic), x < 2^32
+};
+constexpr uint32_t kSeriesBatch = 256;        // jobs per summary pair
+constexpr uint32_t kSeriesLds = 78u * 1024u;  // difference array budget: two workgroups per CU with the static LDS
+constexpr uint32_t kSeriesMaxTile = 127;      // samples per tile at most (two sum lanes per sample)
+constexpr uint32_t kSeriesRep = 16;           // copies of the running and the queued counter rows
+__host__ __device__ inline uint32_t series_rows(uint32_t n_nodes) { return 2u * n_nodes + 2u * kSeriesRep + 2u; }
+// samples per tile of a cluster of n_nodes nodes: series_rows LDS rows of u32; odd, so that the row
+// stride puts neither the per-row prefix chains nor the per-sample sums on one bank
+__host__ __device__ inline uint32_t series_tile(uint32_t n_nodes) {
+    uint32_t ts = kSeriesLds / (4u * series_rows(n_nodes));
+    if (ts > kSeriesMaxTile) ts = kSeriesMaxTile;
+    return (ts - 1u) | 1u;
+}
+// cluster c's summaries start at job_off[c] / kSeriesBatch + c
+inline size_t series_summ_size(uint64_t total_jobs, uint32_t n_clusters) {
+    return (size_t)(total_jobs / kSeriesBatch) + n_clusters + 1;
+}
+hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s);
+hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t s);
+
 // Launchers (mcs_kernels.hip).  Return hipSuccess or the launch error.
 hipError_t launch_fifo(const FifoArgs& a, int npl, int pool, bool hor, hipStream_t s);
 uint32_t cu_count();  // CUs of the current device (256 on MI355X)

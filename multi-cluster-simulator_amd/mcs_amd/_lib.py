@@ -138,6 +138,15 @@ class mcs_cluster_state(C.Structure):
     ]
 
 
+class mcs_cluster_sample(C.Structure):
+    _fields_ = [
+        ("cores_utilization", C.c_float),
+        ("memory_utilization", C.c_float),
+        ("running", C.c_uint32),
+        ("queued", C.c_uint32),
+    ]
+
+
 class mcs_delay_cluster_stats(C.Structure):
     _fields_ = [
         ("total_wait_ms", C.c_int64),
@@ -241,6 +250,8 @@ SIGNATURES = [
     ("mcs_resource_utilization", C.c_int, [vp, C.c_uint32, f32p, f32p]),
     ("mcs_cluster_states", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_state), C.c_uint32,
                                      C.POINTER(C.c_double)]),
+    ("mcs_cluster_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
+                                           C.POINTER(mcs_cluster_state), C.c_uint32, C.POINTER(C.c_double)]),
     # include/mcs_trade.h
     ("mcs_set_shard", C.c_int, [vp, C.c_uint32, C.c_uint32]),
     ("mcs_comm_unique_id", C.c_int, [C.POINTER(mcs_comm_id)]),

@@ -143,6 +143,9 @@ DELAY_STATS_DTYPE = np.dtype([("total_wait_ms", "<i8"), ("jobs_count", "<i8"), (
 CLUSTER_STATE_DTYPE = np.dtype([("cores_utilization", "<f4"), ("memory_utilization", "<f4"), ("total_cpu", "<u4"),
                                 ("total_memory", "<u4"), ("running", "<u4"), ("t_s", "<u4")])
 
+CLUSTER_SAMPLE_DTYPE = np.dtype([("cores_utilization", "<f4"), ("memory_utilization", "<f4"), ("running", "<u4"),
+                                 ("queued", "<u4")])
+
 CONTRACT_DTYPE = np.dtype([("t", "<u4"), ("requester", "<u4"), ("winner", "<i4"), ("approvals", "<u4"),
                            ("policy", "<u4"), ("cores", "<u4"), ("mem", "<u4"), ("time_s", "<u4"), ("failed", "<u4"),
                            ("pad", "<u4")])
@@ -432,6 +435,24 @@ class Engine:
                                            n, C.byref(ms)))
         return (out, ms.value) if with_time else out
 
+    def cluster_state_series(self, t0_s: int, period_s: int, n_samples: int, with_time: bool = False):
+        """The ClusterState time series of every cluster (mcs_cluster_state_series): samples
+        t0_s + k * period_s, k < n_samples, as an array of shape (num_clusters, n_samples) of
+        CLUSTER_SAMPLE_DTYPE, and the full records at t0_s (CLUSTER_STATE_DTYPE), the stream's first
+        messages.  Returns (samples, first); with_time: (samples, first, kernel ms)."""
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), CLUSTER_SAMPLE_DTYPE)
+        first = np.zeros(n, CLUSTER_STATE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(L.lib().mcs_cluster_state_series(self._h, int(t0_s), int(period_s), int(n_samples),
+                                                 samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+                                                 first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n,
+                                                 C.byref(ms)))
+        return (samples, first, ms.value) if with_time else (samples, first)
+
     def approve_trade(self, total_cores, total_memory, core_util, mem_util, cores, memory, time_s) -> np.ndarray:
         """mcs_approve_trade: Trader.ApproveTrade (trader.go:141-167) on the GPU for arrays of
         (responder totals + sample, contract) queries; returns 0/1 per query."""
@@ -500,4 +521,5 @@ def roofline_placements_per_s(peak_bytes_per_s: float = 8.0e12) -> float:
 
 
 __all__ = ["Engine", "GenParams", "JobStreams", "RunStats", "gen_cluster_host", "gen_streams_host",
-           "scaled_lambda", "device_count", "CLUSTER_STATS_DTYPE", "DELAY_STATS_DTYPE", "math"]
+           "scaled_lambda", "device_count", "CLUSTER_STATS_DTYPE", "DELAY_STATS_DTYPE", "CLUSTER_SAMPLE_DTYPE",
+           "math"]

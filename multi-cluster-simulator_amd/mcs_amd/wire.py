@@ -715,8 +715,20 @@ def cluster_state(cu: float, mu: float, avg_wait_ms: float, totals: Optional[Tup
                         total_cpu=tc, total_memory=tm, average_wait_time=float(avg_wait_ms))
 
 
+def start_stream(samples_row, first_record, avg_wait_ms: float = 0.0) -> List[ClusterState]:
+    """The ClusterState messages of one cluster's Start stream (trader_server.go:24-47) over a
+    sampled run: samples_row is the cluster's row of Engine.cluster_state_series (one message per
+    sample), first_record its full record at the first sample.  The first message carries the
+    totals, every later one none (ClusterChange, :28-34).  The series has no average_wait_time
+    (include/mcs.h), so every message carries avg_wait_ms."""
+    totals = (int(first_record["total_cpu"]), int(first_record["total_memory"]))
+    return [cluster_state(s["cores_utilization"], s["memory_utilization"], avg_wait_ms,
+                          totals=totals if k == 0 else None) for k, s in enumerate(samples_row)]
+
+
 __all__ = ["Job", "WireError", "decode_job", "encode_job", "job_record", "streams_from_posts",
            "posts_from_streams", "fifo_waited", "cluster_snapshot", "go_float32", "Duration", "ClusterState",
            "ContractRequest", "ContractResponse", "NodeObject", "VirtualNodeRequest", "PbJob",
            "ProvideJobsResponse", "marshal", "unmarshal", "provide_jobs_batches", "cluster_state",
+           "start_stream",
            "ZERO_TIME", "NS_PER_S", "READY", "RUNNING", "WAITING", "FINISHED"]
