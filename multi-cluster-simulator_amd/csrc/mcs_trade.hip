@@ -21,17 +21,12 @@
 // state a wave both writes and re-reads (node free vectors, slot finish times, trader locks) is
 // staged in LDS: an L2 atomic or store followed by a plain global load of the same line from the
 // same wave could be served stale by the non-coherent vector L1.
-#include "mcs_trade_internal.h"
-#include "mcs_trader_dev.h"
-#include "mcs_wave.h"
+// The scheduler step, the trader rounds and the clock rule are mcs_trade_dev.h's, shared with the
+// resident forms.
+#include "mcs_trade_dev.h"
 
 namespace mcs {
 namespace {
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x; }
 
@@ -165,82 +160,28 @@ __global__ __launch_bounds__(64) void tr_step_kernel(TradeArgs a) {
         st.minf = fin < st.minf ? fin : st.minf;
         return true;
     };
-    auto place_own = [&](uint32_t j, uint32_t k, uint4 jb) -> bool {
-        const uint32_t fin = T + jb.y;
-        if (jb.y != 0u && !commit(k, jb.z, jb.w, fin)) return false;
-        if (lane == 0) {
-            a.out_node[j0 + j] = (int32_t)k;
-            a.out_start[j0 + j] = T;
-            a.out_finish[j0 + j] = fin;
-        }
-        ++st.placed;
-        ++st.decided;
-        return true;
+    auto lent_head = [&]() -> TrLent {
+        const TrLq e = a.lq[(size_t)c * a.LQ + st.lq_head];
+        return TrLent{e.borrower, e.job, e.c, e.m, e.dur};
     };
-
-    TrRecA req{kEmpty, 0u, 0u, 0u};
-    for (;;) {
-        if (st.has_w) {  // WaitQueue head (scheduler.go:219-251)
-            const uint4 jb = jobs[st.w];
-            const uint32_t k = first_fit(jb.z, jb.w);
-            if (k != kEmpty) {
-                if (!place_own(st.w, k, jb)) {
-                    st.flags |= MCS_FLAG_OVERFLOW;
-                    break;
-                }
-                st.has_w = 0u;
-            } else if (a.borrow) {
-                req = TrRecA{st.w, jb.z, jb.w, jb.y};  // BorrowResources (:234)
+    auto lent_run = [&](uint32_t eb, uint32_t ej, uint32_t k, uint32_t fin) {  // logged at once
+        if (lane == 0) {
+            const unsigned long long idx = atomicAdd(&a.ctl->n_lent, 1ull);
+            if (idx < a.lent_cap) {
+                mcs_lent_rec r;
+                r.lender = g;
+                r.borrower = eb;
+                r.job = ej;
+                r.node = k;
+                r.start_s = T;
+                r.finish_s = fin;
+                r.pad = 0u;
+                a.lent_log[idx] = r;
             }
-            break;  // time.Sleep(1 s), :250
         }
-        if (st.rq_head < st.next_arr) {  // ReadyQueue head (:255-272), no sleep
-            const uint32_t j = st.rq_head++;
-            const uint4 jb = jobs[j];
-            const uint32_t k = first_fit(jb.z, jb.w);
-            if (k != kEmpty) {
-                if (!place_own(j, k, jb)) {
-                    st.flags |= MCS_FLAG_OVERFLOW;
-                    break;
-                }
-            } else {
-                st.has_w = 1u;
-                st.w = j;
-                ++st.waited;
-            }
-            continue;
-        }
-        if (st.lq_len > 0u) {  // LentQueue head (:277-290)
-            const TrLq e = a.lq[(size_t)c * a.LQ + st.lq_head];
-            const uint32_t k = first_fit(e.c, e.m);
-            if (k != kEmpty) {
-                const uint32_t fin = T + e.dur;
-                if (e.dur != 0u && !commit(k, e.c, e.m, fin)) {
-                    st.flags |= MCS_FLAG_OVERFLOW;
-                    break;
-                }
-                if (lane == 0) {
-                    const unsigned long long idx = atomicAdd(&a.ctl->n_lent, 1ull);
-                    if (idx < a.lent_cap) {
-                        mcs_lent_rec r;
-                        r.lender = g;
-                        r.borrower = e.borrower;
-                        r.job = e.job;
-                        r.node = k;
-                        r.start_s = T;
-                        r.finish_s = fin;
-                        r.pad = 0u;
-                        a.lent_log[idx] = r;
-                    }
-                }
-                ++st.lent_runs;
-                st.lq_head = st.lq_head + 1u == a.LQ ? 0u : st.lq_head + 1u;
-                --st.lq_len;
-            }
-            break;  // sleep 1 s (:289)
-        }
-        break;  // idle sleep (:294)
-    }
+    };
+    auto ops = tr_step_ops([&](uint32_t j) { return jobs[j]; }, first_fit, commit, lent_head, lent_run);
+    const TrRecA req = tr_fifo_step(a, T, lane, j0, TrRegState{st}, ops).req;
 
     __syncthreads();
     // GetResourceUtilization (cluster.go:46-63) when a trader reads it at this tick: the state
@@ -412,13 +353,6 @@ __device__ __forceinline__ TrRecC post_cluster(const TradeArgs& a, uint32_t g, u
 }
 
 // ---------------------------------------------------------------------------------------------
-// ApproveTrade (trader.go:141-167) of the contract {cores 0, mem 0, time 0 s, price 0} that every
-// FIFO trade carries (the small-node contract over an empty Level1), on the responder's sample:
-// mcs_trader_dev.h's function, shared with the DELAY trader and the mcs_approve_trade mirror.
-__device__ __forceinline__ bool approve_zero_contract(uint32_t tc, uint32_t tm, float cu, float mu) {
-    return approve_trade_dev(tc, tm, cu, mu, 0u, 0u, 0u);
-}
-
 // Phases C and D: every cluster's borrower step and sample record (one lane each), then the
 // trader rounds (replicated) and the next tick.
 __global__ __launch_bounds__(64) void tr_trader_kernel(TradeArgs a) {
@@ -436,69 +370,7 @@ __global__ __launch_bounds__(64) void tr_trader_kernel(TradeArgs a) {
     unsigned long long n_trades = a.ctl->n_trades, n_won = a.ctl->n_won;
     uint32_t lflags = 0;
 
-    if (a.trader) {
-        for (uint32_t q0 = 0; q0 < Ct; q0 += kWave) {
-            const uint32_t ql = q0 + lane;
-            unsigned long long due = __ballot(ql < Ct && trs[ql].next_due <= T);
-            while (due) {  // RequestPolicyMonitor of requester q (trader.go:282-324), index order
-                const uint32_t q = q0 + (uint32_t)__builtin_ctzll(due);
-                due &= due - 1ull;
-                const TrRecC rq = rcs[q];
-                // policies [WaitTime, Utilization] (trader.go:55-62): WaitTime never breaks under
-                // FIFO (its average is only fed by /delay); Utilization (trader.go:127-130)
-                const bool broken = rq.cu > 0.8f || rq.mu > 0.8f;
-                if (!broken) {
-                    if (lane == 0) trs[q].next_due = T + a.period;
-                    __syncthreads();
-                    continue;
-                }
-                // Trade (trader.go:193-278): RequestResource to every other trader, index order
-                uint32_t napp = 0, winner = kEmpty;
-                for (uint32_t r0 = 0; r0 < Ct; r0 += kWave) {
-                    const uint32_t r = r0 + lane;
-                    bool app = false;
-                    if (r < Ct && r != q) {
-                        TrTrader t = trs[r];
-                        if (t.lock_id != 0u && T >= t.lock_until) t.lock_id = 0u;  // 20 s expiry
-                        if (t.lock_id == 0u) {  // else Approve:false (server.go:35-40)
-                            const TrRecC rr = rcs[r];
-                            app = approve_zero_contract(rr.total_c, rr.total_m, rr.cu, rr.mu);
-                            t.lock_id = t.next_id++;  // set even when not approving (:44-46)
-                            t.lock_until = T + a.lock_s;
-                        }
-                        trs[r] = t;
-                    }
-                    const unsigned long long ab = __ballot(app);
-                    napp += (uint32_t)__builtin_popcountll(ab);
-                    // every response echoes the requester's price (server.go:44): the Go heap of
-                    // equal keys pops the first push first (Appendix C), whose lock still matches
-                    // (nothing intervenes), and the zero allocation cannot fail -> first approver
-                    if (winner == kEmpty && ab) winner = r0 + (uint32_t)__builtin_ctzll(ab);
-                }
-                __syncthreads();
-                if (lane == 0) {
-                    if (winner != kEmpty) {
-                        trs[winner].lock_id = 0u;  // ApproveContract resets currentContract (:83)
-                        trs[q].vnodes += 1u;       // AddVirtualNode(0 cores, 0 memory)
-                        ++n_won;
-                    }
-                    if (n_trades < a.trade_cap) {
-                        mcs_trade_rec rec;
-                        rec.t_s = T;
-                        rec.requester = q;
-                        rec.winner = winner == kEmpty ? -1 : (int32_t)winner;
-                        rec.approvals = napp;
-                        a.trade_log[n_trades] = rec;
-                    } else {
-                        lflags |= MCS_FLAG_LOG_OVERFLOW;
-                    }
-                    trs[q].next_due = T + (winner != kEmpty ? a.ok_sleep : a.fail_sleep) + a.period;
-                }
-                ++n_trades;
-                __syncthreads();
-            }
-        }
-    }
+    if (a.trader) tr_trader_rounds_lds(a, T, lane, trs, rcs, n_trades, n_won, lflags);
 
     // the next tick: T+1 while any queue is busy, else the next arrival or trader round
     bool all_done = true, busy = false;
@@ -514,26 +386,16 @@ __global__ __launch_bounds__(64) void tr_trader_kernel(TradeArgs a) {
     const bool done_all = !__ballot(!all_done);
     const bool busy_any = __ballot(busy) != 0ull;
     nxt = wave_min_u32(nxt);
-    for (int o = 32; o > 0; o >>= 1) fl |= (uint32_t)__shfl_xor((int)fl, o);
+    fl = wave_or_u32(fl);
     __syncthreads();
     for (uint32_t q = lane; q < Ct; q += kWave) a.tr[q] = trs[q];
     if (lane == 0) {
         TrCtl* ctl = a.ctl;
-        uint32_t flags = ctl->flags | fl | lflags;
-        uint32_t done = 0, Tn = T;
-        const uint32_t fatal = MCS_FLAG_OVERFLOW | MCS_FLAG_LENT_OVERFLOW;
-        if (done_all || (flags & fatal)) {
-            done = 1u;
-        } else if (T >= a.t_max || (!busy_any && nxt == kEmpty)) {
-            done = 1u;
-            flags |= MCS_FLAG_T_MAX;
-        } else {
-            Tn = (busy_any || nxt <= T + 1u) ? T + 1u : nxt;
-        }
-        ctl->T = Tn;
-        ctl->done = done;
+        const TrNext nx = tr_next_tick(T, a.t_max, done_all, busy_any, nxt, ctl->flags | fl | lflags);
+        ctl->T = nx.Tn;
+        ctl->done = nx.done;
         ctl->ticks += 1u;
-        ctl->flags = flags;
+        ctl->flags = nx.flags;
         ctl->n_trades = n_trades;
         ctl->n_won = n_won;
     }

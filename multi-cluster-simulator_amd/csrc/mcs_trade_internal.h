@@ -33,7 +33,7 @@ constexpr uint32_t kTrMaxClusters = 1024;  // clusters in one trading system (tr
 struct TrCluster {
     uint32_t next_arr;  // first job (local index) not yet queued; ready queue = [rq_head, next_arr)
     uint32_t rq_head;
-    uint32_t has_w;     // WaitQueue head present (scheduler.go:219)
+    uint32_t has_w;     // WaitQueue head present (tr_fifo_step, mcs_trade_dev.h)
     uint32_t w;         // its local index
     uint32_t lq_head;   // LentQueue ring cursor and length
     uint32_t lq_len;

@@ -34,9 +34,8 @@
 // launch; every sweep is bounded (a timeout stops the run with an internal error).
 // Same results bit for bit as the three-kernel tick and the one-workgroup resident tick
 // (tests/test_gpu_trade.py).
-#include "mcs_trade_internal.h"
-#include "mcs_trader_dev.h"
-#include "mcs_wave.h"
+// The scheduler step, the arrivals, the trader rounds and the clock rule are mcs_trade_dev.h's.
+#include "mcs_trade_dev.h"
 
 namespace mcs {
 namespace {
@@ -62,10 +61,6 @@ constexpr uint32_t kMwNodes = 256;       // nodes per cluster
 constexpr uint32_t kX1Words = 10;        // granules of a cluster's post-A record
 constexpr uint32_t kSpinLimit = 1u << 20;  // sweeps per exchange before the run gives up
 
-// a wave's uint32 sum / OR on the DPP scans: VALU steps, no chain of LDS-pipe permutes (every
-// lane active)
-__device__ __forceinline__ uint32_t mw_wave_sum(uint32_t v) { return readlane(wave_scan_add_u32(v), 63u); }
-__device__ __forceinline__ uint32_t mw_wave_or(uint32_t v) { return readlane(wave_scan_or_u32(v), 63u); }
 // HBM this kernel's own wave wrote in an earlier tick and reads back (LentQueue entries)
 __device__ __forceinline__ uint64_t mld64(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -124,30 +119,6 @@ __device__ unsigned long long g_mw_tlog[kMwLogTicks * kMwMaxWg * kMwLogSlots];
     do {                     \
     } while (0)
 #endif
-
-constexpr uint32_t kStWords = sizeof(TrCluster) / 4u;
-static_assert(sizeof(TrCluster) % 4u == 0u && kStWords <= (uint32_t)kWave, "TrCluster in one VGPR");
-struct MwField {  // a TrCluster field held in lane f of a VGPR (phase A's cluster state)
-    uint32_t& v;
-    uint32_t f, lane;
-    __device__ __forceinline__ operator uint32_t() const { return readlane(v, f); }
-    __device__ __forceinline__ MwField& operator=(uint32_t x) {
-        v = lane == f ? x : v;
-        return *this;
-    }
-    __device__ __forceinline__ MwField& operator=(const MwField& o) { return *this = (uint32_t)o; }
-    __device__ __forceinline__ MwField& operator+=(uint32_t x) { return *this = (uint32_t)*this + x; }
-    __device__ __forceinline__ MwField& operator-=(uint32_t x) { return *this = (uint32_t)*this - x; }
-    __device__ __forceinline__ MwField& operator|=(uint32_t x) { return *this = (uint32_t)*this | x; }
-    __device__ __forceinline__ MwField& operator++() { return *this += 1u; }
-    __device__ __forceinline__ MwField& operator--() { return *this -= 1u; }
-    __device__ __forceinline__ uint32_t operator++(int) {
-        const uint32_t o = *this;
-        *this = o + 1u;
-        return o;
-    }
-};
-#define MST(field) (MwField{stv, (uint32_t)(offsetof(TrCluster, field) / 4u), lane})
 
 struct MwShared {  // (this workgroup's node vectors follow: kMwWaves * ns u64)
     // gathered each tick (X1): every cluster's request and queue state
@@ -252,8 +223,8 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
             uc += cp.x;
             um += cp.y;
         }
-        uc = mw_wave_sum(uc);
-        um = mw_wave_sum(um);
+        uc = wave_sum_u32(uc);
+        um = wave_sum_u32(um);
         if (lane == 0) {
             sh.capc[wave] = uc;
             sh.capm[wave] = um;
@@ -347,9 +318,9 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
                 const uint32_t v = (uint32_t)x, k = lane % 3u;
                 uint32_t m0 = lane < nw && k == 0u ? v : 0u, m1 = lane < nw && k == 1u ? v : 0u,
                          fb = lane < nw && k == 2u ? v : 0u;
-                m0 = mw_wave_or(m0);
-                m1 = mw_wave_or(m1);
-                fb = mw_wave_or(fb);
+                m0 = wave_or_u32(m0);
+                m1 = wave_or_u32(m1);
+                fb = wave_or_u32(fb);
                 const uint32_t g = lane;
                 const bool acc = ((g < 32u ? m0 >> g : m1 >> (g - 32u)) & 1u) != 0u;
                 if (acc && g < C && g / kMwWaves == wg && sh.rq_job[g] != kEmpty) {
@@ -403,14 +374,15 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
         // ---- phase A: this wave's cluster (tr_step_kernel) ----
         if (own) {
             uint32_t stv = lane < kStWords ? reinterpret_cast<const uint32_t*>(&sh.st[wave])[lane] : 0u;
+            const TrLaneState st{stv, lane};
             // the tick's job records, every load in flight at once: 64 records from the WaitQueue
             // head (else the ReadyQueue head), 64 arrival times from the first unqueued job, and
             // the LentQueue head entry
-            const uint32_t na0 = MST(next_arr);
+            const uint32_t na0 = TR_ST(next_arr);
             MW_MARK(0);
 
             // releases due at T (cluster.go:153-157), before the tick's decisions
-            if (MST(minf) <= T) {
+            if (TR_ST(minf) <= T) {
                 uint32_t lm = kEmpty, nrel = 0;
 #pragma unroll
                 for (int r = 0; r < kRows; ++r) {
@@ -427,28 +399,14 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
                         lm = f < lm ? f : lm;
                     }
                 }
-                MST(nrun) -= nrel;
-                MST(minf) = wave_min_u32(lm);
+                TR_ST(nrun) -= nrel;
+                TR_ST(minf) = wave_min_u32(lm);
             }
             MW_MARK(1);
             // arrivals up to T join the ReadyQueue (jobs are sorted by arrival)
-            uint32_t nat;  // the arrival second of the first job not yet queued (kEmpty: none)
-            {
-                const uint32_t n = (uint32_t)__builtin_popcountll(__ballot(awin <= T && na0 + lane < J));
-                MST(next_arr) = na0 + n;
-                if (n < (uint32_t)kWave) {
-                    nat = readlane(awin, n);
-                } else {
-                    while (MST(next_arr) < J) {
-                        const uint32_t i = MST(next_arr) + lane;
-                        const bool ok = i < J && jobs[i].x <= T;
-                        const uint32_t m = (uint32_t)__builtin_popcountll(__ballot(ok));
-                        MST(next_arr) += m;
-                        if (m < (uint32_t)kWave) break;
-                    }
-                    nat = MST(next_arr) < J ? jobs[MST(next_arr)].x : kEmpty;
-                }
-            }
+            const TrArrivals arr = tr_arrivals<64>(T, lane, 0u, na0, awin, jobs, J);
+            TR_ST(next_arr) = arr.next_arr;
+            const uint32_t nat = arr.nat;  // the arrival second of the first job not yet queued (kEmpty: none)
             MW_MARK(2);
             auto job_at = [&](uint32_t j) -> uint4 {
                 const uint32_t d = j - hwb;
@@ -495,84 +453,24 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
                         }
                     frm &= ~(1u << row);
                 }
-                ++MST(nrun);
-                MST(peak) = MST(nrun) > MST(peak) ? MST(nrun) : MST(peak);
-                MST(minf) = f < MST(minf) ? f : MST(minf);
+                ++TR_ST(nrun);
+                TR_ST(peak) = TR_ST(nrun) > TR_ST(peak) ? TR_ST(nrun) : TR_ST(peak);
+                TR_ST(minf) = f < TR_ST(minf) ? f : TR_ST(minf);
                 return true;
             };
-            auto place_own = [&](uint32_t j, uint32_t kn, uint4 jb) -> bool {
-                const uint32_t f = T + jb.y;
-                if (jb.y != 0u && !commit(kn, jb.z, jb.w, f)) return false;
-                if (lane == 0) {
-                    a.out_node[j0 + j] = (int32_t)kn;
-                    a.out_start[j0 + j] = T;
-                    a.out_finish[j0 + j] = f;
-                }
-                ++MST(placed);
-                ++MST(decided);
-                return true;
+            // the lent-run record is written after X1, at the index every workgroup derives from the
+            // tick's lent bits (no global counter on this path)
+            auto lent_run = [&](uint32_t eb, uint32_t ej, uint32_t kn, uint32_t f) {
+                lr_b = eb;
+                lr_j = ej;
+                lr_n = kn;
+                lr_f = f;
             };
-
-            TrRecA req{kEmpty, 0u, 0u, 0u};
-            lent_now = 0u;
-            for (;;) {
-                if (MST(has_w)) {  // WaitQueue head (scheduler.go:219-251)
-                    const uint4 jb = job_at(MST(w));
-                    const uint32_t kn = first_fit(jb.z, jb.w);
-                    if (kn != kEmpty) {
-                        if (!place_own(MST(w), kn, jb)) {
-                            MST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                        MST(has_w) = 0u;
-                    } else if (a.borrow) {
-                        req = TrRecA{MST(w), jb.z, jb.w, jb.y};  // BorrowResources (:234)
-                    }
-                    break;  // time.Sleep(1 s), :250
-                }
-                if (MST(rq_head) < MST(next_arr)) {  // ReadyQueue head (:255-272), no sleep
-                    const uint32_t j = MST(rq_head)++;
-                    const uint4 jb = job_at(j);
-                    const uint32_t kn = first_fit(jb.z, jb.w);
-                    if (kn != kEmpty) {
-                        if (!place_own(j, kn, jb)) {
-                            MST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                    } else {
-                        MST(has_w) = 1u;
-                        MST(w) = j;
-                        ++MST(waited);
-                    }
-                    continue;
-                }
-                if (MST(lq_len) > 0u) {  // LentQueue head (:277-290), appended by this wave in phase B
-                    const uint64_t w0 = readlane((uint32_t)lqw, 0) | ((uint64_t)readlane((uint32_t)(lqw >> 32), 0) << 32);
-                    const uint32_t eb = (uint32_t)w0, ej = (uint32_t)(w0 >> 32);
-                    const uint32_t ec = readlane((uint32_t)lqw, 1), em = readlane((uint32_t)(lqw >> 32), 1);
-                    const uint32_t ed = readlane((uint32_t)lqw, 2);
-                    const uint32_t kn = first_fit(ec, em);
-                    if (kn != kEmpty) {
-                        const uint32_t f = T + ed;
-                        if (ed != 0u && !commit(kn, ec, em, f)) {
-                            MST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                        // the lent-run record is written after X1, at the index every workgroup
-                        // derives from the tick's lent bits (no global counter on this path)
-                        lr_b = eb;
-                        lr_j = ej;
-                        lr_n = kn;
-                        lr_f = f;
-                        lent_now = 4u;
-                        ++MST(lent_runs);
-                        MST(lq_head) = MST(lq_head) + 1u == a.LQ ? 0u : MST(lq_head) + 1u;
-                        --MST(lq_len);
-                    }
-                    break;  // sleep 1 s (:289)
-                }
-                break;  // idle sleep (:294)
-            }
+            // (the LentQueue head: appended by this wave in phase B, prefetched since)
+            auto ops = tr_step_ops(job_at, first_fit, commit, [&] { return tr_lent_from_lanes(lqw); }, lent_run);
+            const TrStepOut so = tr_fifo_step(a, T, lane, j0, st, ops);
+            const TrRecA req = so.req;
+            lent_now = so.lent ? 4u : 0u;
             MW_MARK(3);
 
             // GetResourceUtilization (cluster.go:46-63) on the ticks a trader reads it: an exact
@@ -584,10 +482,10 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
                     fc += (uint32_t)v;
                     fm += (uint32_t)(v >> 32);
                 }
-                const float sc = (float)(int32_t)(sh.capc[wave] - mw_wave_sum(fc));
-                const float sm = (float)(int32_t)(sh.capm[wave] - mw_wave_sum(fm));
-                MST(cu) = __float_as_uint(__fdiv_rn(sc, (float)MST(total_c)));
-                MST(mu) = __float_as_uint(__fdiv_rn(sm, (float)MST(total_m)));
+                const float sc = (float)(int32_t)(sh.capc[wave] - wave_sum_u32(fc));
+                const float sm = (float)(int32_t)(sh.capm[wave] - wave_sum_u32(fm));
+                TR_ST(cu) = __float_as_uint(__fdiv_rn(sc, (float)TR_ST(total_c)));
+                TR_ST(mu) = __float_as_uint(__fdiv_rn(sm, (float)TR_ST(total_m)));
             }
             // the post-A record, one granule per lane
             uint32_t xv = 0u;
@@ -595,21 +493,21 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
             xv = lane == 1 ? req.c : xv;
             xv = lane == 2 ? req.m : xv;
             xv = lane == 3 ? req.dur : xv;
-            const uint32_t qs = (MST(has_w) ? 1u : 0u) | (MST(rq_head) < MST(next_arr) ? 2u : 0u) | lent_now |
-                                (MST(lq_len) > 0u ? 8u : 0u);
+            const uint32_t qs = (TR_ST(has_w) ? 1u : 0u) | (TR_ST(rq_head) < TR_ST(next_arr) ? 2u : 0u) | lent_now |
+                                (TR_ST(lq_len) > 0u ? 8u : 0u);
             xv = lane == 4 ? qs : xv;
-            xv = lane == 5 ? (uint32_t)MST(decided) : xv;
+            xv = lane == 5 ? (uint32_t)TR_ST(decided) : xv;
             xv = lane == 6 ? nat : xv;
-            xv = lane == 7 ? (uint32_t)MST(flags) : xv;
-            xv = lane == 8 ? (uint32_t)MST(cu) : xv;
-            xv = lane == 9 ? (uint32_t)MST(mu) : xv;
+            xv = lane == 7 ? (uint32_t)TR_ST(flags) : xv;
+            xv = lane == 8 ? (uint32_t)TR_ST(cu) : xv;
+            xv = lane == 9 ? (uint32_t)TR_ST(mu) : xv;
             if (lane < kX1Words) put(gx1 + (size_t)lane * kTrResMaxClusters + c, tag1, xv);
             MW_TLOG(it, wave, wall_clock64());
             if (lane < kStWords) reinterpret_cast<uint32_t*>(&sh.st[wave])[lane] = stv;
             // the next tick's records (only phase A moves these cursors; a WaitQueue head that C/D
             // moves to the BorrowedQueue leaves the ReadyQueue head inside the same window, or
             // job_at loads it directly)
-            prefetch_jobs(MST(has_w) ? MST(w) : MST(rq_head), MST(next_arr));
+            prefetch_jobs(TR_ST(has_w) ? TR_ST(w) : TR_ST(rq_head), TR_ST(next_arr));
         }
         MW_MARK(4);
 
@@ -719,47 +617,8 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
             }
             unsigned long long n_trades = sh.n_trades, n_won = sh.n_won;
             uint32_t lflags = 0;
-            if (a.trader && !timed_out) {
-                const bool due = g < C && t.next_due <= T;
-                const bool broken = cu > 0.8f || mu > 0.8f;  // Utilization (trader.go:127-130)
-                if (due && !broken) t.next_due = T + a.period;
-                // ApproveTrade of this lane as a responder: its sample is fixed for the tick
-                const bool appr = g < C && approve_trade_dev(tot_c, tot_m, cu, mu, 0u, 0u, 0u);
-                unsigned long long pend = __ballot(due && broken);
-                while (pend) {  // RequestPolicyMonitor of requester q (trader.go:282-324)
-                    const uint32_t q = (uint32_t)__builtin_ctzll(pend);
-                    pend &= pend - 1ull;
-                    bool app = false;
-                    if (g < C && g != q) {  // RequestResource, index order
-                        if (t.lock_id != 0u && T >= t.lock_until) t.lock_id = 0u;  // 20 s expiry
-                        if (t.lock_id == 0u) {  // else Approve:false (server.go:35-40)
-                            app = appr;
-                            t.lock_id = t.next_id++;  // set even when not approving (:44-46)
-                            t.lock_until = T + a.lock_s;
-                        }
-                    }
-                    const unsigned long long ab = __ballot(app);
-                    const uint32_t napp = (uint32_t)__builtin_popcountll(ab);
-                    const uint32_t winner = ab ? (uint32_t)__builtin_ctzll(ab) : kEmpty;
-                    if (winner != kEmpty) {
-                        if (g == winner) t.lock_id = 0u;  // ApproveContract unlocks (:83)
-                        if (g == q) t.vnodes += 1u;       // AddVirtualNode(0 cores, 0 memory)
-                        ++n_won;
-                    }
-                    if (g == q) t.next_due = T + (winner != kEmpty ? a.ok_sleep : a.fail_sleep) + a.period;
-                    if (lane == 0 && wg == 0) {  // (workgroup 0 keeps the log)
-                        if (n_trades < a.trade_cap) {
-                            mcs_trade_rec rec;
-                            rec.t_s = T;
-                            rec.requester = q;
-                            rec.winner = winner == kEmpty ? -1 : (int32_t)winner;
-                            rec.approvals = napp;
-                            a.trade_log[n_trades] = rec;
-                        }
-                    }
-                    if (n_trades >= a.trade_cap) lflags |= MCS_FLAG_LOG_OVERFLOW;
-                    ++n_trades;
-                }
+            if (a.trader && !timed_out) {  // (workgroup 0 keeps the log)
+                tr_trader_rounds(a, T, g, g < C, TrSample{cu, mu, tot_c, tot_m}, wg == 0, t, n_trades, n_won, lflags);
                 if (g < C) sh.trs[g] = t;
             }
             // the next tick: T+1 while any queue is busy, else the next arrival or trader round
@@ -768,28 +627,17 @@ __global__ __launch_bounds__(kMwThreads) void tr_mw_kernel(TradeArgs a, unsigned
             const bool done_all = !__ballot(!done_g);
             const bool busy_any = __ballot(busy != 0u) != 0ull;
             nxt = wave_min_u32(nxt);
-            fl = mw_wave_or(fl);
+            fl = wave_or_u32(fl);
             if (lane == 0) {
-                uint32_t flags = sh.flags | fl | lflags;
-                uint32_t done = 0, Tn = T;
-                const uint32_t fatal = MCS_FLAG_OVERFLOW | MCS_FLAG_LENT_OVERFLOW;
-                sh.tmax_now = 0u;
-                if (timed_out) {
-                    done = 2u;
-                } else if (done_all || (flags & fatal)) {
-                    done = 1u;
-                } else if (T >= a.t_max || (!busy_any && nxt == kEmpty)) {
-                    done = 1u;
-                    flags |= MCS_FLAG_T_MAX;
-                    sh.tmax_now = 1u;
-                } else {
-                    Tn = (busy_any || nxt <= T + 1u) ? T + 1u : nxt;
-                }
-                sh.T = Tn;
-                sh.done = done;
+                const uint32_t flags = sh.flags | fl | lflags;
+                const TrNext nx = timed_out ? TrNext{T, 2u, flags, 0u}
+                                            : tr_next_tick(T, a.t_max, done_all, busy_any, nxt, flags);
+                sh.tmax_now = nx.tmax_now;
+                sh.T = nx.Tn;
+                sh.done = nx.done;
                 sh.ticks += 1u;
                 sh.n_lent_next = sh.n_lent + lent_tick;
-                sh.flags = flags;
+                sh.flags = nx.flags;
                 sh.n_trades = n_trades;
                 sh.n_won = n_won;
             }
@@ -962,21 +810,8 @@ hipError_t launch_trade_mw(const TradeArgs& a, unsigned long long* gx_uc, unsign
     if (st != hipSuccess) return st;
     st = hipMemsetAsync(gx_c, 0, trade_mw_granules(a.Ct) * 8u, s);
     if (st != hipSuccess) return st;
-    const void* fn = a.S == 4u * kWave   ? (const void*)tr_mw_kernel<4>
-                     : a.S == 8u * kWave ? (const void*)tr_mw_kernel<8>
-                                         : (const void*)tr_mw_kernel<16>;
-    st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (st != hipSuccess) return st;
-    if (a.S == 4u * kWave)
-        hipLaunchKernelGGL(tr_mw_kernel<4>, dim3(nblk), dim3(kMwThreads), lds, s, a, gx_uc, gx_c, tick_budget,
-                           nwg, stride, tick0, force_uc ? 1u : 0u);
-    else if (a.S == 8u * kWave)
-        hipLaunchKernelGGL(tr_mw_kernel<8>, dim3(nblk), dim3(kMwThreads), lds, s, a, gx_uc, gx_c, tick_budget,
-                           nwg, stride, tick0, force_uc ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(tr_mw_kernel<16>, dim3(nblk), dim3(kMwThreads), lds, s, a, gx_uc, gx_c, tick_budget,
-                           nwg, stride, tick0, force_uc ? 1u : 0u);
-    return hipGetLastError();
+    return launch_by_rows(tr_mw_kernel<4>, tr_mw_kernel<8>, tr_mw_kernel<16>, a.S, dim3(nblk), dim3(kMwThreads), lds,
+                          s, a, gx_uc, gx_c, tick_budget, nwg, stride, tick0, force_uc ? 1u : 0u);
 }
 
 }  // namespace mcs

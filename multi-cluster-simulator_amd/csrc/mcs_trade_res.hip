@@ -26,9 +26,8 @@
 // max(capacity, JSON availability) per resource is below 2^24 (every partial sum is then an
 // integer float32 represents exactly).  Same results bit for bit as the three-kernel tick
 // (tests/test_gpu_trade.py, MCS_TRADE_RESIDENT=0 forces that path).
-#include "mcs_trade_internal.h"
-#include "mcs_trader_dev.h"
-#include "mcs_wave.h"
+// The scheduler step, the arrivals, the trader rounds and the clock rule are mcs_trade_dev.h's.
+#include "mcs_trade_dev.h"
 
 namespace mcs {
 namespace {
@@ -36,11 +35,6 @@ namespace {
 constexpr int kResWaves = 16;
 constexpr int kResCpw = 4;      // clusters per wave
 constexpr uint32_t kResMaxNodes = 256;
-
-__device__ __forceinline__ uint32_t rwave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
 
 // HBM this kernel wrote and reads back (slot payloads, LentQueue entries): all of it is written and
 // read by the one CU, whose vector L1 sees its own stores, so workgroup-scope loads (served by the
@@ -52,31 +46,6 @@ __device__ __forceinline__ uint64_t rld64(const unsigned long long* p) {
 __device__ __forceinline__ uint32_t rld32(const uint32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-
-// a TrCluster field held in lane f of a VGPR (phase A's per-cluster state)
-constexpr uint32_t kStWords = sizeof(TrCluster) / 4u;
-static_assert(sizeof(TrCluster) % 4u == 0u && kStWords <= (uint32_t)kWave, "TrCluster in one VGPR");
-struct LaneField {
-    uint32_t& v;
-    uint32_t f, lane;
-    __device__ __forceinline__ operator uint32_t() const { return readlane(v, f); }
-    __device__ __forceinline__ LaneField& operator=(uint32_t x) {
-        v = lane == f ? x : v;
-        return *this;
-    }
-    __device__ __forceinline__ LaneField& operator=(const LaneField& o) { return *this = (uint32_t)o; }
-    __device__ __forceinline__ LaneField& operator+=(uint32_t x) { return *this = (uint32_t)*this + x; }
-    __device__ __forceinline__ LaneField& operator-=(uint32_t x) { return *this = (uint32_t)*this - x; }
-    __device__ __forceinline__ LaneField& operator|=(uint32_t x) { return *this = (uint32_t)*this | x; }
-    __device__ __forceinline__ LaneField& operator++() { return *this += 1u; }
-    __device__ __forceinline__ LaneField& operator--() { return *this -= 1u; }
-    __device__ __forceinline__ uint32_t operator++(int) {
-        const uint32_t o = *this;
-        *this = o + 1u;
-        return o;
-    }
-};
-#define ST(field) (LaneField{stv, (uint32_t)(offsetof(TrCluster, field) / 4u), lane})
 
 struct ResShared {  // (the node vectors follow, Ct * ns u64)
     TrXRec x[kTrResMaxClusters];
@@ -156,8 +125,8 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
                 uc += cp.x;
                 um += cp.y;
             }
-            uc = rwave_sum(uc);
-            um = rwave_sum(um);
+            uc = wave_sum_u32(uc);
+            um = wave_sum_u32(um);
             if (lane == 0) {
                 sh.capc[c] = uc;
                 sh.capm[c] = um;
@@ -226,13 +195,12 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
             const uint4* __restrict__ jobs = a.jobs + j0;
             const size_t sb = (size_t)c * S;
             const uint32_t vn = sh.trs[c].vnodes;
-            // the cluster's queue state: word f of its TrCluster in lane f of one VGPR (uniform
-            // reads are v_readlane, writes a lane select; never written under a lane-divergent
-            // branch)
+            // the cluster's queue state: word f of its TrCluster in lane f of one VGPR
             uint32_t stv = lane < kStWords ? reinterpret_cast<const uint32_t*>(&sh.st[c])[lane] : 0u;
+            const TrLaneState st{stv, lane};
 
             // releases due at T (cluster.go:153-157), before the tick's decisions
-            if (ST(minf) <= T) {
+            if (TR_ST(minf) <= T) {
                 // the expired slots' {node, payload} loads of up to 8 rows issued together, then
                 // their node updates
                 constexpr int kG = kResRows < 4 ? kResRows : 4;
@@ -264,31 +232,15 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
                         }
                     }
                 }
-                ST(nrun) -= rwave_sum(nrel);
-                ST(minf) = wave_min_u32(lm);
+                TR_ST(nrun) -= wave_sum_u32(nrel);
+                TR_ST(minf) = wave_min_u32(lm);
             }
             RS_MARK(1);
             // arrivals up to T join the ReadyQueue (jobs are sorted by arrival): the arrival
             // window, then direct loads past a full window
-            uint32_t nat;  // the arrival second of the first job not yet queued (kEmpty: none)
-            {
-                const uint32_t na = ST(next_arr);
-                const uint32_t n = (uint32_t)__builtin_popcountll(
-                    (__ballot(awin <= T && na + (lane & 15u) < J) >> wl) & 0xffffull);
-                ST(next_arr) = na + n;
-                if (n < 16u) {
-                    nat = readlane(awin, wl + n);
-                } else {
-                    while (ST(next_arr) < J) {
-                        const uint32_t i = ST(next_arr) + lane;
-                        const bool ok = i < J && jobs[i].x <= T;
-                        const uint32_t m = (uint32_t)__builtin_popcountll(__ballot(ok));
-                        ST(next_arr) += m;
-                        if (m < (uint32_t)kWave) break;
-                    }
-                    nat = ST(next_arr) < J ? jobs[ST(next_arr)].x : kEmpty;
-                }
-            }
+            const TrArrivals arr = tr_arrivals<16>(T, lane, wl, TR_ST(next_arr), awin, jobs, J);
+            TR_ST(next_arr) = arr.next_arr;
+            const uint32_t nat = arr.nat;  // the arrival second of the first job not yet queued (kEmpty: none)
             // record j: from the head window when it holds it
             auto job_at = [&](uint32_t j) -> uint4 {
                 const uint32_t d = j - hb;
@@ -337,92 +289,37 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
                         if ((uint32_t)r == row) wf[r] = f;
                     wfrm &= ~(1u << row);
                 }
-                ++ST(nrun);
-                ST(peak) = ST(nrun) > ST(peak) ? ST(nrun) : ST(peak);
-                ST(minf) = f < ST(minf) ? f : ST(minf);
+                ++TR_ST(nrun);
+                TR_ST(peak) = TR_ST(nrun) > TR_ST(peak) ? TR_ST(nrun) : TR_ST(peak);
+                TR_ST(minf) = f < TR_ST(minf) ? f : TR_ST(minf);
                 return true;
             };
-            auto place_own = [&](uint32_t j, uint32_t kn, uint4 jb) -> bool {
-                const uint32_t f = T + jb.y;
-                if (jb.y != 0u && !commit(kn, jb.z, jb.w, f)) return false;
+            // the LentQueue head, written by this wave in phase B
+            auto lent_head = [&]() -> TrLent {
+                const TrLq* q = a.lq + (size_t)c * a.LQ + TR_ST(lq_head);
+                const uint64_t w0 = rld64(reinterpret_cast<const unsigned long long*>(q));
+                const uint64_t w1 = rld64(reinterpret_cast<const unsigned long long*>(q) + 1);
+                const uint64_t w2 = rld64(reinterpret_cast<const unsigned long long*>(q) + 2);
+                return TrLent{(uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32), (uint32_t)w2};
+            };
+            auto lent_run = [&](uint32_t eb, uint32_t ej, uint32_t kn, uint32_t f) {  // logged at once
                 if (lane == 0) {
-                    a.out_node[j0 + j] = (int32_t)kn;
-                    a.out_start[j0 + j] = T;
-                    a.out_finish[j0 + j] = f;
+                    const unsigned long long idx = atomicAdd(&sh.n_lent, 1ull);
+                    if (idx < a.lent_cap) {
+                        mcs_lent_rec rec;
+                        rec.lender = c;
+                        rec.borrower = eb;
+                        rec.job = ej;
+                        rec.node = kn;
+                        rec.start_s = T;
+                        rec.finish_s = f;
+                        rec.pad = 0u;
+                        a.lent_log[idx] = rec;
+                    }
                 }
-                ++ST(placed);
-                ++ST(decided);
-                return true;
             };
-
-            TrRecA req{kEmpty, 0u, 0u, 0u};
-            for (;;) {
-                if (ST(has_w)) {  // WaitQueue head (scheduler.go:219-251)
-                    const uint4 jb = job_at(ST(w));
-                    const uint32_t kn = first_fit(jb.z, jb.w);
-                    if (kn != kEmpty) {
-                        if (!place_own(ST(w), kn, jb)) {
-                            ST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                        ST(has_w) = 0u;
-                    } else if (a.borrow) {
-                        req = TrRecA{ST(w), jb.z, jb.w, jb.y};  // BorrowResources (:234)
-                    }
-                    break;  // time.Sleep(1 s), :250
-                }
-                if (ST(rq_head) < ST(next_arr)) {  // ReadyQueue head (:255-272), no sleep
-                    const uint32_t j = ST(rq_head)++;
-                    const uint4 jb = job_at(j);
-                    const uint32_t kn = first_fit(jb.z, jb.w);
-                    if (kn != kEmpty) {
-                        if (!place_own(j, kn, jb)) {
-                            ST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                    } else {
-                        ST(has_w) = 1u;
-                        ST(w) = j;
-                        ++ST(waited);
-                    }
-                    continue;
-                }
-                if (ST(lq_len) > 0u) {  // LentQueue head (:277-290), written by this wave in phase B
-                    const TrLq* q = a.lq + (size_t)c * a.LQ + ST(lq_head);
-                    const uint64_t w0 = rld64(reinterpret_cast<const unsigned long long*>(q));
-                    const uint64_t w1 = rld64(reinterpret_cast<const unsigned long long*>(q) + 1);
-                    const uint64_t w2 = rld64(reinterpret_cast<const unsigned long long*>(q) + 2);
-                    const uint32_t eb = (uint32_t)w0, ej = (uint32_t)(w0 >> 32);
-                    const uint32_t ec = (uint32_t)w1, em = (uint32_t)(w1 >> 32), ed = (uint32_t)w2;
-                    const uint32_t kn = first_fit(ec, em);
-                    if (kn != kEmpty) {
-                        const uint32_t f = T + ed;
-                        if (ed != 0u && !commit(kn, ec, em, f)) {
-                            ST(flags) |= MCS_FLAG_OVERFLOW;
-                            break;
-                        }
-                        if (lane == 0) {
-                            const unsigned long long idx = atomicAdd(&sh.n_lent, 1ull);
-                            if (idx < a.lent_cap) {
-                                mcs_lent_rec rec;
-                                rec.lender = c;
-                                rec.borrower = eb;
-                                rec.job = ej;
-                                rec.node = kn;
-                                rec.start_s = T;
-                                rec.finish_s = f;
-                                rec.pad = 0u;
-                                a.lent_log[idx] = rec;
-                            }
-                        }
-                        ++ST(lent_runs);
-                        ST(lq_head) = ST(lq_head) + 1u == a.LQ ? 0u : ST(lq_head) + 1u;
-                        --ST(lq_len);
-                    }
-                    break;  // sleep 1 s (:289)
-                }
-                break;  // idle sleep (:294)
-            }
+            auto ops = tr_step_ops(job_at, first_fit, commit, lent_head, lent_run);
+            const TrRecA req = tr_fifo_step(a, T, lane, j0, st, ops).req;
 
             RS_MARK(3);
             // GetResourceUtilization (cluster.go:46-63) on the ticks a trader reads it: an exact
@@ -435,26 +332,26 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
                     fm += (uint32_t)(v >> 32);
                 }
                 // (mod 2^32: the signed sum, < 2^24 in size)
-                const float sc = (float)(int32_t)(sh.capc[c] - rwave_sum(fc));
-                const float sm = (float)(int32_t)(sh.capm[c] - rwave_sum(fm));
-                ST(cu) = __float_as_uint(__fdiv_rn(sc, (float)ST(total_c)));
-                ST(mu) = __float_as_uint(__fdiv_rn(sm, (float)ST(total_m)));
+                const float sc = (float)(int32_t)(sh.capc[c] - wave_sum_u32(fc));
+                const float sm = (float)(int32_t)(sh.capm[c] - wave_sum_u32(fm));
+                TR_ST(cu) = __float_as_uint(__fdiv_rn(sc, (float)TR_ST(total_c)));
+                TR_ST(mu) = __float_as_uint(__fdiv_rn(sm, (float)TR_ST(total_m)));
             }
             if (lane == 0) {
                 TrXRec x;
                 x.req = req;
                 x.n = N;
-                x.has_w = ST(has_w);
-                x.lq_len = ST(lq_len);
-                x.rq_busy = ST(rq_head) < ST(next_arr) ? 1u : 0u;
-                x.decided = ST(decided);
+                x.has_w = TR_ST(has_w);
+                x.lq_len = TR_ST(lq_len);
+                x.rq_busy = TR_ST(rq_head) < TR_ST(next_arr) ? 1u : 0u;
+                x.decided = TR_ST(decided);
                 x.J = J;
                 x.next_arr_t = nat;
-                x.flags = ST(flags);
-                x.cu = __uint_as_float(ST(cu));
-                x.mu = __uint_as_float(ST(mu));
-                x.total_c = ST(total_c);
-                x.total_m = ST(total_m);
+                x.flags = TR_ST(flags);
+                x.cu = __uint_as_float(TR_ST(cu));
+                x.mu = __uint_as_float(TR_ST(mu));
+                x.total_c = TR_ST(total_c);
+                x.total_m = TR_ST(total_m);
                 sh.x[c] = x;
             }
 #pragma unroll
@@ -603,47 +500,7 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
             unsigned long long n_trades = sh.n_trades, n_won = sh.n_won;
             uint32_t lflags = 0;
             if (a.trader) {
-                const bool due = g < C && t.next_due <= T;
-                const bool broken = cu > 0.8f || mu > 0.8f;  // Utilization (trader.go:127-130)
-                if (due && !broken) t.next_due = T + a.period;
-                // ApproveTrade of this lane as a responder: its sample is fixed for the tick
-                const bool appr = g < C && approve_trade_dev(tot_c, tot_m, cu, mu, 0u, 0u, 0u);
-                unsigned long long pend = __ballot(due && broken);
-                while (pend) {  // RequestPolicyMonitor of requester q (trader.go:282-324)
-                    const uint32_t q = (uint32_t)__builtin_ctzll(pend);
-                    pend &= pend - 1ull;
-                    bool app = false;
-                    if (g < C && g != q) {  // RequestResource, index order
-                        if (t.lock_id != 0u && T >= t.lock_until) t.lock_id = 0u;  // 20 s expiry
-                        if (t.lock_id == 0u) {  // else Approve:false (server.go:35-40)
-                            app = appr;
-                            t.lock_id = t.next_id++;  // set even when not approving (:44-46)
-                            t.lock_until = T + a.lock_s;
-                        }
-                    }
-                    const unsigned long long ab = __ballot(app);
-                    const uint32_t napp = (uint32_t)__builtin_popcountll(ab);
-                    const uint32_t winner = ab ? (uint32_t)__builtin_ctzll(ab) : kEmpty;
-                    if (winner != kEmpty) {
-                        if (g == winner) t.lock_id = 0u;  // ApproveContract unlocks (:83)
-                        if (g == q) t.vnodes += 1u;       // AddVirtualNode(0 cores, 0 memory)
-                        ++n_won;
-                    }
-                    if (g == q) t.next_due = T + (winner != kEmpty ? a.ok_sleep : a.fail_sleep) + a.period;
-                    if (lane == 0) {
-                        if (n_trades < a.trade_cap) {
-                            mcs_trade_rec rec;
-                            rec.t_s = T;
-                            rec.requester = q;
-                            rec.winner = winner == kEmpty ? -1 : (int32_t)winner;
-                            rec.approvals = napp;
-                            a.trade_log[n_trades] = rec;
-                        } else {
-                            lflags |= MCS_FLAG_LOG_OVERFLOW;
-                        }
-                    }
-                    ++n_trades;
-                }
+                tr_trader_rounds(a, T, g, g < C, TrSample{cu, mu, tot_c, tot_m}, true, t, n_trades, n_won, lflags);
                 if (g < C) sh.trs[g] = t;
             }
             // the next tick: T+1 while any queue is busy, else the next arrival or trader round
@@ -652,24 +509,13 @@ __global__ __launch_bounds__(kResWaves * kWave) void tr_resident_kernel(TradeArg
             const bool done_all = !__ballot(!done_g);
             const bool busy_any = __ballot(busy != 0u) != 0ull;
             nxt = wave_min_u32(nxt);
-            for (int o = 32; o > 0; o >>= 1) fl |= (uint32_t)__shfl_xor((int)fl, o);
-            lflags = (uint32_t)__shfl((int)lflags, 0);
+            fl = wave_or_u32(fl);
             if (lane == 0) {
-                uint32_t flags = sh.flags | fl | lflags;
-                uint32_t done = 0, Tn = T;
-                const uint32_t fatal = MCS_FLAG_OVERFLOW | MCS_FLAG_LENT_OVERFLOW;
-                if (done_all || (flags & fatal)) {
-                    done = 1u;
-                } else if (T >= a.t_max || (!busy_any && nxt == kEmpty)) {
-                    done = 1u;
-                    flags |= MCS_FLAG_T_MAX;
-                } else {
-                    Tn = (busy_any || nxt <= T + 1u) ? T + 1u : nxt;
-                }
-                sh.T = Tn;
-                sh.done = done;
+                const TrNext nx = tr_next_tick(T, a.t_max, done_all, busy_any, nxt, sh.flags | fl | lflags);
+                sh.T = nx.Tn;
+                sh.done = nx.done;
                 sh.ticks += 1u;
-                sh.flags = flags;
+                sh.flags = nx.flags;
                 sh.n_trades = n_trades;
                 sh.n_won = n_won;
             }
@@ -728,18 +574,8 @@ bool trade_resident_shape(const TradeArgs& a) {
 hipError_t launch_trade_resident(const TradeArgs& a, uint32_t tick_budget, size_t lds, hipStream_t s) {
     // 256 / 512 slots per cluster: 16 / 32 VGPRs of finish times per wave; 1024: 64 (that variant
     // spills registers)
-    const void* fn = a.S == 4u * kWave   ? (const void*)tr_resident_kernel<4>
-                     : a.S == 8u * kWave ? (const void*)tr_resident_kernel<8>
-                                         : (const void*)tr_resident_kernel<16>;
-    const hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (st != hipSuccess) return st;
-    if (a.S == 4u * kWave)
-        hipLaunchKernelGGL(tr_resident_kernel<4>, dim3(1), dim3(kResWaves * kWave), lds, s, a, tick_budget);
-    else if (a.S == 8u * kWave)
-        hipLaunchKernelGGL(tr_resident_kernel<8>, dim3(1), dim3(kResWaves * kWave), lds, s, a, tick_budget);
-    else
-        hipLaunchKernelGGL(tr_resident_kernel<16>, dim3(1), dim3(kResWaves * kWave), lds, s, a, tick_budget);
-    return hipGetLastError();
+    return launch_by_rows(tr_resident_kernel<4>, tr_resident_kernel<8>, tr_resident_kernel<16>, a.S, dim3(1),
+                          dim3(kResWaves * kWave), lds, s, a, tick_budget);
 }
 
 }  // namespace mcs

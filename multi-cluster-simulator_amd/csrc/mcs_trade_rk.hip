@@ -32,9 +32,8 @@
 // caller's all-gather in between, so 2- and 4-rank runs over gloo cover this path on one GPU.
 // Same results bit for bit as the three-kernel tick and the oracle (tests/test_gpu_trade.py,
 // tests/trade_2rank.py).
-#include "mcs_trade_internal.h"
-#include "mcs_trader_dev.h"
-#include "mcs_wave.h"
+// The scheduler step, the arrivals, the trader rounds and the clock rule are mcs_trade_dev.h's.
+#include "mcs_trade_dev.h"
 
 namespace mcs {
 namespace {
@@ -57,9 +56,8 @@ static_assert(kRkWords * 4u == sizeof(TrXRec), "record size");
 // some node with free_c > 64 (no G table: phase B scans the snapshot)
 constexpr uint32_t kQsW = 1u, kQsRq = 2u, kQsLent = 4u, kQsLq = 8u, kQsDone = 16u, kQsBig = 32u;
 
-// a wave's uint32 sum (wrapping), on the DPP scan: VALU steps, no LDS-pipe round trips
-__device__ __forceinline__ uint32_t rk_wave_sum(uint32_t v) { return readlane(wave_scan_add_u32(v), 63u); }
-// a wave's OR of a flags word: one ballot per bit some lane holds (none on most ticks)
+// a wave's OR of a flags word: one ballot per bit some lane holds (none on most ticks: one ballot,
+// where mcs_wave.h's wave_or_u32 always runs its scan)
 __device__ __forceinline__ uint32_t rk_wave_or(uint32_t v) {
     uint32_t r = 0u;
     if (__ballot(v != 0u))
@@ -95,33 +93,9 @@ __device__ __forceinline__ uint32_t* rk_gtab(const TradeArgs& a, unsigned char* 
            (size_t)c * 64u;
 }
 
-constexpr uint32_t kStW = sizeof(TrCluster) / 4u;
 constexpr uint32_t kTrW = sizeof(TrTrader) / 4u;
 static_assert(sizeof(TrTrader) % 4u == 0u && kTrResMaxClusters * kTrW <= (uint32_t)kRkThreads,
               "the trader state in one word per thread");
-static_assert(sizeof(TrCluster) % 4u == 0u && kStW <= (uint32_t)kWave, "TrCluster in one VGPR");
-struct RkField {  // a TrCluster field held in lane f of a VGPR (phase A's cluster state)
-    uint32_t& v;
-    uint32_t f, lane;
-    __device__ __forceinline__ operator uint32_t() const { return readlane(v, f); }
-    __device__ __forceinline__ RkField& operator=(uint32_t x) {
-        v = lane == f ? x : v;
-        return *this;
-    }
-    __device__ __forceinline__ RkField& operator=(const RkField& o) { return *this = (uint32_t)o; }
-    __device__ __forceinline__ RkField& operator+=(uint32_t x) { return *this = (uint32_t)*this + x; }
-    __device__ __forceinline__ RkField& operator-=(uint32_t x) { return *this = (uint32_t)*this - x; }
-    __device__ __forceinline__ RkField& operator|=(uint32_t x) { return *this = (uint32_t)*this | x; }
-    __device__ __forceinline__ RkField& operator++() { return *this += 1u; }
-    __device__ __forceinline__ RkField& operator--() { return *this -= 1u; }
-    __device__ __forceinline__ uint32_t operator++(int) {
-        const uint32_t o = *this;
-        *this = o + 1u;
-        return o;
-    }
-};
-#define RST(field) (RkField{stv, (uint32_t)(offsetof(TrCluster, field) / 4u), lane})
-
 #ifdef MCS_RK_STAMPS
 // probe build (tools/variant.sh ... -DMCS_RK_STAMPS): per-wave segment times (s_memrealtime, 100 MHz)
 // summed over the launches since the last read: [wave of the system][segment]; segments: 0 launch
@@ -215,11 +189,11 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
     const uint32_t trn = C * kTrW, tq = threadIdx.x;
     const uint32_t* const trp0 = reinterpret_cast<const uint32_t*>(tr_r) + min(tq, trn - 1u);
     // this wave's cluster (c = 0 for a wave that owns none: its values are never read): TrCluster
-    // (lane f < kStW: word f), CSR bounds, the dense node copy (tick 0's from the CSR initial state,
+    // (lane f < kStWords: word f), CSR bounds, the dense node copy (tick 0's from the CSR initial state,
     // after the barrier), the running slots in registers (row r, lane l: slot (r / 4) * 256 + 4l +
     // r % 4, so a lane's four rows are one 16-byte load; finish time and payload node | cores << 9 |
     // mem << 16, in this kernel's own order in sfin / snode)
-    const uint32_t* const stp = reinterpret_cast<const uint32_t*>(&a.cl[c]) + min(lane, kStW - 1u);
+    const uint32_t* const stp = reinterpret_cast<const uint32_t*>(&a.cl[c]) + min(lane, kStWords - 1u);
     const unsigned long long* np[kRkNodes / kWave];
 #pragma unroll
     for (uint32_t q = 0; q < kRkNodes / kWave; ++q) np[q] = a.tnr + (size_t)c * ns + min(q * kWave + lane, ns - 1u);
@@ -250,7 +224,7 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
     for (uint32_t k = 0; k < kRkLenders; ++k) gl[k] = *glp[k];
     RK_MARK(1);
     // the LDS copies
-    if (own && lane < kStW) reinterpret_cast<uint32_t*>(&sh.st[wave])[lane] = stw;
+    if (own && lane < kStWords) reinterpret_cast<uint32_t*>(&sh.st[wave])[lane] = stw;
     if (tq < trn) reinterpret_cast<uint32_t*>(sh.trs)[tq] = trv0;
     if (threadIdx.x == 0) {
         sh.T = sh.T0 = ctlv.T;
@@ -391,47 +365,9 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
             }
             unsigned long long n_trades = sh.n_trades, n_won = sh.n_won;
             uint32_t lflags = 0;
-            if (a.trader) {
-                const bool due = q < C && t.next_due <= T;
-                const bool broken = cu > 0.8f || mu > 0.8f;  // Utilization (trader.go:127-130)
-                if (due && !broken) t.next_due = T + a.period;
-                const bool appr = q < C && approve_trade_dev(tot_c, tot_m, cu, mu, 0u, 0u, 0u);
-                unsigned long long pend = __ballot(due && broken);
-                while (pend) {  // RequestPolicyMonitor of requester r (trader.go:282-324), index order
-                    const uint32_t r = (uint32_t)__builtin_ctzll(pend);
-                    pend &= pend - 1ull;
-                    bool app = false;
-                    if (q < C && q != r) {  // RequestResource, index order
-                        if (t.lock_id != 0u && T >= t.lock_until) t.lock_id = 0u;  // 20 s expiry
-                        if (t.lock_id == 0u) {  // else Approve:false (server.go:35-40)
-                            app = appr;
-                            t.lock_id = t.next_id++;  // set even when not approving (:44-46)
-                            t.lock_until = T + a.lock_s;
-                        }
-                    }
-                    const unsigned long long ab = __ballot(app);
-                    const uint32_t napp = (uint32_t)__builtin_popcountll(ab);
-                    const uint32_t winner = ab ? (uint32_t)__builtin_ctzll(ab) : kEmpty;
-                    if (winner != kEmpty) {
-                        if (q == winner) t.lock_id = 0u;  // ApproveContract unlocks (:83)
-                        if (q == r) t.vnodes += 1u;       // AddVirtualNode(0 cores, 0 memory)
-                        ++n_won;
-                    }
-                    if (q == r) t.next_due = T + (winner != kEmpty ? a.ok_sleep : a.fail_sleep) + a.period;
-                    if (lane == 0 && wg == 0) {  // (workgroup 0 keeps the log; every rank alike)
-                        if (n_trades < a.trade_cap) {
-                            mcs_trade_rec rec;
-                            rec.t_s = T;
-                            rec.requester = r;
-                            rec.winner = winner == kEmpty ? -1 : (int32_t)winner;
-                            rec.approvals = napp;
-                            a.trade_log[n_trades] = rec;
-                        }
-                    }
-                    if (n_trades >= a.trade_cap) lflags |= MCS_FLAG_LOG_OVERFLOW;
-                    ++n_trades;
-                }
-            }
+            // (workgroup 0 keeps the log; every rank alike)
+            if (a.trader)
+                tr_trader_rounds(a, T, q, q < C, TrSample{cu, mu, tot_c, tot_m}, wg == 0, t, n_trades, n_won, lflags);
             // the next tick: T+1 while any queue is busy, else the next arrival or trader round
             uint32_t nxt = next_arr_t;
             if (a.trader && q < C) nxt = t.next_due < nxt ? t.next_due : nxt;
@@ -442,22 +378,12 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
             // (C/D reads trs[q] of its own lane only before this barrier-free store: lane q owns q)
             if (a.trader && q < C) sh.trs[q] = t;
             if (lane == 0) {
-                uint32_t flags = sh.flags | fl | lflags;
-                uint32_t done = 0, Tn = T;
-                const uint32_t fatal = MCS_FLAG_OVERFLOW | MCS_FLAG_LENT_OVERFLOW;
-                if (done_all || (flags & fatal)) {
-                    done = 1u;
-                } else if (T >= a.t_max || (!busy_any && nxt == kEmpty)) {
-                    done = 1u;
-                    flags |= MCS_FLAG_T_MAX;
-                    sh.tmax_now = 1u;
-                } else {
-                    Tn = (busy_any || nxt <= T + 1u) ? T + 1u : nxt;
-                }
-                sh.T = Tn;
-                sh.done = done;
+                const TrNext nx = tr_next_tick(T, a.t_max, done_all, busy_any, nxt, sh.flags | fl | lflags);
+                sh.tmax_now = nx.tmax_now;
+                sh.T = nx.Tn;
+                sh.done = nx.done;
                 sh.ticks += 1u;
-                sh.flags = flags;
+                sh.flags = nx.flags;
                 sh.n_trades = n_trades;
                 sh.n_won = n_won;
             }
@@ -600,7 +526,8 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
     // (the LDS values A starts from, read in one batch)
     const uint32_t doneA = sh.done, TA = sh.T;
     const uint32_t ndue = lane < C ? sh.trs[lane].next_due : kEmpty;  // (C <= 64)
-    uint32_t stv = !helper && lane < kStW ? reinterpret_cast<const uint32_t*>(&sh.st[wave])[lane] : 0u;
+    uint32_t stv = !helper && lane < kStWords ? reinterpret_cast<const uint32_t*>(&sh.st[wave])[lane] : 0u;
+    const TrLaneState st{stv, lane};
     // the nodes in registers (node q * 64 + l in lane l, word q; 0 past N): the releases alone go
     // through the wave's LDS copy (a scatter), first fit and the commits stay in registers
     unsigned long long nv[kRkNodes / kWave];
@@ -615,10 +542,10 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
         const bool sample = a.trader && T % a.sample_period == 0u && __ballot(ndue <= T) != 0ull;
         // (the WaitQueue head may have left for the BorrowedQueue in X2: the window still holds
         // the ReadyQueue head or job_at loads it)
-        const uint32_t na0 = RST(next_arr);
+        const uint32_t na0 = TR_ST(next_arr);
         RK_MARK(7);
         // releases due at T (cluster.go:153-157), before the tick's decisions
-        if (RST(minf) <= T) {
+        if (TR_ST(minf) <= T) {
 #pragma unroll
             for (uint32_t q = 0; q < kRkNodes / kWave; ++q)
                 if (q * kWave + lane < N) nodes[q * kWave + lane] = nv[q];
@@ -639,31 +566,17 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
                     lm = f < lm ? f : lm;
                 }
             }
-            RST(nrun) -= nrel;
-            RST(minf) = wave_min_u32(lm);
+            TR_ST(nrun) -= nrel;
+            TR_ST(minf) = wave_min_u32(lm);
 #pragma unroll
             for (uint32_t q = 0; q < kRkNodes / kWave; ++q)
                 if (q * kWave + lane < N) nv[q] = nodes[q * kWave + lane];
         }
         RK_MARK(8);
         // arrivals up to T join the ReadyQueue (jobs are sorted by arrival)
-        uint32_t nat;
-        {
-            const uint32_t n = (uint32_t)__builtin_popcountll(__ballot(awin <= T && na0 + lane < J));
-            RST(next_arr) = na0 + n;
-            if (n < (uint32_t)kWave) {
-                nat = readlane(awin, n);
-            } else {
-                while (RST(next_arr) < J) {
-                    const uint32_t i = RST(next_arr) + lane;
-                    const bool ok = i < J && jobs[i].x <= T;
-                    const uint32_t m = (uint32_t)__builtin_popcountll(__ballot(ok));
-                    RST(next_arr) += m;
-                    if (m < (uint32_t)kWave) break;
-                }
-                nat = RST(next_arr) < J ? jobs[RST(next_arr)].x : kEmpty;
-            }
-        }
+        const TrArrivals arr = tr_arrivals<64>(T, lane, 0u, na0, awin, jobs, J);
+        TR_ST(next_arr) = arr.next_arr;
+        const uint32_t nat = arr.nat;
         auto job_at = [&](uint32_t j) -> uint4 {
             const uint32_t d = j - hwb;
             if (d < (uint32_t)kWave)
@@ -707,82 +620,18 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
                 frm &= ~(1u << row);
                 drt |= 1u << row;
             }
-            ++RST(nrun);
-            RST(peak) = RST(nrun) > RST(peak) ? RST(nrun) : RST(peak);
-            RST(minf) = f < RST(minf) ? f : RST(minf);
+            ++TR_ST(nrun);
+            TR_ST(peak) = TR_ST(nrun) > TR_ST(peak) ? TR_ST(nrun) : TR_ST(peak);
+            TR_ST(minf) = f < TR_ST(minf) ? f : TR_ST(minf);
             return true;
         };
-        auto place_own = [&](uint32_t j, uint32_t kn, uint4 jb) -> bool {
-            const uint32_t f = T + jb.y;
-            if (jb.y != 0u && !commit(kn, jb.z, jb.w, f)) return false;
-            if (lane == 0) {
-                a.out_node[j0 + j] = (int32_t)kn;
-                a.out_start[j0 + j] = T;
-                a.out_finish[j0 + j] = f;
-            }
-            ++RST(placed);
-            ++RST(decided);
-            return true;
-        };
-
-        TrRecA req{kEmpty, 0u, 0u, 0u};
-        uint32_t lent_now = 0u;
+        // the lent-run record is written by the next launch, at the index the gathered lent bits give it
         uint4 lr = make_uint4(0u, 0u, 0u, 0u);
-        for (;;) {
-            if (RST(has_w)) {  // WaitQueue head (scheduler.go:219-251)
-                const uint4 jb = job_at(RST(w));
-                const uint32_t kn = first_fit(jb.z, jb.w);
-                if (kn != kEmpty) {
-                    if (!place_own(RST(w), kn, jb)) {
-                        RST(flags) |= MCS_FLAG_OVERFLOW;
-                        break;
-                    }
-                    RST(has_w) = 0u;
-                } else if (a.borrow) {
-                    req = TrRecA{RST(w), jb.z, jb.w, jb.y};  // BorrowResources (:234)
-                }
-                break;  // time.Sleep(1 s), :250
-            }
-            if (RST(rq_head) < RST(next_arr)) {  // ReadyQueue head (:255-272), no sleep
-                const uint32_t j = RST(rq_head)++;
-                const uint4 jb = job_at(j);
-                const uint32_t kn = first_fit(jb.z, jb.w);
-                if (kn != kEmpty) {
-                    if (!place_own(j, kn, jb)) {
-                        RST(flags) |= MCS_FLAG_OVERFLOW;
-                        break;
-                    }
-                } else {
-                    RST(has_w) = 1u;
-                    RST(w) = j;
-                    ++RST(waited);
-                }
-                continue;
-            }
-            if (RST(lq_len) > 0u) {  // LentQueue head (:277-290)
-                const uint64_t w0 = readlane((uint32_t)lqw, 0) | ((uint64_t)readlane((uint32_t)(lqw >> 32), 0) << 32);
-                const uint32_t eb = (uint32_t)w0, ej = (uint32_t)(w0 >> 32);
-                const uint32_t ec = readlane((uint32_t)lqw, 1), em = readlane((uint32_t)(lqw >> 32), 1);
-                const uint32_t ed = readlane((uint32_t)lqw, 2);
-                const uint32_t kn = first_fit(ec, em);
-                if (kn != kEmpty) {
-                    const uint32_t f = T + ed;
-                    if (ed != 0u && !commit(kn, ec, em, f)) {
-                        RST(flags) |= MCS_FLAG_OVERFLOW;
-                        break;
-                    }
-                    // the lent-run record is written by the next launch, at the index the gathered
-                    // lent bits give it
-                    lr = make_uint4(eb, ej, kn, f);
-                    lent_now = kQsLent;
-                    ++RST(lent_runs);
-                    RST(lq_head) = RST(lq_head) + 1u == a.LQ ? 0u : RST(lq_head) + 1u;
-                    --RST(lq_len);
-                }
-                break;  // sleep 1 s (:289)
-            }
-            break;  // idle sleep (:294)
-        }
+        auto lent_run = [&](uint32_t eb, uint32_t ej, uint32_t kn, uint32_t f) { lr = make_uint4(eb, ej, kn, f); };
+        auto ops = tr_step_ops(job_at, first_fit, commit, [&] { return tr_lent_from_lanes(lqw); }, lent_run);
+        const TrStepOut so = tr_fifo_step(a, T, lane, j0, st, ops);
+        const TrRecA req = so.req;
+        const uint32_t lent_now = so.lent ? kQsLent : 0u;
         RK_MARK(9);
 
         // GetResourceUtilization (cluster.go:46-63) on the ticks a trader reads it: an exact integer
@@ -795,10 +644,10 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
                 fc += (uint32_t)nv[q];
                 fm += (uint32_t)(nv[q] >> 32);
             }
-            const float sc = (float)(int32_t)((uint32_t)RST(total_c) - rk_wave_sum(fc));
-            const float sm = (float)(int32_t)((uint32_t)RST(total_m) - rk_wave_sum(fm));
-            RST(cu) = __float_as_uint(__fdiv_rn(sc, (float)RST(total_c)));
-            RST(mu) = __float_as_uint(__fdiv_rn(sm, (float)RST(total_m)));
+            const float sc = (float)(int32_t)((uint32_t)TR_ST(total_c) - wave_sum_u32(fc));
+            const float sm = (float)(int32_t)((uint32_t)TR_ST(total_m) - wave_sum_u32(fm));
+            TR_ST(cu) = __float_as_uint(__fdiv_rn(sc, (float)TR_ST(total_c)));
+            TR_ST(mu) = __float_as_uint(__fdiv_rn(sm, (float)TR_ST(total_m)));
         }
         // the lender's G table of the post-A nodes (phase B of the next launch, every workgroup):
         // G[x] = max free_m over the nodes with free_c > x, x < 64; "big" when some free_c > 64
@@ -816,13 +665,13 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
         const bool bigw = __ballot(big) != 0ull;
         // (no snapshot room when the engine proved no node exceeds 64 cores: cannot happen, and is
         // refused loudly, as an overflow of this tick's record, if it ever does)
-        if (bigw && !a.snaps) RST(flags) |= MCS_FLAG_OVERFLOW;
+        if (bigw && !a.snaps) TR_ST(flags) |= MCS_FLAG_OVERFLOW;
         rk_gtab(a, xw, g)[63u - lane] = wave_scan_max_u32(tab[63u - lane]);  // G[63 - lane]
         RK_MARK(10);
         // the post-A record and the node snapshot: this rank's block of the next all-gather
-        const uint32_t lql = RST(lq_len);
-        const uint32_t qs = (RST(has_w) ? kQsW : 0u) | (RST(rq_head) < RST(next_arr) ? kQsRq : 0u) | lent_now |
-                            (lql > 0u ? kQsLq : 0u) | (RST(decided) == J && lql == 0u ? kQsDone : 0u) |
+        const uint32_t lql = TR_ST(lq_len);
+        const uint32_t qs = (TR_ST(has_w) ? kQsW : 0u) | (TR_ST(rq_head) < TR_ST(next_arr) ? kQsRq : 0u) | lent_now |
+                            (lql > 0u ? kQsLq : 0u) | (TR_ST(decided) == J && lql == 0u ? kQsDone : 0u) |
                             (bigw ? kQsBig : 0u);
         uint32_t xv = 0u;
         xv = lane == kRkJob ? req.job : xv;
@@ -830,15 +679,15 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
         xv = lane == kRkM ? req.m : xv;
         xv = lane == kRkDur ? req.dur : xv;
         xv = lane == kRkQs ? qs : xv;
-        xv = lane == kRkDecided ? (uint32_t)RST(decided) : xv;
+        xv = lane == kRkDecided ? (uint32_t)TR_ST(decided) : xv;
         xv = lane == kRkNat ? nat : xv;
-        xv = lane == kRkFlags ? (uint32_t)RST(flags) : xv;
-        xv = lane == kRkCu ? (uint32_t)RST(cu) : xv;
-        xv = lane == kRkMu ? (uint32_t)RST(mu) : xv;
+        xv = lane == kRkFlags ? (uint32_t)TR_ST(flags) : xv;
+        xv = lane == kRkCu ? (uint32_t)TR_ST(cu) : xv;
+        xv = lane == kRkMu ? (uint32_t)TR_ST(mu) : xv;
         xv = lane == kRkLq ? lql : xv;
         xv = lane == kRkN ? N : xv;
-        xv = lane == kRkTc ? (uint32_t)RST(total_c) : xv;
-        xv = lane == kRkTm ? (uint32_t)RST(total_m) : xv;
+        xv = lane == kRkTc ? (uint32_t)TR_ST(total_c) : xv;
+        xv = lane == kRkTm ? (uint32_t)TR_ST(total_m) : xv;
         uint32_t* const rp = rk_rec(a, xw, g);
         if (lane < kRkWords) rp[lane] = xv;
         if (bigw && a.snaps) {  // (read only for a big lender)
@@ -848,7 +697,7 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
                 if (q * kWave + lane < N) sn[q * kWave + lane] = nv[q];
         }
         if (lane == 0 && lent_now) a.lrp[c] = lr;
-        if (lane < kStW) reinterpret_cast<uint32_t*>(&sh.st[wave])[lane] = stv;
+        if (lane < kStWords) reinterpret_cast<uint32_t*>(&sh.st[wave])[lane] = stv;
     }
 
     RK_MARK(5);
@@ -861,7 +710,7 @@ __global__ __launch_bounds__(kRkThreads) void tr_rk_kernel(TradeArgs a, uint32_t
             const uint32_t i = q * kWave + lane;
             if (i < N && (mode == 0u || nv[q] != nreg[q])) a.tnr[(size_t)c * ns + i] = nv[q];
         }
-        if (lane < kStW) reinterpret_cast<uint32_t*>(&a.cl[c])[lane] = reinterpret_cast<const uint32_t*>(&sh.st[wave])[lane];
+        if (lane < kStWords) reinterpret_cast<uint32_t*>(&a.cl[c])[lane] = reinterpret_cast<const uint32_t*>(&sh.st[wave])[lane];
 #pragma unroll
         for (int k = 0; k < kRows / 4; ++k) {  // a quad with a changed row, back as one 16-byte store
             if ((drt >> (4 * k)) & 15u) {
@@ -910,18 +759,8 @@ bool trade_rk_shape(const TradeArgs& a) {
 
 hipError_t launch_trade_rk(const TradeArgs& a, uint32_t mode, size_t lds, hipStream_t s) {
     const uint32_t nwg = (a.Ct + kRkWaves - 1u) / kRkWaves;
-    const void* fn = a.S == 4u * kWave   ? (const void*)tr_rk_kernel<4>
-                     : a.S == 8u * kWave ? (const void*)tr_rk_kernel<8>
-                                         : (const void*)tr_rk_kernel<16>;
-    hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (st != hipSuccess) return st;
-    if (a.S == 4u * kWave)
-        hipLaunchKernelGGL(tr_rk_kernel<4>, dim3(nwg), dim3(kRkThreads), lds, s, a, mode);
-    else if (a.S == 8u * kWave)
-        hipLaunchKernelGGL(tr_rk_kernel<8>, dim3(nwg), dim3(kRkThreads), lds, s, a, mode);
-    else
-        hipLaunchKernelGGL(tr_rk_kernel<16>, dim3(nwg), dim3(kRkThreads), lds, s, a, mode);
-    return hipGetLastError();
+    return launch_by_rows(tr_rk_kernel<4>, tr_rk_kernel<8>, tr_rk_kernel<16>, a.S, dim3(nwg), dim3(kRkThreads), lds,
+                          s, a, mode);
 }
 
 }  // namespace mcs

@@ -122,5 +122,9 @@ __device__ __forceinline__ uint32_t wave_scan_add_u32(uint32_t v) {
     v += dpp_src0<0x143, 0xc>(v);
     return v;
 }
+// a wave's uint32 sum (wrapping) / OR, the scans read at lane 63: VALU steps, no chain of LDS-pipe
+// permutes (every lane active)
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return readlane(wave_scan_add_u32(v), 63u); }
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) { return readlane(wave_scan_or_u32(v), 63u); }
 
 }  // namespace mcs

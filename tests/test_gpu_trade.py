@@ -96,6 +96,19 @@ def test_gpu_trade_caller_driven_equals_run():
     assert trade_rows(a["trades"]) == trade_rows(b["trades"])
 
 
+@pytest.mark.parametrize("driven", [False, True])
+def test_gpu_trade_above_64_clusters(driven):
+    """A system of more than 64 clusters: the trader kernel's 64-at-a-time requester / responder
+    loops and the step / lend kernels at global indices >= 64, on the replayed kernels (no resident
+    or one-launch form takes 70 clusters) == the oracle."""
+    arrays, streams, _ = seeded_workload("n64_hot", 70, 300)
+    g = gpu_trade(arrays, streams, driven=driven)
+    o = assert_trade_parity(arrays, streams, g)
+    assert g["tstats"]["loop_form"] == 0, g["tstats"]["loop_form"]
+    assert any(r[1] >= 64 for r in trade_rows(o["trades"]))  # a requester beyond the first 64 lanes
+    assert any(r[0] >= 64 for r in lent_rows(o["lent"]))  # a lender beyond them
+
+
 def test_gpu_trade_cadences_and_small_lent_queue():
     """Non-default cadences reach the kernels; a LentQueue overflow is reported, not ignored."""
     arrays, streams, _ = seeded_workload("n64_hot", 6, 1500)
