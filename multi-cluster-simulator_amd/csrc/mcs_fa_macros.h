@@ -42,7 +42,8 @@
 //                                                                                              s_cmp)
 //  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch             (interlocked on gfx9; SALU
 //                                                                                              instructions between anyway)
-//  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop)
+//  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16Q's row
+//                                                                                              pairs: s_or_b64 exec)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
 //    rewritten
 //  VALU writes SGPR -> VMEM reads it (address/      5     none: the store/load bases s[64:71]   -
@@ -96,10 +97,11 @@
 //   s50 fl   s51 byte mask of fl   s52 8 * chunk   s53 register index of the chunk
 //   s[54:55] kx, finish   s56 next clock   s57 cb   s[60:61] lanes with a free row
 //   s[62:63] one-lane exec masks   s[64:65] jobs  s[66:67] out_node  s[68:69] out_start
-//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1  s75 expired  s76 tmp
+//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1 (W16Q: unused)  s75 expired  s76 tmp
 //   s77 the wave's earliest finish  s78/s79 failed fits / bound 4J + 256 (a runaway loop ends as a
 //   pool overflow: the engine re-runs the cluster on the compiled kernel)   s80 used  s81 peak
-//   s82 waited  s83 passes without a decision  s84 release scans  s85 insert lane
+//   s82 waited (W16Q: the WaitQueue heads placed; a head waiting at the exit is s43)
+//   s83 passes without a decision  s84 release scans  s85 insert lane
 //   release: row expiry masks in s[50:55], s[60:63], s[86:91]
 //   v[64:71] nodes (W32: pairs {C, M} per chunk; W16: v64-v67)   v[72:79] fit-test differences
 //   v80-v86 fit bits / byte mask   (release: finish rows in v[72:87])
@@ -329,13 +331,15 @@
     "s_and_b64 exec, " MASK ", -1\n\t"                                                           \
     "s_cbranch_scc1 mcsfa_rb" #p "_%=\n"                                                         \
     "mcsfa_r" #p "_%=:\n\t"
-#define MCS_FR_BODY(p, MASK, F, P, A)                                                             \
-    "mcsfa_rb" #p "_%=:\n\t"                                                                     \
+// (a row's release under exec = its expiry mask: the payloads back to the nodes, the slots free, counted)
+#define MCS_FR_REL(p, MASK, F, P, A)                                                              \
     "s_bcnt1_i32_b64 s76, " MASK "\n\t"                                                          \
     "ds_add_u32 " A ", " P "\n\t"                                                               \
     "v_mov_b32 " F ", -1\n\t"                                                                    \
     "s_add_u32 s75, s75, s76\n\t"                                                                \
-    "v_or_b32 v89, 1<<" #p ", v89\n\t"                                                           \
+    "v_or_b32 v89, 1<<" #p ", v89\n\t"
+#define MCS_FR_BODY(p, MASK, F, P, A)                                                             \
+    "mcsfa_rb" #p "_%=:\n\t" MCS_FR_REL(p, MASK, F, P, A)                                        \
     "s_branch mcsfa_r" #p "_%=\n"
 #define MCS_FA_SCAN16R                                                                            \
     /* the LDS node copy is refreshed from the registers first (commits do not touch it) */       \
@@ -474,6 +478,32 @@
 #define MCS_FA_ZEROKX32 MCS_FA_ZEROKX
 #define MCS_FA_ZEROKX16 MCS_FA_ZEROKX
 #define MCS_FA_ZEROKX16R MCS_FA_ZEROKX
+// The WaitQueue statistic and the scan's t + 1, at the places the loop touches them: a failed fit
+// (WAITQ: a head that joins the WaitQueue counts as waited, once: s43 tells a retry), the placed
+// WaitQueue head at the pass bound's end (WAITP), the scalar the LDS-slot scans read as t + 1 (TNEXT)
+// and the exit (XWAITED).  W16Q has its own of each, with the streamed W16R loop's macros below.
+#define MCS_FA_WAITQ_                                                                             \
+    "s_sub_u32 s76, 1, s43\n\t"                                                                   \
+    "s_add_u32 s82, s82, s76\n\t"                                                                 \
+    "s_mov_b32 s43, 1\n\t"
+#define MCS_FA_TNEXT_ "s_add_u32 s74, s40, 1\n\t"
+#define MCS_FA_XWAITED_ "s_mov_b32 %[waited], s82\n\t"
+#define MCS_FA_WAITQ32 MCS_FA_WAITQ_
+#define MCS_FA_WAITQ16 MCS_FA_WAITQ_
+#define MCS_FA_WAITQ16R MCS_FA_WAITQ_
+#define MCS_FA_WAITQ16S MCS_FA_WAITQ_
+#define MCS_FA_WAITP32 ""
+#define MCS_FA_WAITP16 ""
+#define MCS_FA_WAITP16R ""
+#define MCS_FA_WAITP16S ""
+#define MCS_FA_TNEXT32 MCS_FA_TNEXT_
+#define MCS_FA_TNEXT16 MCS_FA_TNEXT_
+#define MCS_FA_TNEXT16R MCS_FA_TNEXT_
+#define MCS_FA_TNEXT16S MCS_FA_TNEXT_
+#define MCS_FA_XWAITED32 MCS_FA_XWAITED_
+#define MCS_FA_XWAITED16 MCS_FA_XWAITED_
+#define MCS_FA_XWAITED16R MCS_FA_XWAITED_
+#define MCS_FA_XWAITED16S MCS_FA_XWAITED_
 // slots of the pool (64 lanes x P rows)
 #define MCS_FA_POOLMAX32 "64*8"
 #define MCS_FA_POOLMAX16 "64*8"
@@ -493,7 +523,7 @@
 // and the lanes whose row R is free and not yet handed out in s[58:59] (CUR): an insert takes CUR's
 // lowest lane with scalar instructions only — no v_cmp / v_ffbl of v89 in the fit test, no v_readlane
 // of the row, no v_xor.  v89 stays the truth for the other rows; bit R of v89 means "row R freed by
-// a release since it became current" (the release bodies are W16R's).  When CUR runs out the insert
+// a release since it became current" (the rows' release is W16R's).  When CUR runs out the insert
 // branches out of line to the re-pick (MCS_FA_REPICK16Q), which takes the next row p = R+1 ... R+8
 // (mod 8) with a free lane: CUR = the lanes with bit p of v89, R = p, bit p cleared.  No such row:
 // the pool is full, CUR stays 0 and the insert runs under an empty exec (peak > 64*8 at the batch
@@ -567,6 +597,37 @@
     "s_lshl2_add_u32 s54, s50, s53\n\t"
 #define MCS_FA_POOLMAX16Q "64*8"
 #define MCS_FA_NODEIDX16Q "v_mov_b32 v126, v91\n\t"
+// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled (the pass
+// bound's end: once per waited job, where the shared loop pays a subtract and an add at every failed
+// fit); a head still waiting when the loop leaves (deadlock, clock overflow, the runaway guard: s43 = 1
+// on exactly those exits, 0 on every other) is added at the exit.  (s43 is set at a failed fit only and
+// cleared after WAITP, before the placed head's own clock step; mcsfa_bend, and the exit from it, is
+// reached only on s43 = 0: from the entry, and from loopend's s_cmp_lg_u32 s43, 0.)  Its scan reads no
+// t + 1 (s74).
+#define MCS_FA_WAITQ16Q "s_mov_b32 s43, 1\n\t"
+#define MCS_FA_WAITP16Q "s_add_u32 s82, s82, 1\n\t"
+#define MCS_FA_TNEXT16Q ""
+#define MCS_FA_XWAITED16Q "s_add_u32 %[waited], s82, s43\n\t"
+// This form's scan tests its slot rows in pairs: exec = the union of a pair's expiry masks, SCC = any
+// (one s_or_b64; exec is written by the scalar unit only, no vector instruction runs under a pair's
+// union, and exec is set to the full wave after the last pair), so a pair without an expiry, the usual
+// case, falls through on two instructions where its rows took four.  A pair with one branches to its
+// block out of line (MCS_FQ_PBODY), which tests its two rows as MCS_FR_ROW does and runs their bodies
+// (MCS_FR_REL, as every other form's) in place; the second row's test is the return when that row has no
+// expiry.  tools/scan_rows_model.py counts it on the bench stream: 14.8 scalar and branch instructions
+// per scan where the single row tests and their returns take 17.6, for 0.46 more taken branches.
+#define MCS_FQ_PAIR(k, MA, MB)                                                                    \
+    "s_or_b64 exec, " MA ", " MB "\n\t"                                                          \
+    "s_cbranch_scc1 mcsfa_pb" #k "_%=\n"                                                         \
+    "mcsfa_pr" #k "_%=:\n\t"
+#define MCS_FQ_PBODY(k, ra, MA, FA, PA, AA, rb, MB, FB, PB, AB)                                   \
+    "mcsfa_pb" #k "_%=:\n\t"                                                                     \
+    "s_and_b64 exec, " MA ", -1\n\t"                                                             \
+    "s_cbranch_scc0 mcsfa_pm" #k "_%=\n\t" MCS_FR_REL(ra, MA, FA, PA, AA) "\n"                   \
+    "mcsfa_pm" #k "_%=:\n\t"                                                                     \
+    "s_and_b64 exec, " MB ", -1\n\t"                                                             \
+    "s_cbranch_scc0 mcsfa_pr" #k "_%=\n\t" MCS_FR_REL(rb, MB, FB, PB, AB)                        \
+    "s_branch mcsfa_pr" #k "_%=\n"
 #define MCS_FA_SCAN16Q                                                                            \
     /* the LDS node copy is refreshed from the registers first (commits do not touch it) */       \
     "ds_write_b128 v108, v[64:67]\n\t"                                                           \
@@ -579,10 +640,8 @@
     "v_cmp_ge_u32_e64 s[86:87], s40, v37\n\t"                                                    \
     "v_cmp_ge_u32_e64 s[88:89], s40, v38\n\t"                                                    \
     "v_cmp_ge_u32_e64 s[90:91], s40, v39\n\t"                                                    \
-    MCS_FR_ROW(0, "s[50:51]", "v32", "v40", "v48") MCS_FR_ROW(1, "s[52:53]", "v33", "v41", "v49")  \
-    MCS_FR_ROW(2, "s[54:55]", "v34", "v42", "v50") MCS_FR_ROW(3, "s[60:61]", "v35", "v43", "v51")  \
-    MCS_FR_ROW(4, "s[62:63]", "v36", "v44", "v52") MCS_FR_ROW(5, "s[86:87]", "v37", "v45", "v53")  \
-    MCS_FR_ROW(6, "s[88:89]", "v38", "v46", "v54") MCS_FR_ROW(7, "s[90:91]", "v39", "v47", "v55")  \
+    MCS_FQ_PAIR(0, "s[50:51]", "s[52:53]") MCS_FQ_PAIR(1, "s[54:55]", "s[60:61]")                 \
+    MCS_FQ_PAIR(2, "s[62:63]", "s[86:87]") MCS_FQ_PAIR(3, "s[88:89]", "s[90:91]")                 \
     "s_mov_b64 exec, -1\n\t"                                                                     \
     "s_sub_u32 s80, s80, s75\n\t" MCS_FA_RELOAD16Q                                              \
     /* the lane's earliest remaining finish (released rows now hold -1) */                     \
@@ -698,7 +757,12 @@
     "s_mov_b64 exec, s[62:63]\n\t"                                                                \
     "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
     "s_branch mcsfa_ins_%=\n"
-#define MCS_FA_RBODY16Q MCS_FA_RBODY16R MCS_FA_REPICK16Q MCS_FA_FITSTUB16Q
+#define MCS_FA_RBODY16Q                                                                           \
+    MCS_FQ_PBODY(0, 0, "s[50:51]", "v32", "v40", "v48", 1, "s[52:53]", "v33", "v41", "v49")       \
+    MCS_FQ_PBODY(1, 2, "s[54:55]", "v34", "v42", "v50", 3, "s[60:61]", "v35", "v43", "v51")       \
+    MCS_FQ_PBODY(2, 4, "s[62:63]", "v36", "v44", "v52", 5, "s[86:87]", "v37", "v45", "v53")       \
+    MCS_FQ_PBODY(3, 6, "s[88:89]", "v38", "v46", "v54", 7, "s[90:91]", "v39", "v47", "v55")       \
+    MCS_FA_REPICK16Q MCS_FA_FITSTUB16Q
 
 // the pass's finish time t + duration, after the fit test (W16Q: inside its fit test)
 #define MCS_FA_FINISH32 "s_add_u32 s55, s40, s46\n\t"

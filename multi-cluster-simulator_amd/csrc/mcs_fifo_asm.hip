@@ -38,8 +38,9 @@
 //     by line (see the comments there); the result batch keeps the node's LDS index
 //     (chunk * 64 + lane) and converts it to the node index when it is stored.  The streamed
 //     W16R loop (W16Q) keeps its LDS node copy as one 16-byte word per lane, so its index is the
-//     node index itself; its release scan carries the head job's fit test in the DPP wait states,
-//     and its zero-duration jobs leave the pass through the arrival test (mcs_fa_macros.h).
+//     node index itself; its release scan tests the slot rows in pairs and carries the head job's
+//     fit test in the DPP wait states, its zero-duration jobs leave the pass through the arrival
+//     test, and it counts a waited job where the placed WaitQueue head is handled (mcs_fa_macros.h).
 //
 // Hazards (wait states are not inserted by the compiler inside asm): DPP reads a VGPR 2 states
 // after its write (s_nop 1), v_readlane reads a VGPR at least 1 instruction after its write, m0
@@ -130,7 +131,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
     "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
     "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t"                                                                  \
+    "s_min_u32 s41, s41, 64\n\t" MCS_FA_WAITP##W                                                 \
     /* (the clock moves by t + 1 here and on a failed fit: the carry is the u32 clock's overflow) */ \
     "s_mov_b32 s43, 0\n\t"                                                                        \
     "s_add_u32 s40, s40, 1\n\t"                                                                   \
@@ -150,10 +151,7 @@ __device__ unsigned long long g_fa_stamps[4];
                                                                                                   \
     /* no node fits: WaitQueue append (:264-268), sleep to the next completion (A.3); falls */   \
     /* through to the release (a failed head sleeps to a completion, so it always releases) */  \
-    "mcsfa_nofit_%=:\n\t" MCS_FA_T0                                                              \
-    "s_sub_u32 s76, 1, s43\n\t"                                                                   \
-    "s_add_u32 s82, s82, s76\n\t"                                                                 \
-    "s_mov_b32 s43, 1\n\t"                                                                        \
+    "mcsfa_nofit_%=:\n\t" MCS_FA_T0 MCS_FA_WAITQ##W /* the head waits (s43 = 1) */              \
     "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
     MCS_FA_CNTS_##D                                                                               \
     /* runaway guard: every advance moves the clock forward and a loop without decisions goes */  \
@@ -174,7 +172,7 @@ __device__ unsigned long long g_fa_stamps[4];
     /* release every running job with finish <= t (cluster.go:153-157) */                        \
     MCS_FA_CNTR_##D MCS_FA_T0                                                                     \
     "s_max_u32 s81, s81, s80\n\t" /* peak: used only grows between releases */                   \
-    "s_add_u32 s74, s40, 1\n\t" MCS_FA_SCAN##W MCS_FA_SCANEND##W MCS_FA_T1("s94")                \
+    MCS_FA_TNEXT##W MCS_FA_SCAN##W MCS_FA_SCANEND##W MCS_FA_T1("s94")                            \
     /* (loopend's test, so the usual continuation is one taken branch) */                        \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
@@ -226,7 +224,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_mov_b32 s59, 1\n\t" MCS_FA_T1("s96")                                                      \
     "s_branch mcsfa_exit_%=\n"
 
-#define MCS_FA_EXIT_S                                                                             \
+#define MCS_FA_EXIT_S(W)                                                                          \
     /* ---- exit: state back to the compiler's registers ---- */                                 \
     "mcsfa_exit_%=:\n\t"                                                                          \
     "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t" MCS_FA_TEND                                               \
@@ -236,7 +234,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_mov_b32 %[hw], s43\n\t"                                                                    \
     "s_mov_b32 %[used], s80\n\t"                                                                  \
     "s_max_u32 %[peak], s81, s80\n\t"                                                             \
-    "s_mov_b32 %[waited], s82\n\t"                                                                \
+    MCS_FA_XWAITED##W                                                                             \
     "s_mov_b32 %[nslow], s83\n\t"                                                                 \
     "s_mov_b32 %[nrel], s84\n\t"                                                                  \
     "v_mov_b32 %[on], v91\n\t"                                                                    \
@@ -253,7 +251,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_mov_b32 %[lmin], v90\n\t"                                                                  \
     "s_nop 1"
 
-#define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S
+#define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S(W)
 
 // ---- W16L: W16R with a one-job lookahead (r06; form 22) -----------------------
 // Every pass also tests the NEXT job's request (s92, read one record ahead) against the nodes as they
@@ -542,7 +540,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_mov_b32 s58, s59\n\t" /* new records: the lookahead is void */                            \
     MCS_FL_REC                                                                                    \
     "s_branch mcsfl_innerF_%=\n"
-#define MCS_FL_LOOP(D) MCS_FL_ENTRY MCS_FL_BODY(D) MCS_FA_EXIT_S
+#define MCS_FL_LOOP(D) MCS_FL_ENTRY MCS_FL_BODY(D) MCS_FA_EXIT_S(16R)
 // the lookahead loop's clobbers: W16R's plus its own (no probe build of this form: MCS_STAMPS uses
 // s92-s99 for its segment clocks)
 #define MCS_FL_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98"
