@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_ref as O
+import util_ref as U
 from kat_util import GOLDEN, fuzz_workload, seeded_workload
 from mcs_amd import Engine
 from test_dtrade_oracle import check_kat, dt_system
@@ -230,13 +231,28 @@ def test_gpu_approve_trade_sweep_vs_oracle(engine):
                                           # (r04: longer streams through the grown-node pass: the
                                           # snapshot, the untested marks across rows, quiet row pairs)
                                           ("w16s", 4, 900), ("w16s", 5, 900), ("w16s", 6, 1500),
-                                          ("mid", 7, 900), ("mid", 8, 1500)])
-def test_gpu_dtrade_fuzz(shape, seed, J):
+                                          ("mid", 7, 900), ("mid", 8, 1500),
+                                          # sums past 2^24: the sample's float32 loop rounds (dt_sample)
+                                          # (this seed: contracts with one, two and three approvers)
+                                          ("w32", 15, 300)])
+def test_gpu_dtrade_fuzz(shape, seed, J, monkeypatch):
     """kat_util's randomised clusters and streams in a DELAY trading system (real contracts, Foreign
-    jobs, virtual nodes): every output bit-exact against the oracle."""
+    jobs, virtual nodes): every output bit-exact against the oracle.  The 'w32' system runs on both
+    tick forms, the resident tick (loop_form 5) and the replayed kernels (0)."""
     arrays, streams = fuzz_workload(shape, seed, n_clusters=8, J=J, blocking=False)
-    g = run(arrays, streams)
     o = O.dtrade_run(arrays, streams)
+    if shape != "w32":
+        check_dtrade_fuzz(run(arrays, streams), o)
+        return
+    assert U.sums_reach_2_24(arrays) and U.clusters_where_the_integer_sum_differs(arrays)
+    for resident, form in (("1", 5), ("0", 0)):
+        monkeypatch.setenv("MCS_DT_RESIDENT", resident)
+        g = run(arrays, streams)
+        assert g["ts"]["loop_form"] == form, g["ts"]["loop_form"]
+        check_dtrade_fuzz(g, o)
+
+
+def check_dtrade_fuzz(g, o):
     bad = np.nonzero((g["node"] != o["node"]) | (g["start"] != o["start"]) | (g["finish"] != o["finish"]))[0]
     assert bad.size == 0, f"{bad.size} mismatches, first {bad[:5]}: gpu {g['node'][bad[:5]]} {g['start'][bad[:5]]} " \
                           f"oracle {o['node'][bad[:5]]} {o['start'][bad[:5]]}"

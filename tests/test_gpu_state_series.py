@@ -246,6 +246,213 @@ def test_series_of_a_fused_run_equals_the_materialised_stream():
     assert_samples_equal(got[0][0][:, ::13], series_ref(arrays, streams, node, start, fin, 0, 65, 20))
 
 
+# ---- long streams: the batch cursor of series_kernel beyond one round of 256 summaries ----------
+#
+# Workload L, FIFO on cluster_small (5 nodes, tiles of 127 samples): arrivals about a second apart,
+# durations of at most 30 s, so a batch of 256 jobs ends soon after its last arrival.  Cluster LONG has
+# 3 * 65536 + 300 jobs, 769 batches: three full rounds and a fourth.  The streams before it have 300,
+# and those between it and the next multi-batch cluster 255 and 257 jobs, so the multi-batch
+# clusters start at job offsets that are no multiple of 256.  HOLD_0 and HOLD_300 repeat LONG's stream
+# with one small job of duration 2^30 in batch 0 and in batch 300: that batch never ends, so the
+# leading run of ended batches stops there in every tile.
+L_JOBS = (300, 3 * 65536 + 300, 255, 257, 70000)
+LONG, HOLD_0, HOLD_300 = 1, 5, 6
+HOLD_BATCH = 300
+BATCH, ROUND, GROUP = 256, 256, 8  # kSeriesBatch, kStateThreads, kGroup (csrc/mcs_state.hip)
+
+
+def workload_l():
+    rng = np.random.default_rng(0x4C4F4E47)
+    parts = []
+    for J in L_JOBS:
+        parts.append([np.cumsum(rng.integers(0, 3, J)), rng.integers(0, 31, J), rng.integers(0, 9, J),
+                      rng.integers(0, 6001, J)])
+    for b in (0, HOLD_BATCH):
+        p = [x.copy() for x in parts[LONG]]
+        i = b * BATCH + 17
+        p[1][i], p[2][i], p[3][i] = 1 << 30, 1, 1
+        parts.append(p)
+    arrays = seeded_workload("small", len(parts), 1)[0]
+    off = np.concatenate([[0], np.cumsum([len(p[0]) for p in parts])]).astype(np.uint64)
+    assert [int(o) % BATCH != 0 for o in off[[LONG, 4, HOLD_0, HOLD_300]]] == [True] * 4
+    return arrays, JobStreams(*(np.concatenate([p[f] for p in parts]).astype(np.uint32) for f in range(4)), off)
+
+
+def summaries(streams, node, fin, c):
+    """{arrival_min, end_max} per 256 jobs of cluster c, as series_summary_kernel defines them (an
+    unplaced job never ends)."""
+    js = streams.of(c)
+    arr = streams.arrival[js].astype(np.int64)
+    end = np.where(node[js] >= 0, fin[js].astype(np.int64), 0xFFFFFFFF)
+    cuts = np.arange(0, len(arr), BATCH)
+    return np.minimum.reduceat(arr, cuts), np.maximum.reduceat(end, cuts)
+
+
+def cursor_walk(amin, emax, t0, period, n, ts):
+    """What the cursor of one cluster has to do, tile by tile, stated from the summaries alone: the
+    rounds of 256 summaries from the first batch that may still be alive up to the round with the
+    first batch that arrives after the tile.  Per tile: b_lo on entry and on exit, and per round its
+    base, the length of the run of ended batches at its head, its hit batches and whether it holds a
+    batch past the tile."""
+    nb, b_lo, tiles = len(amin), 0, []
+    for k0 in range(0, n, ts):
+        tsa = min(ts, n - k0)
+        t_first = t0 + k0 * period
+        t_last = t_first + (tsa - 1) * period
+        dead, past = emax <= t_first, amin > t_last
+        alive = np.nonzero(~dead)[0]
+        b_next = int(alive[0]) if alive.size else nb  # every batch below has ended before the tile
+        rounds = []
+        for base in range(b_lo, nb, ROUND):
+            sl = slice(base, min(base + ROUND, nb))
+            live = np.nonzero(~dead[sl])[0]
+            rounds.append(dict(base=base, lead=int(live[0]) if live.size else sl.stop - sl.start,
+                               hits=base + np.nonzero(~dead[sl] & ~past[sl])[0], past=bool(past[sl].any())))
+            if rounds[-1]["past"]:
+                break
+        tiles.append(dict(b_in=b_lo, b_out=max(b_lo, b_next), rounds=rounds, t_first=t_first, t_last=t_last))
+        b_lo = max(b_lo, b_next)
+    return tiles
+
+
+def window_jobs(arrays, streams, node, start, fin, t0, t_last):
+    """The jobs that can touch a sample in [t0, t_last] (the others change no sample), as streams of
+    their own with their placements: the brute-force reference then reads far fewer jobs."""
+    keep = (streams.arrival.astype(np.int64) <= t_last) & ((node < 0) | (fin.astype(np.int64) > t0))
+    off = np.concatenate([[0], np.cumsum([int(keep[streams.of(c)].sum()) for c in range(arrays.n_clusters)])])
+    sub = JobStreams(*(getattr(streams, f)[keep] for f in ("arrival", "dur", "cores", "mem")), off.astype(np.uint64))
+    return sub, node[keep], start[keep], fin[keep]
+
+
+def assert_window(run, t0, period, n):
+    eng, arrays, streams, node, start, fin = run
+    samples, first = eng.cluster_state_series(t0, period, n)
+    sub, sn, ss, sf = window_jobs(arrays, streams, node, start, fin, t0, t0 + (n - 1) * period)
+    assert_samples_equal(samples, series_ref(arrays, sub, sn, ss, sf, t0, period, n), f"t0 {t0} period {period}")
+    assert first.tobytes() == eng.cluster_states(t0).tobytes()
+    return samples
+
+
+@pytest.fixture(scope="module")
+def run_l():
+    arrays, streams = workload_l()
+    node, start, fin = oracle_run("FIFO", arrays, streams)
+    assert (node >= 0).all()  # the held jobs are small enough: every stream drains
+    with Engine(0, policy="FIFO") as eng:
+        eng.load_clusters(arrays)
+        eng.submit_jobs(streams)
+        eng.run()
+        gn, gs, gf = eng.placements()
+        np.testing.assert_array_equal(gn, node)
+        np.testing.assert_array_equal(gs, start)
+        np.testing.assert_array_equal(gf, fin)
+        yield eng, arrays, streams, node, start, fin
+
+
+def walks(run, t0, period, n):
+    eng, arrays, streams, node, start, fin = run
+    assert tile(5) == 127 and (np.diff(arrays.node_off) == 5).all()
+    return {c: cursor_walk(*summaries(streams, node, fin, c), t0, period, n, 127) for c in (LONG, HOLD_0, HOLD_300)}
+
+
+def assert_held_clusters(w, k):
+    """Tile k lies late in the streams.  HOLD_0: batch 0 never ends, so the cursor stays at 0, every
+    round up to the tile's own is read, and batch 0 is the only hit below the tile's batches.
+    HOLD_300: the run of ended batches stops at batch 300, 44 batches into the second round."""
+    t0, t300, tl = w[HOLD_0][k], w[HOLD_300][k], w[LONG][k]
+    assert tl["b_out"] > 2 * ROUND  # late: LONG's own cursor is past two rounds
+    assert t0["b_in"] == 0 and t0["b_out"] == 0
+    assert [r["base"] for r in t0["rounds"]] == list(range(0, ROUND * len(t0["rounds"]), ROUND))
+    assert len(t0["rounds"]) >= 3
+    hits = np.concatenate([r["hits"] for r in t0["rounds"]])
+    assert hits[0] == 0 and hits.size > 1 and hits[1] > 2 * ROUND
+    assert t300["b_out"] == HOLD_BATCH and t300["b_in"] in (0, HOLD_BATCH)
+    hits = np.concatenate([r["hits"] for r in t300["rounds"]])
+    assert hits[0] == HOLD_BATCH and hits.size > 1 and hits[1] > 2 * ROUND
+    if t300["b_in"] == 0:  # the run ends in the middle of the second round
+        assert [r["lead"] for r in t300["rounds"][:2]] == [ROUND, HOLD_BATCH - ROUND]
+
+
+def run_length(run):
+    streams, fin = run[2], run[5]
+    return int(fin[: int(streams.job_off[HOLD_0])].max())  # without the two jobs of 2^30 seconds
+
+
+def test_long_stream_cursor_carries_over_full_rounds(run_l):
+    period = run_length(run_l) // 140 + 1
+    n = 150
+    w = walks(run_l, 0, period, n)
+    second = w[LONG][1]
+    assert second["b_in"] == 0  # nothing has ended at t = 0, so the whole dead run is found in this tile
+    assert [r["lead"] for r in second["rounds"][:2]] == [ROUND, ROUND] and second["b_out"] >= 2 * ROUND
+    assert_held_clusters(w, 1)
+    samples = assert_window(run_l, 0, period, n)
+    assert samples["running"][[LONG, HOLD_0, HOLD_300]].max(axis=1).min() > 1
+    assert samples["running"][:, -1].tolist() == [0, 0, 0, 0, 0, 1, 1]  # the two held jobs
+
+
+def test_long_stream_cursor_stops_inside_the_second_round(run_l):
+    streams = run_l[2]
+    t0 = int(streams.arrival[streams.of(LONG)][70000])
+    w = walks(run_l, t0, 1, 300)
+    head = w[LONG][0]
+    assert head["b_in"] == 0 and len(head["rounds"]) == 2
+    assert head["rounds"][0]["lead"] == ROUND and not head["rounds"][0]["past"]
+    assert 0 < head["rounds"][1]["lead"] < ROUND and head["rounds"][1]["past"]
+    assert ROUND < head["b_out"] < 2 * ROUND
+    assert w[HOLD_0][0]["b_out"] == 0 and len(w[HOLD_0][0]["rounds"]) == 2
+    assert w[HOLD_300][0]["b_out"] == head["b_out"]  # batch 300 has not arrived yet
+    assert_window(run_l, t0, 1, 300)
+
+
+def test_long_stream_cursor_breaks_in_the_first_round(run_l):
+    w = walks(run_l, 0, 1, 40)
+    for c in (LONG, HOLD_0, HOLD_300):
+        (only,) = w[c]
+        assert len(only["rounds"]) == 1 and only["rounds"][0]["past"] and only["b_out"] == 0
+    streams = run_l[2]
+    assert (int(streams.job_off[LONG + 1] - streams.job_off[LONG]) + BATCH - 1) // BATCH - ROUND > ROUND
+    assert_window(run_l, 0, 1, 40)
+
+
+def test_long_stream_round_with_more_hits_than_a_group(run_l):
+    streams = run_l[2]
+    t0 = int(streams.arrival[streams.of(LONG)][150000])
+    period, n = 20, 2 * 127 + 30
+    w = walks(run_l, t0, period, n)
+    for c in (LONG, HOLD_0, HOLD_300):
+        assert max(len(r["hits"]) for t in w[c] for r in t["rounds"]) > GROUP
+    assert_held_clusters(w, 0)
+    assert_held_clusters(w, 1)
+    assert_window(run_l, t0, period, n)
+
+
+def test_long_stream_in_chunks_is_the_same_series(run_l, monkeypatch):
+    eng = run_l[0]
+    period = run_length(run_l) // 140 + 1
+    whole, first = eng.cluster_state_series(0, period, 150)
+    monkeypatch.setenv("MCS_SERIES_CHUNK", "41")
+    parts, first2 = eng.cluster_state_series(0, period, 150)
+    assert parts.tobytes() == whole.tobytes() and first2.tobytes() == first.tobytes()
+
+
+def test_series_of_the_first_clusters_only(run_l):
+    """n_clusters below the engine's count: those rows, and nothing written behind them."""
+    eng, arrays = run_l[0], run_l[1]
+    assert arrays.n_clusters == 7
+    period, n = run_length(run_l) // 140 + 1, 150
+    whole, first = eng.cluster_state_series(0, period, n)
+    out = np.zeros((7, n), CLUSTER_SAMPLE_DTYPE)
+    out.view(np.uint8)[...] = 0xA5
+    one = np.zeros(7, first.dtype)
+    one.view(np.uint8)[...] = 0xA5
+    rc = L.lib().mcs_cluster_state_series(eng._h, 0, period, n, out.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+                                          one.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), 3, None)
+    assert rc == L.MCS_OK
+    assert out[:3].tobytes() == whole[:3].tobytes() and one[:3].tobytes() == first[:3].tobytes()
+    assert (out[3:].view(np.uint8) == 0xA5).all() and (one[3:].view(np.uint8) == 0xA5).all()
+
+
 def test_series_refusals(run_a):
     eng, arrays = run_a[0], run_a[1]
     n = arrays.n_clusters

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_ref as O
+import util_ref as U
 from kat_util import fuzz_workload, seeded_workload
 from mcs_amd import Engine
 from mcs_amd.shard import run_lockstep
@@ -262,13 +263,26 @@ def test_gpu_trade_config5_full_size():
     assert ts["t_final"] == o["t_final"]
 
 
-@pytest.mark.parametrize("shape,seed", [("w16s", 1), ("w16s", 2), ("mid", 3), ("w16r", 4)])
+def assert_float_sum_regime(arrays):
+    """A 'w32' system: the utilization samples its traders read come from the float32 loop itself
+    (csrc/mcs_trade.hip), not from the exact integer sum the resident and one-launch ticks use below
+    2^24, and at load that loop's result is not the integer sum's in some cluster."""
+    assert U.sums_reach_2_24(arrays)
+    assert U.clusters_where_the_integer_sum_differs(arrays)
+
+
+@pytest.mark.parametrize("shape,seed", [("w16s", 1), ("w16s", 2), ("mid", 3), ("w16r", 4), ("w32", 6)])
 def test_gpu_trade_fuzz(shape, seed):
     """kat_util's randomised clusters and streams (mixed node counts and availability, bursts, idle
     stretches, zero-duration and zero-resource jobs) in a FIFO trading system: placements, borrows,
-    lent runs, trades, virtual nodes and the final tick bit-exact against the oracle."""
+    lent runs, trades, virtual nodes and the final tick bit-exact against the oracle.  'w32': sums
+    past 2^24, where the engine keeps the replayed kernels and their float32 utilization loop."""
     arrays, streams = fuzz_workload(shape, seed, n_clusters=12, J=500, blocking=False)
+    if shape == "w32":
+        assert_float_sum_regime(arrays)
     g = gpu_trade(arrays, streams)
+    if shape == "w32":
+        assert g["tstats"]["loop_form"] == 0, g["tstats"]["loop_form"]
     assert_trade_parity(arrays, streams, g)
 
 
@@ -335,15 +349,19 @@ def test_gpu_trade_resident_form_by_capacity(monkeypatch):
         assert_trade_parity(arrays, streams, g)
 
 
-@pytest.mark.parametrize("shape,seed", [("w16s", 5), ("w16s", 17), ("mid", 3), ("w16r", 9)])
+@pytest.mark.parametrize("shape,seed", [("w16s", 5), ("w16s", 17), ("mid", 3), ("w16r", 9), ("w32", 7)])
 def test_gpu_trade_one_launch_tick_fuzz(shape, seed, monkeypatch):
     """The one-launch tick (mcs_trade_rk.hip) on the caller-driven path at world 1 (loop_form 9) over
     kat_util's randomised systems (mixed node counts and availability, bursts, idle stretches,
-    zero-duration and zero-resource jobs) == the oracle on every output."""
+    zero-duration and zero-resource jobs) == the oracle on every output.  'w32': sums past 2^24; the
+    one-launch tick sums in integers, so the engine must keep the three replayed kernels (loop_form
+    0) although MCS_TRADE_RK asks for it."""
     monkeypatch.setenv("MCS_TRADE_RK", "1")
     arrays, streams = fuzz_workload(shape, seed, n_clusters=12, J=500, blocking=False)
+    if shape == "w32":
+        assert_float_sum_regime(arrays)
     g = gpu_trade(arrays, streams, driven=True)
-    assert g["tstats"]["loop_form"] == 9, g["tstats"]["loop_form"]
+    assert g["tstats"]["loop_form"] == (0 if shape == "w32" else 9), g["tstats"]["loop_form"]
     assert_trade_parity(arrays, streams, g)
 
 

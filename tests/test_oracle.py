@@ -4,14 +4,21 @@ properties that pin the fast-forward restatement to the literal one-second Go lo
 The reference has no tests; these KATs (tests/golden/kats.json) are hand-derived from its source
 (SURVEY Appendix B).  No GPU needed.
 """
+import ctypes as C
+import json
+import os
+
 import numpy as np
 import pytest
 
 import oracle_ref as O
-from kat_util import kat_cluster, kat_expect, kat_streams, load_kats, seeded_workload
+import util_ref as U
+from kat_util import GOLDEN, kat_cluster, kat_expect, kat_streams, load_kats, seeded_workload
 from mcs_amd import pack_clusters
 
 KATS = load_kats()
+with open(os.path.join(GOLDEN, "kats_util.json")) as _f:
+    UTIL_KATS = json.load(_f)["resource_utilization"]
 
 
 @pytest.mark.parametrize("literal", [False, True])
@@ -96,6 +103,72 @@ def test_resource_utilization_float32_order():
         m = np.float32(m + np.float32(np.float32(cap_m[i]) - np.float32(free_m[i])))
     assert cu == np.float32(c / np.float32(160))
     assert mu == np.float32(m / np.float32(120000))
+
+
+def _f32_from_json(v):
+    return {"nan": np.float32("nan"), "+inf": np.float32("inf")}[v] if not v.startswith("0x") else \
+        np.array([int(v, 16)], np.uint32).view(np.float32)[0]
+
+
+@pytest.mark.parametrize("k", UTIL_KATS, ids=[k["name"] for k in UTIL_KATS])
+def test_resource_utilization_rounding_kats(k):
+    """tests/golden/kats_util.json, derived by hand from cluster.go:46-63 with float32 = 24-bit
+    significand, round to nearest even (odd integers in (2^24, 2^25) are ties between their even
+    neighbours; the one whose half is even wins):
+      order                 0 + 2^24 = 2^24; 2^24 + 1 is a tie -> 2^24 (even significand), twice.  Reversed
+                            1 + 1 = 2, 2 + 2^24 = 2^24 + 2 exactly; so does the integer sum.  Divisor
+                            float32(2^24 + 2) is exact; 2^24 / (2^24 + 2) = 1 - 2^-23 + O(2^-46) -> 1 - 2^-23.
+      convert before sub.   float32(2^24 + 1) = 2^24 (tie, down to even); 2^24 - 1 = 16777215 exactly.
+                            Subtracting in integers first gives 2^24.  16777215 / 2^24 = 1 - 2^-24 exactly.
+      conversion ties       2^24 + 1 -> 2^24 (2^23 is even); 2^24 + 3 lies between 2^24 + 2 = 2 (2^23 + 1)
+                            and 2^24 + 4 = 2 (2^23 + 2): up to the even one.  Sum and divisor convert alike: 1.0.
+      total wraps to small  2^31 + 2^31 + 5 = 5 mod 2^32; terms 0, 0, 3; 3.0f / 5.0f = 0.6f = 0x3F19999A.
+      total wraps to 0      4 * 2^30 = 0 mod 2^32: 2^30 / 0.0f = +Inf when a node is in use, 0 / 0 = NaN idle.
+      empty cluster         no term, total 0: 0 / 0 = NaN.
+    Every case is checked on both columns, against the oracle and the numpy restatement."""
+    cap, free = np.array(k["cap"], np.uint64), np.array(k["free"], np.uint64)
+    want = _f32_from_json(k["util"])
+    assert U.total_u32(cap) == k["total"]
+    assert U.serial_sum(cap, free) == np.float32(k["sum"]) and float(np.float32(k["sum"])) == k["sum"]
+    assert U.same(U.utilization(cap, free), want)
+    # the oracle's sum alone (a divisor of 1), then its utilization over the wrapping uint32 total
+    cu, mu = C.c_float(), C.c_float()
+    p = [np.ascontiguousarray(x).ctypes.data_as(O.u64p) for x in (cap, cap, free, free)]
+    O.lib().or_resource_utilization(len(cap), *p, 1, 1, C.byref(cu), C.byref(mu))
+    assert cu.value == k["sum"] and mu.value == k["sum"]
+    cu, mu = O.resource_utilization(cap, cap, free, free)
+    assert U.same(np.float32(cu), want) and U.same(np.float32(mu), want), (cu, mu, want)
+    if k["name"] == "order":
+        w = U.wrong_sums(cap, free)
+        assert w["reversed"] == 16777218 and w["integer"] == 16777218
+    if k["name"] == "convert_before_subtracting":
+        assert U.wrong_sums(cap, free)["integer"] == 16777216
+
+
+def w32_clusters(n=200, seed=0x7532):
+    rng = np.random.default_rng(seed)
+    return [U.w32_cluster(rng) for _ in range(n)]
+
+
+def test_resource_utilization_equals_numpy_restatement_where_sums_round():
+    """200 clusters of the 'w32' fuzz range: the memory sums pass 2^24, so every addition rounds."""
+    rounded = 0
+    for cap_c, cap_m, free_c, free_m in w32_clusters():
+        cu, mu = O.resource_utilization(cap_c, cap_m, free_c, free_m)
+        wc, wm = U.resource_utilization(cap_c, cap_m, free_c, free_m)
+        assert U.same(np.float32(cu), wc) and U.same(np.float32(mu), wm), (cu, wc, mu, wm)
+        rounded += float(U.serial_sum(cap_m, free_m)) != float(sum(int(c) - int(f) for c, f in zip(cap_m, free_m)))
+    assert rounded >= 100, rounded
+
+
+def test_wrong_sums_differ_from_the_serial_sum():
+    """The inputs above tell the Go sum from each wrong method in at least half of the clusters."""
+    differ = {}
+    for cap_c, cap_m, free_c, free_m in w32_clusters():
+        for name, d in U.discriminates(cap_m, free_m).items():
+            differ[name] = differ.get(name, 0) + d
+    assert sorted(differ) == ["float64", "integer", "reversed", "tree"]
+    assert min(differ.values()) >= 100, differ
 
 
 @pytest.mark.parametrize("kind,jobs", [("small", 600), ("big", 600), ("n64", 400), ("n64_hot", 400)])
