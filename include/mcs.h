@@ -294,8 +294,9 @@ int mcs_resource_utilization(mcs_engine* eng, uint32_t cluster, float* core_util
  * (trader_server.go:24-47) would send at simulated second t_s, rebuilt from the last FIFO/DELAY
  * run's placements: the counters after second t_s (jobs with start <= t_s < finish hold their
  * node), GetResourceUtilization over them (cluster.go:46-63, float32 in node order) and the Run
- * totals (cluster.go:26-40).  average_wait_time is not part of it (host side: mcs_read_delay_stats
- * at the end of a DELAY run, 0 under FIFO where "/delay" never feeds WaitTime). */
+ * totals (cluster.go:26-40).  average_wait_time (trader_server.go:39) is not in this record: under
+ * DELAY it is mcs_wait_time_series at t_s (the value at the end of the run: mcs_read_delay_stats),
+ * under FIFO it is 0, since only "/delay" feeds WaitTime. */
 typedef struct mcs_cluster_state {
     float cores_utilization;
     float memory_utilization;
@@ -317,9 +318,9 @@ int mcs_cluster_states(mcs_engine* eng, uint32_t t_s, mcs_cluster_state* out, ui
  * (server.go:75) and falls at each placement (scheduler.go:320,348).  The engine reports it with
  * this one definition under FIFO as well; the reference never moves the counter under FIFO.
  * A zero-duration job is queued on [arrival, start) and never running; an unplaced job stays queued
- * for every t_k >= arrival.  average_wait_time is not part of a sample, as it is not part of
- * mcs_cluster_state: WaitTime depends on each pending job's last attempt, so it is not a function
- * of the placements at t. */
+ * for every t_k >= arrival.  average_wait_time, the stream's last field, is a series of its own,
+ * mcs_wait_time_series below: WaitTime depends on each pending job's last attempt, which follows
+ * from the arrivals and starts of the whole stream up to t, not from the jobs placed at t. */
 typedef struct mcs_cluster_sample {   /* 16 B */
     float cores_utilization;          /* as mcs_cluster_state, at t_k                        */
     float memory_utilization;
@@ -340,6 +341,31 @@ typedef struct mcs_cluster_sample {   /* 16 B */
 int mcs_cluster_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                              mcs_cluster_sample* out, mcs_cluster_state* first, uint32_t n_clusters,
                              double* kernel_ms);
+
+/* ---- the average wait time series of a DELAY run: the Start stream's last field -------------- */
+/* ClusterState.AverageWaitTime (trader_server.go:39), the value the trader's WaitTime policy reads
+ * (trader.go:138) and RunMetrics records every 5 s (metrics.go:25-30): the scheduler's WaitTime
+ * (scheduler.go:47-63) after the Delay iteration at simulated second t (SDELAY, DESIGN.md §10:
+ * releases, arrivals, the Level1 pass, the Level0 head). */
+typedef struct mcs_wait_sample {      /* 24 B */
+    double average_wait_time;         /* WaitTime.GetAverage() (scheduler.go:56-63), milliseconds:
+                                         (double)total_wait_ms / (double)jobs_count, 0 for no jobs */
+    int64_t total_wait_ms;            /* WaitTime.TotalTime                                       */
+    int64_t jobs_count;               /* WaitTime.JobsCount: arrivals <= t (server.go:72)          */
+} mcs_wait_sample;
+
+/* Every sample t_k = t0_s + k * period_s, k < n_samples, of every cluster, rebuilt on the GPU from the
+ * last DELAY run's arrivals and starts and the engine's max_wait_s: the Level1
+ * removal without i-- (D6) is followed, so an entry stepped over at t_k keeps its earlier value.
+ * out[c * n_samples + k] is cluster c at t_k.  The Go loop is continued past the run's end: a cluster
+ * whose jobs are all placed keeps its final values, a deadlocked one examines the Level1 jobs it has
+ * left every second, so their share keeps growing.  A cluster's sample at its own t_end
+ * (mcs_cluster_stats) equals mcs_read_delay_stats in total_wait_ms and jobs_count.
+ * MCS_E_STATE: before a run, after a FIFO run, after a trading run, after mcs_append_jobs.
+ * MCS_E_INVALID: period_s == 0, n_samples == 0, out == NULL, n_clusters above the engine's count, or
+ * a last sample past 0xFFFFFFFE.  kernel_ms (may be NULL) receives the summed device time. */
+int mcs_wait_time_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                         mcs_wait_sample* out, uint32_t n_clusters, double* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -928,4 +928,74 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     return MCS_OK;
 }
 
+int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                         mcs_wait_sample* out, uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (!e->has_run || !e->delay_run) return fail(e, MCS_E_STATE, "no DELAY run");
+    if (e->trade_run || e->dtrade_run)
+        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from a DELAY run without trading");
+    if (e->segmented)
+        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from batch runs (not after mcs_append_jobs)");
+    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
+    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
+    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
+        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+    for (uint32_t c = 0; c < n_clusters; ++c)  // job indices within a cluster are 32-bit on the device
+        if (e->job_off[c + 1] - e->job_off[c] > 0xFFFFFFFEull)
+            return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    if (n_clusters == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return MCS_OK;
+    }
+    // samples per launch: the device buffer stays within 256 MiB (MCS_SERIES_CHUNK overrides the count)
+    uint64_t chunk = (256ull << 20) / (sizeof(mcs_wait_sample) * (uint64_t)n_clusters);
+    if (const char* env = getenv("MCS_SERIES_CHUNK"))
+        if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_samples) chunk = n_samples;
+    const uint64_t nj = e->job_off[n_clusters] ? e->job_off[n_clusters] : 1;
+    mcs_wait_sample* d_out = nullptr;
+    uint4* d_rec = nullptr;
+    uint2* d_ev = nullptr;
+    hipError_t st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_wait_sample));
+    if (st == hipSuccess) st = hipMalloc(&d_rec, nj * sizeof(uint4));
+    if (st == hipSuccess) st = hipMalloc(&d_ev, nj * sizeof(uint2));
+    mcs::WaitArgs a{};
+    a.jobs = e->d_jobs;
+    a.job_off = e->d_job_off;
+    a.out_node = e->d_out_node;
+    a.out_start = e->d_out_start;
+    a.rec = d_rec;
+    a.ev = d_ev;
+    a.out = d_out;
+    a.max_wait = e->cfg.max_wait_s;
+    a.period = period_s;
+    a.n_clusters = n_clusters;
+    double total_ms = 0.0;
+    for (uint64_t k0 = 0; st == hipSuccess && k0 < n_samples; k0 += chunk) {
+        const uint32_t nk = (uint32_t)(n_samples - k0 < chunk ? n_samples - k0 : chunk);
+        a.t0 = (uint32_t)(t0_s + k0 * period_s);
+        a.n_samples = nk;
+        st = hipEventRecord(e->ev0, e->stream);
+        if (st == hipSuccess && k0 == 0) st = mcs::launch_wait_prep(a, e->stream);
+        if (st == hipSuccess) st = mcs::launch_wait_series(a, e->stream);
+        if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
+        total_ms += ms;
+        if (st == hipSuccess)  // the chunk's columns of every cluster's row
+            st = hipMemcpy2D(out + k0, (size_t)n_samples * sizeof(mcs_wait_sample), d_out,
+                             (size_t)nk * sizeof(mcs_wait_sample), (size_t)nk * sizeof(mcs_wait_sample),
+                             n_clusters, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_out);
+    (void)hipFree(d_rec);
+    (void)hipFree(d_ev);
+    if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("wait time series: ") + hipGetErrorString(st));
+    if (kernel_ms) *kernel_ms = total_ms;
+    return MCS_OK;
+}
+
 }  // extern "C"

@@ -164,6 +164,21 @@ inline size_t series_summ_size(uint64_t total_jobs, uint32_t n_clusters) {
 hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s);
 hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t s);
 
+// The average wait time series of a DELAY run (mcs_wait.hip): WaitTime after the Delay iteration at
+// the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters.
+struct WaitArgs {
+    const uint4* jobs;
+    const uint64_t* job_off;
+    const int32_t* out_node;
+    const uint32_t* out_start;
+    uint4* rec;            // per job {h, m, s, arrival}: wait_prep_kernel
+    uint2* ev;             // per job {the entry its Level1 placement steps over, that entry's run}: wait_skip_kernel
+    mcs_wait_sample* out;  // [n_clusters][n_samples], cluster-major
+    uint32_t max_wait, t0, period, n_samples, n_clusters;
+};
+hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s);    // rec and ev: once per call
+hipError_t launch_wait_series(const WaitArgs& a, hipStream_t s);  // one chunk of samples
+
 // Launchers (mcs_kernels.hip).  Return hipSuccess or the launch error.
 hipError_t launch_fifo(const FifoArgs& a, int npl, int pool, bool hor, hipStream_t s);
 uint32_t cu_count();  // CUs of the current device (256 on MI355X)

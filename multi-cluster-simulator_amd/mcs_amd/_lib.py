@@ -147,6 +147,14 @@ class mcs_cluster_sample(C.Structure):
     ]
 
 
+class mcs_wait_sample(C.Structure):
+    _fields_ = [
+        ("average_wait_time", C.c_double),
+        ("total_wait_ms", C.c_int64),
+        ("jobs_count", C.c_int64),
+    ]
+
+
 class mcs_delay_cluster_stats(C.Structure):
     _fields_ = [
         ("total_wait_ms", C.c_int64),
@@ -252,6 +260,8 @@ SIGNATURES = [
                                      C.POINTER(C.c_double)]),
     ("mcs_cluster_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
                                            C.POINTER(mcs_cluster_state), C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_wait_time_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_wait_sample),
+                                       C.c_uint32, C.POINTER(C.c_double)]),
     # include/mcs_trade.h
     ("mcs_set_shard", C.c_int, [vp, C.c_uint32, C.c_uint32]),
     ("mcs_comm_unique_id", C.c_int, [C.POINTER(mcs_comm_id)]),

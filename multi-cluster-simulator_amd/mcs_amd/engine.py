@@ -146,6 +146,8 @@ CLUSTER_STATE_DTYPE = np.dtype([("cores_utilization", "<f4"), ("memory_utilizati
 CLUSTER_SAMPLE_DTYPE = np.dtype([("cores_utilization", "<f4"), ("memory_utilization", "<f4"), ("running", "<u4"),
                                  ("queued", "<u4")])
 
+WAIT_SAMPLE_DTYPE = np.dtype([("average_wait_time", "<f8"), ("total_wait_ms", "<i8"), ("jobs_count", "<i8")])
+
 CONTRACT_DTYPE = np.dtype([("t", "<u4"), ("requester", "<u4"), ("winner", "<i4"), ("approvals", "<u4"),
                            ("policy", "<u4"), ("cores", "<u4"), ("mem", "<u4"), ("time_s", "<u4"), ("failed", "<u4"),
                            ("pad", "<u4")])
@@ -453,6 +455,21 @@ class Engine:
                                                  C.byref(ms)))
         return (samples, first, ms.value) if with_time else (samples, first)
 
+    def wait_time_series(self, t0_s: int, period_s: int, n_samples: int, with_time: bool = False):
+        """The average wait time series of the last DELAY run (mcs_wait_time_series): WaitTime after
+        the Delay iteration at t0_s + k * period_s, k < n_samples, as an array of shape
+        (num_clusters, n_samples) of WAIT_SAMPLE_DTYPE.  with_time: (samples, kernel ms)."""
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), WAIT_SAMPLE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(L.lib().mcs_wait_time_series(self._h, int(t0_s), int(period_s), int(n_samples),
+                                             samples.ctypes.data_as(C.POINTER(L.mcs_wait_sample)), n,
+                                             C.byref(ms)))
+        return (samples, ms.value) if with_time else samples
+
     def approve_trade(self, total_cores, total_memory, core_util, mem_util, cores, memory, time_s) -> np.ndarray:
         """mcs_approve_trade: Trader.ApproveTrade (trader.go:141-167) on the GPU for arrays of
         (responder totals + sample, contract) queries; returns 0/1 per query."""
@@ -522,4 +539,4 @@ def roofline_placements_per_s(peak_bytes_per_s: float = 8.0e12) -> float:
 
 __all__ = ["Engine", "GenParams", "JobStreams", "RunStats", "gen_cluster_host", "gen_streams_host",
            "scaled_lambda", "device_count", "CLUSTER_STATS_DTYPE", "DELAY_STATS_DTYPE", "CLUSTER_SAMPLE_DTYPE",
-           "math"]
+           "WAIT_SAMPLE_DTYPE", "math"]

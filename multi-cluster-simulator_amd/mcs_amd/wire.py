@@ -715,15 +715,22 @@ def cluster_state(cu: float, mu: float, avg_wait_ms: float, totals: Optional[Tup
                         total_cpu=tc, total_memory=tm, average_wait_time=float(avg_wait_ms))
 
 
-def start_stream(samples_row, first_record, avg_wait_ms: float = 0.0) -> List[ClusterState]:
+def start_stream(samples_row, first_record, avg_wait_ms=0.0) -> List[ClusterState]:
     """The ClusterState messages of one cluster's Start stream (trader_server.go:24-47) over a
     sampled run: samples_row is the cluster's row of Engine.cluster_state_series (one message per
     sample), first_record its full record at the first sample.  The first message carries the
-    totals, every later one none (ClusterChange, :28-34).  The series has no average_wait_time
-    (include/mcs.h), so every message carries avg_wait_ms."""
+    totals, every later one none (ClusterChange, :28-34).  avg_wait_ms is WaitTime.GetAverage() (:39):
+    one value per message — the cluster's row of Engine.wait_time_series()["average_wait_time"] over
+    the same samples — or a scalar carried by every message."""
     totals = (int(first_record["total_cpu"]), int(first_record["total_memory"]))
-    return [cluster_state(s["cores_utilization"], s["memory_utilization"], avg_wait_ms,
-                          totals=totals if k == 0 else None) for k, s in enumerate(samples_row)]
+    if np.ndim(avg_wait_ms) == 0:
+        waits = [avg_wait_ms] * len(samples_row)
+    else:
+        waits = list(avg_wait_ms)
+        if len(waits) != len(samples_row):
+            raise ValueError(f"{len(waits)} average wait times for {len(samples_row)} samples")
+    return [cluster_state(s["cores_utilization"], s["memory_utilization"], w,
+                          totals=totals if k == 0 else None) for k, (s, w) in enumerate(zip(samples_row, waits))]
 
 
 __all__ = ["Job", "WireError", "decode_job", "encode_job", "job_record", "streams_from_posts",
