@@ -97,9 +97,11 @@
 //   s50 fl   s51 byte mask of fl   s52 8 * chunk   s53 register index of the chunk
 //   s[54:55] kx, finish   s56 next clock   s57 cb   s[60:61] lanes with a free row
 //   s[62:63] one-lane exec masks   s[64:65] jobs  s[66:67] out_node  s[68:69] out_start
-//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1 (W16Q: unused)  s75 expired  s76 tmp
+//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1 (W16Q: unused)  s75 expired (W16Q: unused,
+//   its rows count out of s80)  s76 tmp
 //   s77 the wave's earliest finish  s78/s79 failed fits / bound 4J + 256 (a runaway loop ends as a
-//   pool overflow: the engine re-runs the cluster on the compiled kernel)   s80 used  s81 peak
+//   pool overflow: the engine re-runs the cluster on the compiled kernel; W16Q: s78 the failed fits
+//   left of that bound, s79 unused)   s80 used  s81 peak
 //   s82 waited (W16Q: the WaitQueue heads placed; a head waiting at the exit is s43)
 //   s83 passes without a decision  s84 release scans  s85 insert lane
 //   release: row expiry masks in s[50:55], s[60:63], s[86:91]
@@ -504,6 +506,44 @@
 #define MCS_FA_XWAITED16 MCS_FA_XWAITED_
 #define MCS_FA_XWAITED16R MCS_FA_XWAITED_
 #define MCS_FA_XWAITED16S MCS_FA_XWAITED_
+// The runaway guard (GUARD0 at the entry, GUARD at a failed fit: SCC = the bound 4J + 256 is passed) and
+// the way from a clock advance to the release scan: TOADV ends the arrival advance and the placed head's
+// sleep (the zero route's sleep is W16Q's own), ADV stands between the failed fit and the scan.  The
+// shared loop counts the failed fits up in s78 against the bound in s79, and every advance jumps to
+// mcsfa_adv, whose test skips the scan when nothing finishes by t.  W16Q has its own of each, below.
+#define MCS_FA_GUARD0_                                                                            \
+    "s_mov_b32 s78, 0\n\t"                                                                        \
+    "s_lshl2_add_u32 s79, s42, 0x100\n\t"
+#define MCS_FA_GUARD_                                                                             \
+    "s_add_u32 s78, s78, 1\n\t"                                                                   \
+    "s_cmp_gt_u32 s78, s79\n\t"
+#define MCS_FA_TOADV_ "s_branch mcsfa_adv_%=\n"
+#define MCS_FA_ADV_                                                                               \
+    "mcsfa_adv_%=:\n\t"                                                                           \
+    "s_cmp_lt_u32 s40, s77\n\t" /* nothing finishes by t: no release */                          \
+    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"
+#define MCS_FA_GUARD032 MCS_FA_GUARD0_
+#define MCS_FA_GUARD016 MCS_FA_GUARD0_
+#define MCS_FA_GUARD016R MCS_FA_GUARD0_
+#define MCS_FA_GUARD016S MCS_FA_GUARD0_
+#define MCS_FA_GUARD32 MCS_FA_GUARD_
+#define MCS_FA_GUARD16 MCS_FA_GUARD_
+#define MCS_FA_GUARD16R MCS_FA_GUARD_
+#define MCS_FA_GUARD16S MCS_FA_GUARD_
+#define MCS_FA_TOADV32 MCS_FA_TOADV_
+#define MCS_FA_TOADV16 MCS_FA_TOADV_
+#define MCS_FA_TOADV16R MCS_FA_TOADV_
+#define MCS_FA_TOADV16S MCS_FA_TOADV_
+#define MCS_FA_ADV32 MCS_FA_ADV_
+#define MCS_FA_ADV16 MCS_FA_ADV_
+#define MCS_FA_ADV16R MCS_FA_ADV_
+#define MCS_FA_ADV16S MCS_FA_ADV_
+// where the streamed loop's head (mcsfa_inner) lies, right after the entry (W16Q places it; nothing
+// falls into it but the entry, once)
+#define MCS_FA_HEAD32 ""
+#define MCS_FA_HEAD16 ""
+#define MCS_FA_HEAD16R ""
+#define MCS_FA_HEAD16S ""
 // slots of the pool (64 lanes x P rows)
 #define MCS_FA_POOLMAX32 "64*8"
 #define MCS_FA_POOLMAX16 "64*8"
@@ -546,6 +586,9 @@
     "v_perm_b32 v86, v81, v80, s72\n\t"
 #define MCS_FA_FINISH16Q ""
 #define MCS_FA_ANYFIT16Q MCS_FA_ANYFIT
+// (the record broadcasts stay: one s_load_dwordx4 per job into an SGPR quad, a pass ahead, measured
+// faster at 512 clusters and slower at 4096, where the scalar port pays 7 instructions for the three
+// v_readlane: DESIGN.md §4 "pass trim", profiles/pass_trim/steps_flagged.patch)
 #define MCS_FA_REC16Q MCS_FA_REC16
 // Zero-duration jobs (1 in 600 of the reference's streams) leave the common pass through the test
 // it runs anyway: when a batch is taken, the arrival column v94 gets 0xffffffff in the lanes of
@@ -577,8 +620,7 @@
     "s_cmp_gt_u32 s76, s40\n\t"                                                                   \
     "s_cbranch_scc0 mcsfa_zfit_%=\n\t"                                                            \
     "s_mov_b32 s40, s76\n\t" /* not arrived: sleep to it */                                      \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_branch mcsfa_adv_%=\n"                                                                     \
+    MCS_FA_CNTS_##D MCS_FA_TOADV16Q                                                               \
     "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT                                             \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
@@ -608,30 +650,57 @@
 #define MCS_FA_WAITP16Q "s_add_u32 s82, s82, 1\n\t"
 #define MCS_FA_TNEXT16Q ""
 #define MCS_FA_XWAITED16Q "s_add_u32 %[waited], s82, s43\n\t"
+// This form's failed fit falls straight into the scan: it has slept to max(t + 1, the earliest finish),
+// so something finishes by t and the advance test could never skip the scan from there.  The test is
+// run by the three paths that can skip it (the arrival advance, the placed head's sleep, the zero
+// route's sleep), each in place of its jump to the test: no release is one taken branch where it was
+// two, a release one as before.  The runaway guard counts s78 down from the bound 4J + 256 and the
+// borrow is its test (the failed fit number 4J + 257 trips it, as the shared loop's s78 > s79); s79 is
+// unused by this form.
+#define MCS_FA_GUARD016Q "s_lshl2_add_u32 s78, s42, 0x100\n\t"
+#define MCS_FA_GUARD16Q "s_sub_u32 s78, s78, 1\n\t"
+#define MCS_FA_TOADV16Q                                                                           \
+    "s_cmp_lt_u32 s40, s77\n\t" /* nothing finishes by t: no release */                          \
+    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"                                                         \
+    "s_branch mcsfa_rel_%=\n"
+#define MCS_FA_ADV16Q "mcsfa_rel_%=:\n\t"
+// The loop's head starts a 64-byte instruction line.  Where the loop lies decides up to 1.8 % of this
+// kernel's time at 4096 clusters and 3.4 % at 512 (the head at each of the eight 4-byte positions of a
+// 32-byte period, profiles/pass_trim/ab_place_*.txt: every edit before or inside the loop used to move
+// it); position 0 is one of the two best at either size, and the alignment keeps it there whatever the
+// entry code before it grows or loses.
+#define MCS_FA_HEAD16Q ".p2align 6\n\t"
 // This form's scan tests its slot rows in pairs: exec = the union of a pair's expiry masks, SCC = any
 // (one s_or_b64; exec is written by the scalar unit only, no vector instruction runs under a pair's
 // union, and exec is set to the full wave after the last pair), so a pair without an expiry, the usual
 // case, falls through on two instructions where its rows took four.  A pair with one branches to its
 // block out of line (MCS_FQ_PBODY), which tests its two rows as MCS_FR_ROW does and runs their bodies
-// (MCS_FR_REL, as every other form's) in place; the second row's test is the return when that row has no
-// expiry.  tools/scan_rows_model.py counts it on the bench stream: 14.8 scalar and branch instructions
+// (MCS_FQ_REL: every other form's MCS_FR_REL but for the count) in place; the second row's test is the
+// return when that row has no expiry.  tools/scan_rows_model.py counts it on the bench stream: 14.8 scalar and branch instructions
 // per scan where the single row tests and their returns take 17.6, for 0.46 more taken branches.
 #define MCS_FQ_PAIR(k, MA, MB)                                                                    \
     "s_or_b64 exec, " MA ", " MB "\n\t"                                                          \
     "s_cbranch_scc1 mcsfa_pb" #k "_%=\n"                                                         \
     "mcsfa_pr" #k "_%=:\n\t"
+// (MCS_FR_REL counting the released slots out of the running count itself: the peak is taken from s80
+// before the scan and nothing reads s80 inside it, so this form's scan has no released total)
+#define MCS_FQ_REL(p, MASK, F, P, A)                                                              \
+    "s_bcnt1_i32_b64 s76, " MASK "\n\t"                                                          \
+    "ds_add_u32 " A ", " P "\n\t"                                                               \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_sub_u32 s80, s80, s76\n\t"                                                                \
+    "v_or_b32 v89, 1<<" #p ", v89\n\t"
 #define MCS_FQ_PBODY(k, ra, MA, FA, PA, AA, rb, MB, FB, PB, AB)                                   \
     "mcsfa_pb" #k "_%=:\n\t"                                                                     \
     "s_and_b64 exec, " MA ", -1\n\t"                                                             \
-    "s_cbranch_scc0 mcsfa_pm" #k "_%=\n\t" MCS_FR_REL(ra, MA, FA, PA, AA) "\n"                   \
+    "s_cbranch_scc0 mcsfa_pm" #k "_%=\n\t" MCS_FQ_REL(ra, MA, FA, PA, AA) "\n"                   \
     "mcsfa_pm" #k "_%=:\n\t"                                                                     \
     "s_and_b64 exec, " MB ", -1\n\t"                                                             \
-    "s_cbranch_scc0 mcsfa_pr" #k "_%=\n\t" MCS_FR_REL(rb, MB, FB, PB, AB)                        \
+    "s_cbranch_scc0 mcsfa_pr" #k "_%=\n\t" MCS_FQ_REL(rb, MB, FB, PB, AB)                        \
     "s_branch mcsfa_pr" #k "_%=\n"
 #define MCS_FA_SCAN16Q                                                                            \
     /* the LDS node copy is refreshed from the registers first (commits do not touch it) */       \
     "ds_write_b128 v108, v[64:67]\n\t"                                                           \
-    "s_mov_b32 s75, 0\n\t"                                                                       \
     "v_cmp_ge_u32_e64 s[50:51], s40, v32\n\t"                                                    \
     "v_cmp_ge_u32_e64 s[52:53], s40, v33\n\t"                                                    \
     "v_cmp_ge_u32_e64 s[54:55], s40, v34\n\t"                                                    \
@@ -642,8 +711,7 @@
     "v_cmp_ge_u32_e64 s[90:91], s40, v39\n\t"                                                    \
     MCS_FQ_PAIR(0, "s[50:51]", "s[52:53]") MCS_FQ_PAIR(1, "s[54:55]", "s[60:61]")                 \
     MCS_FQ_PAIR(2, "s[62:63]", "s[86:87]") MCS_FQ_PAIR(3, "s[88:89]", "s[90:91]")                 \
-    "s_mov_b64 exec, -1\n\t"                                                                     \
-    "s_sub_u32 s80, s80, s75\n\t" MCS_FA_RELOAD16Q                                              \
+    "s_mov_b64 exec, -1\n\t" MCS_FA_RELOAD16Q                                                    \
     /* the lane's earliest remaining finish (released rows now hold -1) */                     \
     "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
     "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \

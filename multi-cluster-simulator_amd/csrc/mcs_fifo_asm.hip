@@ -69,9 +69,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_mov_b32 s43, 0\n\t"                                                                        \
     "s_mov_b32 s44, 0\n\t"                                                                        \
     "s_mov_b32 s47, 0\n\t"                                                                        \
-    "s_mov_b32 s57, 0\n\t"                                                                        \
-    "s_mov_b32 s78, 0\n\t"                                                                        \
-    "s_lshl2_add_u32 s79, s42, 0x100\n\t"                                                         \
+    "s_mov_b32 s57, 0\n\t" MCS_FA_GUARD0##W                                                      \
     "s_mov_b32 s80, 0\n\t"                                                                        \
     "s_mov_b32 s81, 0\n\t"                                                                        \
     "s_mov_b32 s82, 0\n\t"                                                                        \
@@ -101,7 +99,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "global_load_dwordx4 v[98:101], v121, s[64:65]\n\t"                                           \
     "s_min_u32 s41, s42, 64\n\t" MCS_FA_REC##W                                                    \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc0 mcsfa_bend_%=\n"
+    "s_cbranch_scc0 mcsfa_bend_%=\n" MCS_FA_HEAD##W
 
 #define MCS_FA_BODY(W, D, F)                                                                      \
     /* ---- one pass = one decision (scheduler.go:216-296) ---- */                               \
@@ -135,8 +133,7 @@ __device__ unsigned long long g_fa_stamps[4];
     /* (the clock moves by t + 1 here and on a failed fit: the carry is the u32 clock's overflow) */ \
     "s_mov_b32 s43, 0\n\t"                                                                        \
     "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_branch mcsfa_adv_%=\n"                                                                     \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t" MCS_FA_TOADV##W                                          \
                                                                                                   \
     /* zero-duration job: committed and released before the next decision (D3) */               \
     "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX##W                                                        \
@@ -146,18 +143,17 @@ __device__ unsigned long long g_fa_stamps[4];
                                                                                                   \
     "mcsfa_arrive_%=:\n\t" MCS_FA_ARRIVE##W                                                      \
     "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_branch mcsfa_adv_%=\n"                                                                     \
+    MCS_FA_CNTS_##D MCS_FA_TOADV##W                                                               \
                                                                                                   \
     /* no node fits: WaitQueue append (:264-268), sleep to the next completion (A.3); falls */   \
-    /* through to the release (a failed head sleeps to a completion, so it always releases) */  \
+    /* through to the release (a failed head sleeps to a completion, so it always releases: */  \
+    /* W16Q falls into the scan itself, the other forms into the advance test) */               \
     "mcsfa_nofit_%=:\n\t" MCS_FA_T0 MCS_FA_WAITQ##W /* the head waits (s43 = 1) */              \
     "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
     MCS_FA_CNTS_##D                                                                               \
     /* runaway guard: every advance moves the clock forward and a loop without decisions goes */  \
     /* through here; at most 2 failed fits per job (one per arrival, one per completion) */      \
-    "s_add_u32 s78, s78, 1\n\t"                                                                   \
-    "s_cmp_gt_u32 s78, s79\n\t"                                                                   \
+    MCS_FA_GUARD##W                                                                               \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_cmp_eq_u32 s77, -1\n\t"                                                                    \
     "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
@@ -165,10 +161,9 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
     "s_max_u32 s40, s40, s77\n\t" /* (every running job finishes after t: no wrap) */           \
     MCS_FA_T1("s95")                                                                              \
-    /* the clock has advanced: releases at the new instant (A.2 step 1) */                       \
-    "mcsfa_adv_%=:\n\t"                                                                           \
-    "s_cmp_lt_u32 s40, s77\n\t" /* nothing finishes by t: no release */                          \
-    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"                                                         \
+    /* the clock has advanced: releases at the new instant (A.2 step 1), unless nothing */       \
+    /* finishes by t (W16Q: tested by the paths that come here, MCS_FA_TOADV16Q) */              \
+    MCS_FA_ADV##W                                                                                 \
     /* release every running job with finish <= t (cluster.go:153-157) */                        \
     MCS_FA_CNTR_##D MCS_FA_T0                                                                     \
     "s_max_u32 s81, s81, s80\n\t" /* peak: used only grows between releases */                   \
