@@ -54,6 +54,17 @@
 //                                                                                              entered from inside DECIDE16Q's,
 //                                                                                              turns the mode off before its
 //                                                                                              VALU and on again to return)
+//  SALU writes M0 -> s_movrels / s_movreld         1     W16C's insert (FREE[r], m0 = 2r) and   v_readlane + s_lshl_b64 exec between
+//    reads it                                              its spill                           (the spill: s_nop 0); s_movreld
+//                                                                                              follows with m0 untouched
+//  s_set_gpr_idx_on / _idx overwrite M0            -     W16C's insert                       both relative moves come before the
+//                                                                                              region; m0 = the cursor is set
+//                                                                                              after it, as in every form
+//  VALU writes SGPR -> SALU reads it               0     W16C's row blocks and full scan      (interlocked: v_cmp s[50:51] ->
+//                                                          (s_cmp_lg_u64 right after v_cmp)    s_cmp / s_mov exec, as REPICK16Q)
+//  s_setpc_b64 to a computed address               -     W16C's mcsfa_adv1                    the eight row blocks are 64 bytes
+//                                                                                              apart from a 512-byte line, so
+//                                                                                              s74 | 64 * (t & 7) never carries
 // A reorder that moves a consumer next to its producer in the table must add the s_nop.
 
 // progress-based wave priority at each batch end: the fewer of its jobs a wave has decided, the higher
@@ -114,6 +125,8 @@
 //   v110 lane  v111 -1   v[112:113] payload  v[114:115] {node address, fin}  v117 slot address
 //   v118 frm - 1  v120 DPP min / scan temp  v121 address  v[122:123] payload  v124 lane minimum
 //   v125-v127 store temps
+// (W16C, the streamed W16R loop as built: s49, s[58:59], s74, s77, s79 and s[86:101] have their own
+// meaning, v89 and s75 none: see "W16C" below)
 #define MCS_FA_CLOBBERS                                                                            \
     "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53",  \
         "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",     \
@@ -558,6 +571,8 @@
 #define MCS_FA_NODEIDX16R MCS_FA_NODEIDX
 
 // ---- W16Q: W16R with the insert's slot handed out from a scalar lane mask (streamed loop only) -----
+// (The streamed loop is W16C, below, which shares W16Q's fit test, records, zero route, LDS node copy
+// and counters; the whole of W16Q is still what the MCS_STAMPS probe build runs.)
 // Any free slot serves an insert (a release scans every row, and the node adds commute), so the
 // insert does not look for the lowest lane's lowest free row.  It keeps a current row s49 (R, 0-7)
 // and the lanes whose row R is free and not yet handed out in s[58:59] (CUR): an insert takes CUR's
@@ -831,6 +846,320 @@
     MCS_FQ_PBODY(2, 4, "s[62:63]", "v36", "v44", "v52", 5, "s[86:87]", "v37", "v45", "v53")       \
     MCS_FQ_PBODY(3, 6, "s[88:89]", "v38", "v46", "v54", 7, "s[90:91]", "v39", "v47", "v55")       \
     MCS_FA_REPICK16Q MCS_FA_FITSTUB16Q
+
+// ---- W16C: W16Q with calendar slot rows (streamed loop only; DESIGN.md §4 "Calendar rows") ----------
+// A slot lives in row finish & 7, so a clock advance to second t compares ONE row, v(32 + (t & 7)),
+// and the wave's earliest finish is not kept at all (no lane-minimum tree, no DPP chain, no s_min per
+// insert).  Invariant, after the clock has been handled at second t: no slot has finish <= t; every
+// slot sits in row finish & 7 but the misplaced ones (their row was full: they took the next row with
+// a free lane); XMIN (s77) <= the earliest finish of any misplaced slot, 0xffffffff when there is none.
+//   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), read and written by the
+//             insert with s_movrels/s_movreld (m0 = 2r), by a release as static registers
+//   s77 XMIN   s74, s59 the address of row block 0 (512-byte aligned, 64 bytes per block), low and
+//   high word   s[58:59] the block's address (s58 = s74 | 64 * (t & 7))   s[60:61] the insert's FREE[r], s[50:51] without the lane handed
+//   out   s49 r / 64 * (t & 7) / the full scan's released count   s79 the node address of the insert; the seconds left of a failed fit's stepping
+//   v89 and v90 are not used (v90: the exact-minimum fallback's temporary)
+// The clock moves in three ways.  By one second (the placed WaitQueue head, each step of a failed fit's
+// sleep) or to a second nothing can finish before (an arrival one second on, the exact-minimum
+// fallback): mcsfa_adv1, the XMIN test and a computed jump into the row's block (MCS_FC_BLOCK), which
+// compares the row and either leaves at once (mcsfa_norel: no LDS traffic) or releases it and goes to
+// the tail (mcsfa_reltail: node reload, the head's fit test, mcsfa_fitted as W16Q's scan).  By more
+// than a second (an arrival gap), or with a misplaced slot due (t >= XMIN): mcsfa_full, every row in
+// turn against t, and after one that XMIN asked for, XMIN rebuilt as the minimum over the slots with
+// finish & 7 != row (free slots hold -1 and drop out; a gap's full scan at t < XMIN releases no
+// misplaced slot, so XMIN stands, and stays exact).  A failed fit steps second by second (each step the row compare and the XMIN
+// test); after eight steps without a release every row has been compared, and the clock jumps to the
+// exact earliest finish (lane-minimum tree + DPP, as every other form's scan end).  Nothing running
+// is s80 == 0.  A release scan is counted where something is released (mcsfa_reltail).
+// Hazards (table above): m0 is written two instructions before s_movrels reads it (one wait state
+// needed) and nothing writes it before s_movreld; s_set_gpr_idx_on / _idx overwrite m0, so both
+// relative moves come before the region, and m0 = the cursor is set after it as in every form; the
+// block's v_cmp writes s[50:51] that only SALU reads (interlocked); the DPP chains keep s_nop 1.
+#define MCS_FA_FIT16C MCS_FA_FIT16Q
+#define MCS_FA_REC16C MCS_FA_REC16
+#define MCS_FA_TAKE16C MCS_FA_TAKE16Q
+#define MCS_FA_RELOAD16C MCS_FA_RELOAD16Q
+#define MCS_FA_ZEROKX16C MCS_FA_ZEROKX16Q
+#define MCS_FA_POOLMAX16C MCS_FA_POOLMAX16Q
+#define MCS_FA_NODEIDX16C MCS_FA_NODEIDX16Q
+#define MCS_FA_XWAITED16C MCS_FA_XWAITED16Q
+#define MCS_FA_GUARD016C MCS_FA_GUARD016Q
+// (the head lies 16 bytes into its 64-byte line: of the eight 4-byte positions of the 32-byte period
+// that one measured best at 4096 and at 512 clusters, 5.758 and 3.904 ms against 5.869 and 4.048 ms on
+// the line itself and 6.078 and 4.293 ms for the loop before; every position beats that loop,
+// profiles/calendar_rows/ab_place_*.txt.  The four s_nop run once, at the entry.)
+#define MCS_FA_HEAD16C MCS_FA_HEAD16Q "s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
+#define MCS_FA_INIT16C MCS_FA_ZMASK16Q("v94") /* (batch 0) */                                     \
+    "s_mov_b64 s[86:87], -1\n\t"                                                                 \
+    "s_mov_b64 s[88:89], -1\n\t"                                                                 \
+    "s_mov_b64 s[90:91], -1\n\t"                                                                 \
+    "s_mov_b64 s[92:93], -1\n\t"                                                                 \
+    "s_mov_b64 s[94:95], -1\n\t"                                                                 \
+    "s_mov_b64 s[96:97], -1\n\t"                                                                 \
+    "s_mov_b64 s[98:99], -1\n\t"                                                                 \
+    "s_mov_b64 s[100:101], -1\n\t"                                                               \
+    "s_getpc_b64 s[58:59]\n"                                                                      \
+    "mcsfa_pc_%=:\n\t"                                                                            \
+    "s_add_u32 s74, s58, mcsfa_blk0_%=-mcsfa_pc_%=\n\t"                                           \
+    "s_addc_u32 s59, s59, 0\n\t"                                                                      \
+    "v_mov_b32 v32, -1\n\t"                                                                      \
+    "v_mov_b32 v33, -1\n\t"                                                                      \
+    "v_mov_b32 v34, -1\n\t"                                                                      \
+    "v_mov_b32 v35, -1\n\t"                                                                      \
+    "v_mov_b32 v36, -1\n\t"                                                                      \
+    "v_mov_b32 v37, -1\n\t"                                                                      \
+    "v_mov_b32 v38, -1\n\t"                                                                      \
+    "v_mov_b32 v39, -1\n\t"
+// MCS_FA_DECIDE16Q's single register-index region; the slot is the lowest free lane of row
+// r = finish & 7 (s_ff1 of an empty FREE[r] is -1: the shift then gives a bit the AND drops, SCC of
+// the AND = a slot exists; none: the spill, out of line)
+#define MCS_FA_DECIDE16C                                                                          \
+    "s_and_b32 s49, s55, 7\n\t"                                                                   \
+    "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
+    "v_readlane_b32 s51, v86, s50\n\t"                                                            \
+    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
+    "s_movrels_b64 s[60:61], s[86:87]\n\t" /* FREE[r] */                                         \
+    "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
+    "s_ff1_i32_b64 s85, s[60:61]\n\t"                                                             \
+    "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
+    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
+    "s_lshl2_add_u32 s54, s50, s53\n\t" /* kx = the node index, lane * 4 + chunk */             \
+    "s_andn2_b64 s[50:51], s[60:61], s[62:63]\n\t" /* (s50, s51 are done) */                    \
+    "s_and_b64 s[62:63], s[62:63], s[60:61]\n\t"                                                  \
+    "s_cbranch_scc0 mcsfa_sp_%=\n\t"                                                              \
+    "s_movreld_b64 s[86:87], s[50:51]\n" /* the slot is handed out */                            \
+    "mcsfa_ins_%=:\n\t"                                                                           \
+    "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
+    "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
+    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
+    "s_lshl2_add_u32 s79, s54, s73\n\t"                                                           \
+    "s_set_gpr_idx_idx s49\n\t"                                                                   \
+    "v_mov_b32 v32, s55\n\t" /* the slot: finish, payload, node address (SGPR sources) */        \
+    "v_mov_b32 v40, s48\n\t"                                                                      \
+    "v_mov_b32 v48, s79\n\t"                                                                      \
+    "s_set_gpr_idx_off\n\t"
+// the spill (out of line; returns to mcsfa_ins with s49 the row, s[62:63] the lane's mask): the first
+// row r+1 ... r+7 (mod 8) with a free lane, XMIN = min(XMIN, finish); none: the pool is full, the
+// insert runs under an empty exec (peak > 64*8 at the batch end, as W16Q)
+#define MCS_FC_SPILL                                                                              \
+    "mcsfa_sp_%=:\n\t"                                                                            \
+    "s_and_b32 s76, s55, 7\n"                                                                     \
+    "mcsfa_spl_%=:\n\t"                                                                           \
+    "s_add_u32 s49, s49, 1\n\t"                                                                   \
+    "s_and_b32 s49, s49, 7\n\t"                                                                   \
+    "s_cmp_eq_u32 s49, s76\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_spf_%=\n\t"                                                             \
+    "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
+    "s_nop 0\n\t"                                                                                 \
+    "s_movrels_b64 s[60:61], s[86:87]\n\t"                                                        \
+    "s_cmp_lg_u64 s[60:61], 0\n\t"                                                                \
+    "s_cbranch_scc0 mcsfa_spl_%=\n\t"                                                             \
+    "s_ff1_i32_b64 s85, s[60:61]\n\t"                                                             \
+    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
+    "s_andn2_b64 s[50:51], s[60:61], s[62:63]\n\t"                                                \
+    "s_movreld_b64 s[86:87], s[50:51]\n\t"                                                        \
+    "s_min_u32 s77, s77, s55\n\t"                                                                 \
+    "s_branch mcsfa_ins_%=\n"                                                                     \
+    "mcsfa_spf_%=:\n\t"                                                                           \
+    "s_mov_b64 s[62:63], 0\n\t"                                                                   \
+    "s_branch mcsfa_ins_%=\n"
+// the wave's minimum of v120 into an SGPR (MCS_FA_SCANEND's chain)
+#define MCS_FC_WMIN(DST)                                                                          \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                     \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                  \
+    "s_nop 1\n\t"                                                                                 \
+    "v_min_u32_dpp v120, v120, v120 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                  \
+    "s_nop 1\n\t"                                                                                 \
+    "v_readlane_b32 " DST ", v120, 63\n\t"
+// row p's block of the computed jump (64 bytes apart): the row against t; an expiry refreshes the LDS
+// node copy under the full wave, then hands the payloads back under exec = the expiry mask
+#define MCS_FC_BLOCK(p, F, P, A, FREE)                                                            \
+    ".p2align 6\n"                                                                                \
+    "mcsfa_blk" #p "_%=:\n\t"                                                                     \
+    "v_cmp_ge_u32_e64 s[50:51], s40, " F "\n\t"                                                  \
+    "s_cmp_lg_u64 s[50:51], 0\n\t"                                                                \
+    "s_cbranch_scc0 mcsfa_norel_%=\n\t"                                                           \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b64 exec, s[50:51]\n\t"                                                                \
+    "s_bcnt1_i32_b64 s76, s[50:51]\n\t"                                                          \
+    "ds_add_u32 " A ", " P "\n\t"                                                               \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_or_b64 " FREE ", " FREE ", s[50:51]\n\t"                                                  \
+    "s_branch mcsfa_reltail_%=\n"
+#define MCS_FC_BLOCKS                                                                             \
+    ".p2align 9\n" MCS_FC_BLOCK(0, "v32", "v40", "v48", "s[86:87]")                              \
+    MCS_FC_BLOCK(1, "v33", "v41", "v49", "s[88:89]") MCS_FC_BLOCK(2, "v34", "v42", "v50", "s[90:91]") \
+    MCS_FC_BLOCK(3, "v35", "v43", "v51", "s[92:93]") MCS_FC_BLOCK(4, "v36", "v44", "v52", "s[94:95]") \
+    MCS_FC_BLOCK(5, "v37", "v45", "v53", "s[96:97]") MCS_FC_BLOCK(6, "v38", "v46", "v54", "s[98:99]") \
+    MCS_FC_BLOCK(7, "v39", "v47", "v55", "s[100:101]")
+// the full scan's rows, one after the other (the slow path: no compare ahead of its row)
+#define MCS_FC_FROW(p, F, P, A, FREE)                                                             \
+    "v_cmp_ge_u32_e64 s[50:51], s40, " F "\n\t" /* (under the full wave) */                     \
+    "s_cmp_lg_u64 s[50:51], 0\n\t"                                                                \
+    "s_cbranch_scc0 mcsfa_fr" #p "_%=\n\t"                                                       \
+    "s_mov_b64 exec, s[50:51]\n\t"                                                                \
+    "s_bcnt1_i32_b64 s76, s[50:51]\n\t"                                                          \
+    "ds_add_u32 " A ", " P "\n\t"                                                               \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_add_u32 s49, s49, s76\n\t"                                                                \
+    "s_or_b64 " FREE ", " FREE ", s[50:51]\n\t"                                                  \
+    "s_mov_b64 exec, -1\n"                                                    \
+    "mcsfa_fr" #p "_%=:\n\t"
+// (a slot of row p counts towards XMIN when finish & 7 != p; v111 = -1)
+#define MCS_FC_XROW(p, F)                                                                         \
+    "v_and_b32 v121, 7, " F "\n\t"                                                               \
+    "v_cmp_ne_u32_e32 vcc, " #p ", v121\n\t"                                                     \
+    "v_cndmask_b32_e32 v121, v111, " F ", vcc\n\t"                                               \
+    "v_min_u32 v120, v120, v121\n\t"
+#define MCS_FC_FULL                                                                               \
+    "mcsfa_full_%=:\n\t"                                                                          \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b32 s49, 0\n\t"                                                                        \
+    MCS_FC_FROW(0, "v32", "v40", "v48", "s[86:87]") MCS_FC_FROW(1, "v33", "v41", "v49", "s[88:89]") \
+    MCS_FC_FROW(2, "v34", "v42", "v50", "s[90:91]") MCS_FC_FROW(3, "v35", "v43", "v51", "s[92:93]") \
+    MCS_FC_FROW(4, "v36", "v44", "v52", "s[94:95]") MCS_FC_FROW(5, "v37", "v45", "v53", "s[96:97]") \
+    MCS_FC_FROW(6, "v38", "v46", "v54", "s[98:99]") MCS_FC_FROW(7, "v39", "v47", "v55", "s[100:101]") \
+    "s_cmp_lt_u32 s40, s77\n\t" /* no misplaced slot was due: XMIN stands */                    \
+    "s_cbranch_scc1 mcsfa_fx_%=\n\t"                                                              \
+    "v_mov_b32 v120, -1\n\t"                                                                      \
+    MCS_FC_XROW(0, "v32") MCS_FC_XROW(1, "v33") MCS_FC_XROW(2, "v34") MCS_FC_XROW(3, "v35")      \
+    MCS_FC_XROW(4, "v36") MCS_FC_XROW(5, "v37") MCS_FC_XROW(6, "v38") MCS_FC_XROW(7, "v39")      \
+    MCS_FC_WMIN("s77") "\n"                                                                      \
+    "mcsfa_fx_%=:\n\t"                                                                            \
+    "s_mov_b32 s76, s49\n\t"                                                                      \
+    "s_cmp_eq_u32 s49, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_norel_%=\n\t"                                                           \
+    "s_branch mcsfa_reltail_%=\n"
+// the zero route's sleep to the true arrival (MCS_FA_ZROUTE16Q with this form's advance)
+#define MCS_FC_ZROUTE(D)                                                                          \
+    "mcsfa_zarr_%=:\n\t"                                                                          \
+    "v_readlane_b32 s76, v87, s47\n\t" /* the true arrival */                                    \
+    "s_cmp_lg_u32 s46, 0\n\t"                                                                     \
+    "s_cselect_b32 s76, s45, s76\n\t" /* (a non-zero job: the arrival it carries) */             \
+    "s_cmp_gt_u32 s76, s40\n\t"                                                                   \
+    "s_cbranch_scc0 mcsfa_zfit_%=\n\t"                                                            \
+    "s_sub_u32 s49, s76, s40\n\t"                                                                 \
+    "s_mov_b32 s40, s76\n\t" /* not arrived: sleep to it */                                      \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_cmp_lg_u32 s49, 1\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
+    "s_branch mcsfa_adv1_%=\n"                                                                    \
+    "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT                                             \
+    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
+    "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
+    "s_branch mcsfa_zero_%=\n"
+// the passes of this form (MCS_FA_PASS's, with its own clock advances)
+#define MCS_FC_PASS(D)                                                                            \
+    "mcsfa_inner_%=:\n\t"                                                                         \
+    "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
+    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT "\n"                        \
+    "mcsfa_fitted_%=:\n\t" /* (a release enters here, the fit test done in its tail) */          \
+    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
+    "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
+    MCS_FA_DECIDE16C                                                                              \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_mov_b32 m0, s47\n\t"                                                                       \
+    "s_add_u32 s80, s80, 1\n\t"                                                                   \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n"                                                              \
+    /* next ready job; a WaitQueue head placed sleeps 1 s (:250) */                               \
+    "mcsfa_placed_%=:\n\t"                                                                        \
+    "s_add_u32 s47, s47, 1\n\t" MCS_FA_REC16                                                      \
+    "mcsfa_loopend_%=:\n\t"                                                                       \
+    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
+    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
+    "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
+    "s_sub_u32 s41, s42, s57\n\t"                                                                 \
+    "s_min_u32 s41, s41, 64\n\t" MCS_FA_WAITP16Q                                                 \
+    "s_mov_b32 s43, 0\n\t"                                                                        \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
+    "s_branch mcsfa_adv1_%=\n"                                                                    \
+                                                                                                  \
+    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16Q                                                        \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
+    "s_branch mcsfa_placed_%=\n"                                                                  \
+                                                                                                  \
+    /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
+    /* time; after eight seconds without one, to the exact earliest finish */                    \
+    "mcsfa_nofit_%=:\n\t" MCS_FA_WAITQ16Q                                                        \
+    "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
+    MCS_FA_CNTS_##D MCS_FA_GUARD16Q                                                               \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
+    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
+    "s_mov_b32 s79, 8\n"                                                                          \
+    "mcsfa_step_%=:\n\t"                                                                          \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
+    "s_sub_u32 s79, s79, 1\n\t"                                                                   \
+    "s_cbranch_scc0 mcsfa_adv1_%=\n\t"                                                            \
+    "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
+    "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \
+    "v_min3_u32 v90, v90, v37, v38\n\t"                                                          \
+    "v_min3_u32 v120, v90, v39, v39\n\t" MCS_FC_WMIN("s76")                                      \
+    "s_mov_b32 s79, 8\n\t"                                                                        \
+    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_max_u32 s40, s40, s76\n\t"                                                                 \
+    "s_branch mcsfa_adv1_%=\n"                                                                    \
+                                                                                                  \
+    "mcsfa_arrive_%=:\n\t" MCS_FA_ARRIVE16Q                                                      \
+    "s_sub_u32 s76, s45, s40\n\t"                                                                 \
+    "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_cmp_lg_u32 s76, 1\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_full_%=\n"                                                              \
+    /* the clock has moved to a second nothing but its own row's slots, or a misplaced one, can */ \
+    /* have finished by */                                                                        \
+    "mcsfa_adv1_%=:\n\t"                                                                          \
+    "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
+    "s_and_b32 s49, s40, 7\n\t"                                                                   \
+    "s_lshl_b32 s49, s49, 6\n\t"                                                                  \
+    "s_or_b32 s58, s74, s49\n\t"                                                                  \
+    "s_setpc_b64 s[58:59]\n"                                                                      \
+    /* nothing released: a failed fit's sleep goes on, every other advance ends */               \
+    "mcsfa_norel_%=:\n\t"                                                                         \
+    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_step_%=\n\t"                                                            \
+    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
+    "s_branch mcsfa_loopend_%=\n"                                                                 \
+    /* released (s76 slots; exec any): the peak before the count falls, the node reload, the */  \
+    /* head's fit test and the pass-head tests (MCS_FA_SCANEND16Q's, less the minimum) */        \
+    "mcsfa_reltail_%=:\n\t" MCS_FA_CNTR_##D                                                      \
+    "s_max_u32 s81, s81, s80\n\t"                                                                 \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16Q                                               \
+    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
+    "s_cselect_b32 s76, s45, -1\n\t" /* the head's arrival; none: never */                       \
+    "s_add_u32 s55, s40, s46\n\t"    /* finish */                                                \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
+    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
+    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
+    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
+    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "s_cmp_le_u32 s76, s40\n\t" /* (the wait state the v_perm's read of v81 needs) */            \
+    "v_perm_b32 v86, v81, v80, s72\n\t" MCS_FA_ANYFIT                                            \
+    "s_cbranch_scc1 mcsfa_fitted_%=\n\t"                                                          \
+    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
+    "s_branch mcsfa_loopend_%=\n" MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D) MCS_FC_BLOCKS
 
 // the pass's finish time t + duration, after the fit test (W16Q: inside its fit test)
 #define MCS_FA_FINISH32 "s_add_u32 s55, s40, s46\n\t"

@@ -26,9 +26,11 @@
 //   * Slot insert under exec = the lowest lane with a free row (s_ff1 of the free-row lanes,
 //     ANDed back with them); a full pool leaves exec empty and is caught by peak > 64*P at the
 //     batch end (the cluster is re-run with a bigger pool by the engine, as for the compiled
-//     kernel).  The counters (used, peak, waited, passes) are scalar.  The streamed W16R loop takes
-//     any free slot instead: the next lane of a current slot row, from a scalar mask (W16Q,
-//     mcs_fa_macros.h), with the same full-pool rule.
+//     kernel).  The counters (used, peak, waited, passes) are scalar.  The streamed W16R loop keeps
+//     calendar rows instead (W16C, mcs_fa_macros.h): a slot goes to row finish & 7, the lowest lane
+//     of that row's free-lane mask (eight 64-bit masks in SGPRs, read and written with
+//     s_movrels / s_movreld), or when that row is full to the next row with a free lane, with the
+//     same full-pool rule.
 //   * The cursor's lane in the batch lives in m0 for the result batch writes (v_writelane) and
 //     in s47 for the record broadcasts (v_readlane).
 //   * Release at a clock advance: every slot row's expiry lane mask is computed before the first
@@ -37,10 +39,14 @@
 //   * The ready head's arrival/clock checks and the WaitQueue bookkeeping follow fifo_kernel line
 //     by line (see the comments there); the result batch keeps the node's LDS index
 //     (chunk * 64 + lane) and converts it to the node index when it is stored.  The streamed
-//     W16R loop (W16Q) keeps its LDS node copy as one 16-byte word per lane, so its index is the
-//     node index itself; its release scan tests the slot rows in pairs and carries the head job's
-//     fit test in the DPP wait states, its zero-duration jobs leave the pass through the arrival
-//     test, and it counts a waited job where the placed WaitQueue head is handled (mcs_fa_macros.h).
+//     W16R loop (W16C) keeps its LDS node copy as one 16-byte word per lane, so its index is the
+//     node index itself; a clock advance of one second compares the one slot row of that second
+//     (a computed jump into eight row blocks) and keeps no earliest finish, a failed fit sleeps a
+//     second at a time, and an advance of more seconds, or one with a misplaced slot due, scans
+//     every row; a release ends with the head job's fit test; its zero-duration jobs leave the
+//     pass through the arrival test, and it counts a waited job where the placed WaitQueue head is
+//     handled (mcs_fa_macros.h).  The probe build (MCS_STAMPS) keeps the loop before it, W16Q: the
+//     rows tested in pairs, any free slot for an insert.
 //
 // Hazards (wait states are not inserted by the compiler inside asm): DPP reads a VGPR 2 states
 // after its write (s_nop 1), v_readlane reads a VGPR at least 1 instruction after its write, m0
@@ -101,7 +107,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc0 mcsfa_bend_%=\n" MCS_FA_HEAD##W
 
-#define MCS_FA_BODY(W, D, F)                                                                      \
+#define MCS_FA_PASS(W, D)                                                                         \
     /* ---- one pass = one decision (scheduler.go:216-296) ---- */                               \
     "mcsfa_inner_%=:\n\t"                                                                         \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
@@ -171,8 +177,10 @@ __device__ unsigned long long g_fa_stamps[4];
     /* (loopend's test, so the usual continuation is one taken branch) */                        \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W MCS_FA_ZROUTE##W(D)                             \
-                                                                                                  \
+    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W MCS_FA_ZROUTE##W(D)
+
+// the loop's ends, after the passes: the three flagged exits and the batch end
+#define MCS_FA_ENDS(W, F)                                                                         \
     "mcsfa_deadlock_%=:\n\t"                                                                      \
     "s_or_b32 s44, s44, %[fdl]\n\t"                                                               \
     "s_branch mcsfa_exit_%=\n"                                                                    \
@@ -201,6 +209,8 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_add_u32 v93, v92, v95\n\t" /* finish = start + the batch's duration column */            \
     "global_store_dword v125, v93, s[70:71] nt\n\t"                                               \
     "s_add_u32 s57, s57, 64\n\t" MCS_FA_PRIO("mcsfa_") MCS_FA_BENDTAIL_##F(W)
+
+#define MCS_FA_BODY(W, D, F) MCS_FA_PASS(W, D) MCS_FA_ENDS(W, F)
 
 // streamed records: the prefetched batch becomes current, the next one is prefetched
 #define MCS_FA_BENDTAIL_S(W)                                                                      \
@@ -247,6 +257,11 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_nop 1"
 
 #define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S(W)
+// the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes, the shared
+// entry, ends and exit; its clobbers add FREE's upper rows (the probe build keeps W16Q, whose segment
+// clocks live in s92-s99)
+#define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, S) MCS_FA_EXIT_S(16C)
+#define MCS_FC_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101"
 
 // ---- W16L: W16R with a one-job lookahead (r06; form 22) -----------------------
 // Every pass also tests the NEXT job's request (s92, read one record ahead) against the nodes as they
@@ -737,6 +752,7 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
       [fov] "i"(MCS_FLAG_OVERFLOW)
 #define MCS_FA_OPERANDS MCS_FA_OPERANDS_IO : MCS_FA_CLOBBERS
 #define MCS_FL_OPERANDS MCS_FA_OPERANDS_IO : MCS_FL_CLOBBERS
+#define MCS_FC_OPERANDS MCS_FA_OPERANDS_IO : MCS_FC_CLOBBERS
     if constexpr (LOOK) {
 #ifndef MCS_STAMPS
         if constexpr (DIAG) asm volatile(MCS_FL_LOOP(D1) MCS_FL_OPERANDS);
@@ -748,14 +764,20 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     else if constexpr (NPL == 1)
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16S, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16S, D0) MCS_FA_OPERANDS);
-    else if constexpr (RS)  // (the streamed W16R loop hands out its slots by rows: W16Q)
+    else if constexpr (RS)  // (the streamed W16R loop keeps calendar slot rows: W16C)
+#ifdef MCS_STAMPS
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16Q, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16Q, D0) MCS_FA_OPERANDS);
+#else
+        if constexpr (DIAG) asm volatile(MCS_FC_LOOP(D1) MCS_FC_OPERANDS);
+        else asm volatile(MCS_FC_LOOP(D0) MCS_FC_OPERANDS);
+#endif
     else
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16, D0) MCS_FA_OPERANDS);
 #undef MCS_FA_OPERANDS
 #undef MCS_FL_OPERANDS
+#undef MCS_FC_OPERANDS
 #undef MCS_FA_OPERANDS_IO
 #pragma clang diagnostic pop
 

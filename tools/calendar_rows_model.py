@@ -1,0 +1,175 @@
+"""Calendar slot rows of the streamed W16R loop (W16C, DESIGN.md §4 "Calendar rows") on the C4 stream:
+what the loop's clock advances compare and release when a running slot lives in row finish & 7.
+
+The loop's control flow is replayed from the oracle's start and finish seconds as in
+tools/scan_rows_model.py (the clock moves to a head's arrival, from a failed fit to the next
+completion, and by one second after a placed WaitQueue head), with the slot policy of the loop:
+  insert    row r = finish & 7, its lowest free lane; the row full: the first row r+1 ... r+7 (mod 8)
+            with a free lane (a misplaced slot; XMIN = the earliest finish of the misplaced slots);
+  advance   by one second (a placed head, a step of a failed fit's sleep, an arrival one second on):
+            t >= XMIN -> the full scan (every row, then XMIN rebuilt), else row t & 7 alone;
+            an arrival more than one second on: the full scan (XMIN rebuilt only if t >= XMIN);
+  failed    the head steps a second at a time until a step releases something; after eight steps
+  fit       without a release the clock jumps to the exact earliest finish.
+Printed per job: release scans and what they compared, spills, failed fits and the seconds their sleeps
+cross, the compares that release nothing, the running slots; and the instructions a scan issues, counted
+from the listing of the loop as built (COST below; the pair scan of the loop before it from
+tools/scan_rows_model.py's figures and MCS_FA_SCAN16Q / MCS_FA_SCANEND16Q).  Test infrastructure (the oracle).
+usage: python tools/calendar_rows_model.py [clusters]"""
+import collections
+import heapq
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "multi-cluster-simulator_amd"), os.path.join(REPO, "tests")]
+import oracle_ref as O  # noqa: E402
+from mcs_amd import GenParams  # noqa: E402
+from mcs_amd.engine import gen_cluster_host, scaled_lambda  # noqa: E402
+
+N, J, LANES, ROWS = 256, 16384, 64, 8
+
+# instructions issued, from the listing (scalar and branch | vector | LDS)
+COST = {
+    # mcsfa_adv1 (6) + the row's block with an expiry (6 | 2 | 2) + mcsfa_reltail (9 | 10 | 1)
+    "one-row scan": {"scalar": 6 + 6 + 9, "vector": 2 + 10, "lds": 3},
+    # mcsfa_adv1 + the block's compare and two scalar + mcsfa_norel (2 and the next step's 4 after a failed
+    # fit, the usual case; 4 or 5 else)
+    "empty compare": {"scalar": 6 + 2 + 6, "vector": 1, "lds": 0},
+    # MCS_FC_FULL: the advance's test (2-4) + 8 x (2 | 1) + per expiring row (6 | 1 | 1) + 5 + mcsfa_reltail
+    "full scan": {"scalar": 4 + 1 + 16 + 6 * 1.7 + 5 + 9, "vector": 8 + 1.7 + 10, "lds": 2 + 1.7},
+    # ... and XMIN's rebuild after one a misplaced slot asked for (32 vector, v_mov, 6 DPP, v_readlane | 7 s_nop)
+    "XMIN rebuild": {"scalar": 7, "vector": 40, "lds": 0},
+    # MCS_FA_SCAN16Q + MCS_FA_SCANEND16Q + the pair blocks (tools/scan_rows_model.py: 14.8 scalar and branch
+    # for the pairs) + the peak and exec (2) + two instructions of a row's body scalar, two vector, per
+    # expiring row (1.63) + the tail's 6 scalar, 4 + 7 vector of the minimum and 10 of the fit test
+    "pair scan before": {"scalar": 14.8 + 2 + 2 * 1.63 + 6, "vector": 8 + 2 * 1.63 + 4 + 7 + 10, "lds": 2 + 1.63},
+}
+
+
+def replay(arr, dur, start, finish, st):
+    free = np.ones((ROWS, LANES), bool)
+    heap = []  # (finish, row, lane, misplaced)
+    mis = []  # finishes of the misplaced slots alive (a heap)
+    t = 0
+
+    def release():
+        """-> rows released at t, misplaced among them"""
+        rows, m = set(), 0
+        while heap and heap[0][0] <= t:
+            f, row, lane, x = heapq.heappop(heap)
+            free[row, lane] = True
+            rows.add(row)
+            if x:
+                m += 1
+                mis.remove(f)
+                heapq.heapify(mis)
+        return rows, m
+
+    def full(why):
+        rows, _ = release()
+        st["full scans: " + why] += 1
+        if rows:
+            st["release scans"] += 1
+            st["scans of all eight rows"] += 1
+        else:
+            st["full scans that release nothing"] += 1
+        return bool(rows)
+
+    def adv1(kind):
+        if mis and t >= mis[0]:
+            return full("a misplaced slot is due")
+        due = heap and heap[0][0] <= t
+        if due:
+            rows, m = release()
+            assert rows == {t & 7} and not m, (rows, t)
+            st["release scans"] += 1
+            st["scans of one row"] += 1
+        else:
+            st["empty compares: " + kind] += 1
+        return bool(due)
+
+    for k in range(len(arr)):
+        if arr[k] > t:
+            gap, t = int(arr[k]) - t, int(arr[k])
+            st["arrival advances"] += 1
+            if gap == 1:
+                adv1("arrival")
+            else:
+                st["arrival gaps of 2-7 s" if gap < 8 else "arrival gaps of 8 s and more"] += 1
+                full("an arrival gap")
+        w = False
+        while int(start[k]) != t:  # a failed fit: the head sleeps to the next completion
+            assert int(start[k]) > t and heap
+            st["failed fits"] += 1
+            w = True
+            steps, sleep0 = 0, t
+            while True:
+                if steps == 8:
+                    st["exact-minimum jumps"] += 1
+                    t = heap[0][0]
+                    assert adv1("failed fit")
+                    break
+                t += 1
+                steps += 1
+                if adv1("failed fit"):
+                    break
+            st["longest sleep"] = max(st["longest sleep"], t - sleep0)
+        if dur[k]:
+            f = int(finish[k])
+            r, x = f & 7, 0
+            if not free[r].any():
+                st["spills"] += 1
+                x = 1
+                for i in range(1, ROWS):
+                    if free[(f + i) & 7].any():
+                        r = (f + i) & 7
+                        break
+                else:
+                    raise AssertionError("pool full")
+                heapq.heappush(mis, f)
+            lane = int(np.argmax(free[r]))
+            free[r, lane] = False
+            heapq.heappush(heap, (f, r, lane, x))
+            st["inserts"] += 1
+        st["running"].append(len(heap))
+        if w:  # a placed WaitQueue head sleeps one second
+            st["waited"] += 1
+            t += 1
+            adv1("placed head")
+
+
+def main():
+    gp = GenParams(seed=0x4D43535F53494D31, arrival_mode=1, lam=scaled_lambda(N, load=0.9))
+    nc = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+    st = collections.Counter()
+    st["running"] = []
+    jobs = 0
+    for ci in range(nc):
+        a, d, c, m = gen_cluster_host(gp, ci, 32, 24000, J)
+        node, start, finish = O.fifo_run(np.full(N, 32, np.uint32), np.full(N, 24000, np.uint32), a, d, c, m)[:3]
+        assert (node >= 0).all()
+        replay(a, d, start, finish, st)
+        jobs += len(a)
+    run = np.array(st.pop("running"))
+    longest = st.pop("longest sleep")
+    scans = st["release scans"]
+    out = {"clusters": nc, "jobs": jobs, "per_job": {k: round(v / jobs, 4) for k, v in sorted(st.items())},
+           "share_of_release_scans": {k: round(st[k] / scans, 4) for k in ("scans of one row", "scans of all eight rows")},
+           "longest_failed_fit_sleep_s": longest,
+           "running_slots": {"mean": round(float(run.mean()), 1), "p99": int(np.percentile(run, 99)), "max": int(run.max())},
+           "instructions_per_scan": {k: {f: round(x, 1) for f, x in v.items()} for k, v in COST.items()}}
+    one, full_, emp = st["scans of one row"], st["scans of all eight rows"], sum(v for k, v in st.items() if k.startswith("empty"))
+    for f in ("scalar", "vector", "lds"):
+        new = (one * COST["one-row scan"][f] + (full_ + st["full scans that release nothing"]) * COST["full scan"][f]
+               + st["full scans: a misplaced slot is due"] * COST["XMIN rebuild"][f] + emp * COST["empty compare"][f]) / jobs
+        old = scans * COST["pair scan before"][f] / jobs
+        out.setdefault("clock_advance_instructions_per_job", {})[f] = {"calendar rows": round(new, 2), "pair scan before": round(old, 2)}
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()
