@@ -11,49 +11,43 @@
 //
 //  hazard (CDNA3/gfx950)                           needs  where it occurs                     covered by
 //  VALU writes VGPR -> DPP reads it                  2     every DPP min/max chain (SCANEND,   s_nop 1 between the steps; before
-//                                                          the DELAY filter)                   the first: s_nop 1, or (DELAY rel)
-//                                                                                              s_mov s96 + s_nop 0;
-//                                                          MCS_FA_SCANEND16Q                   two fit-test / pass-head
-//                                                                                              instructions in every gap (none
-//                                                                                              writes v120); before the first:
-//                                                                                              s_waitcnt + 2 v_pk_sub
+//                                                          W16C's MCS_FC_WMIN, the DELAY       the first: s_nop 1, or (DELAY rel)
+//                                                          filter)                             s_mov s96 + s_nop 0
 //  SDWA / op_sel write preserving the other word     1     MCS_FA_FIT16: v80/v81 (WORD_1,      v_cmp_lt s[60:61] + v_ffbl v117
 //    -> VALU reads that VGPR (DstSelForwarding)            UNUSED_PRESERVE) -> v_perm          between (found by measurement,
-//                                                                                              tools/asm_debug.py); MCS_FA_FIT16Q:
+//                                                                                              tools/asm_debug.py); MCS_FA_FIT16C:
 //                                                                                              s_add s55 (one wait state, after
 //                                                                                              the v81 write the v_perm reads);
-//                                                                                              MCS_FA_SCANEND16Q: a DPP step and
-//                                                                                              the s_add s55 between
+//                                                                                              W16C's release tail (the same
+//                                                                                              pair): s_cmp_le_u32 between
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
-//    uses it as the lane select                            written                             from s_add/s_mov; REPICK16Q's
-//                                                                                              v_cmp writes s[58:59], which only
-//                                                                                              SALU reads: interlocked)
+//    uses it as the lane select                            written                             from s_add/s_mov)
 //  SALU writes M0 -> v_writelane with an M0 lane     1*    result writes at a Level0 decision  >= 1 other instruction between
 //    select (*not in the ISA table; kept anyway)           (HEAD, ZEROKX)                      (s_add s80 / s_ff1, s_lshl3_add)
 //                                                          DELAY G list (MCS_FD_ENUM: m0 =     s_add s86 between
 //                                                          cursor -> v_writelane v113/v118)
-//  VALU writes VGPR -> v_readlane / v_readfirstlane  1     DECIDE16R / ZEROKX read v86, v117;  >= 3 instructions between every
-//    reads it (gfx950)                                     REC16 after TAKE16; SCANEND v120     pair; SCANEND: s_nop 1;
-//                                                          SCANEND16Q v120; ZROUTE16Q v87      SCANEND16Q: s_cselect + s_cmp;
-//                                                          (written at the batch's TAKE16Q)    v87: a batch's passes apart
+//  VALU writes VGPR -> v_readlane / v_readfirstlane  1     DECIDE16R / DECIDE16C / ZEROKX      >= 3 instructions between every
+//    reads it (gfx950)                                     read v86, v117; REC16 after TAKE16; pair; SCANEND, WMIN: s_nop 1;
+//                                                          SCANEND, MCS_FC_WMIN v120;          v87: a batch's passes apart
+//                                                          MCS_FC_ZROUTE v87 (written at the
+//                                                          batch's TAKE16C)
 //                                                          DELAY G pass (r04): v_cndmask v113  >= 6 (GTEST's scalar prologue)
 //                                                          -> GTEST's v_readlane v113; v123
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
 //                                                                                              s_cmp)
 //  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch             (interlocked on gfx9; SALU
 //                                                                                              instructions between anyway)
-//  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16Q's row
-//                                                                                              pairs: s_or_b64 exec)
+//  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16C's row
+//                                                                                              blocks: s_mov_b64 exec)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
 //    rewritten
 //  VALU writes SGPR -> VMEM reads it (address/      5     none: the store/load bases s[64:71]   -
 //    soffset)                                              are SALU-written
-//  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16Q / COMMIT16 /   (the indexed moves sit between
+//  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16C / COMMIT16 /   (the indexed moves sit between
 //                                                          INSERT16R (none is open in a        on and off; no non-indexed VALU
-//                                                          release scan or its tail)           read inside a region: REPICK16Q,
-//                                                                                              entered from inside DECIDE16Q's,
-//                                                                                              turns the mode off before its
-//                                                                                              VALU and on again to return)
+//                                                          release scan or its tail)           read inside a region: W16C's spill
+//                                                                                              is scalar and returns before
+//                                                                                              DECIDE16C opens its region)
 //  SALU writes M0 -> s_movrels / s_movreld         1     W16C's insert (FREE[r], m0 = 2r) and   v_readlane + s_lshl_b64 exec between
 //    reads it                                              its spill                           (the spill: s_nop 0); s_movreld
 //                                                                                              follows with m0 untouched
@@ -61,7 +55,7 @@
 //                                                                                              region; m0 = the cursor is set
 //                                                                                              after it, as in every form
 //  VALU writes SGPR -> SALU reads it               0     W16C's row blocks and full scan      (interlocked: v_cmp s[50:51] ->
-//                                                          (s_cmp_lg_u64 right after v_cmp)    s_cmp / s_mov exec, as REPICK16Q)
+//                                                          (s_cmp_lg_u64 right after v_cmp)    s_cmp / s_mov exec)
 //  s_setpc_b64 to a computed address               -     W16C's mcsfa_adv1                    the eight row blocks are 64 bytes
 //                                                                                              apart from a 512-byte line, so
 //                                                                                              s74 | 64 * (t & 7) never carries
@@ -103,30 +97,26 @@
 // Register map of the loop (all fixed; listed as clobbers).
 //   s40 t     s41 min(64, J - cb)  s42 J   s43 have_w  s44 flags  s45 arr   s46 dur
 //   s47 cursor's lane in the batch (r - cb)  s48 (W16: {cores|mem<<16}) / s[48:49] cores, mem
-//   (W16 forms but W16Q: s49 = 0x100;  W16Q: s49 current slot row R, s[58:59] its free lanes not
-//   yet handed out, s86 the re-pick's starting row;  W16L / fused: s58, s59 their own, see there)
+//   (W16 forms: s49 = 0x100;  fused: s59 its own, see there)
 //   s50 fl   s51 byte mask of fl   s52 8 * chunk   s53 register index of the chunk
 //   s[54:55] kx, finish   s56 next clock   s57 cb   s[60:61] lanes with a free row
 //   s[62:63] one-lane exec masks   s[64:65] jobs  s[66:67] out_node  s[68:69] out_start
-//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1 (W16Q: unused)  s75 expired (W16Q: unused,
-//   its rows count out of s80)  s76 tmp
+//   s[70:71] out_finish  s72/s73 perm selectors   s74 t + 1  s75 expired  s76 tmp
 //   s77 the wave's earliest finish  s78/s79 failed fits / bound 4J + 256 (a runaway loop ends as a
-//   pool overflow: the engine re-runs the cluster on the compiled kernel; W16Q: s78 the failed fits
-//   left of that bound, s79 unused)   s80 used  s81 peak
-//   s82 waited (W16Q: the WaitQueue heads placed; a head waiting at the exit is s43)
+//   pool overflow: the engine re-runs the cluster on the compiled kernel)   s80 used  s81 peak
+//   s82 waited
 //   s83 passes without a decision  s84 release scans  s85 insert lane
 //   release: row expiry masks in s[50:55], s[60:63], s[86:91]
 //   v[64:71] nodes (W32: pairs {C, M} per chunk; W16: v64-v67)   v[72:79] fit-test differences
 //   v80-v86 fit bits / byte mask   (release: finish rows in v[72:87])
-//   (W16Q: v87 the batch's true arrival column; v94 holds 0xffffffff for its zero-duration jobs)
 //   v89 free rows  v90 earliest finish  v91-92 result batch (kx, start; finish = start + dur at
 //   the store)
 //   v[94:97] records  v[98:101] next records   v107 slot column  v108 node column  v109 node base
 //   v110 lane  v111 -1   v[112:113] payload  v[114:115] {node address, fin}  v117 slot address
 //   v118 frm - 1  v120 DPP min / scan temp  v121 address  v[122:123] payload  v124 lane minimum
 //   v125-v127 store temps
-// (W16C, the streamed W16R loop as built: s49, s[58:59], s74, s77, s79 and s[86:101] have their own
-// meaning, v89 and s75 none: see "W16C" below)
+// (W16C, the streamed W16R loop: s49, s[58:59], s74, s77-s79, s82 and s[86:101] have their own
+// meaning, v87 holds a column, v89 and s75 nothing: see "W16C" below)
 #define MCS_FA_CLOBBERS                                                                            \
     "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53",  \
         "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",     \
@@ -453,23 +443,6 @@
     "s_set_gpr_idx_off\n\t"                                                                       \
     "s_lshl_b32 s76, 1, s86\n\t"                                                                  \
     "v_xor_b32 v89, s76, v89\n\t" /* the row is taken */
-// the decision's test for a zero-duration job (s50 = the fitting lane), the hook at the head of
-// mcsfa_arrive and the out-of-line code after the release bodies: W16Q's zero-duration route
-#define MCS_FA_ZTEST                                                                              \
-    "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_zero_%=\n\t"
-#define MCS_FA_ZTEST32 MCS_FA_ZTEST
-#define MCS_FA_ZTEST16 MCS_FA_ZTEST
-#define MCS_FA_ZTEST16R MCS_FA_ZTEST
-#define MCS_FA_ZTEST16S MCS_FA_ZTEST
-#define MCS_FA_ARRIVE32 ""
-#define MCS_FA_ARRIVE16 ""
-#define MCS_FA_ARRIVE16R ""
-#define MCS_FA_ARRIVE16S ""
-#define MCS_FA_ZROUTE32(D) ""
-#define MCS_FA_ZROUTE16(D) ""
-#define MCS_FA_ZROUTE16R(D) ""
-#define MCS_FA_ZROUTE16S(D) ""
 // lanes with a fit into vcc
 #define MCS_FA_ANYFIT "v_cmp_ne_u32_e32 vcc, 0, v86\n\t"
 #define MCS_FA_ANYFIT32 MCS_FA_ANYFIT
@@ -493,70 +466,23 @@
 #define MCS_FA_ZEROKX32 MCS_FA_ZEROKX
 #define MCS_FA_ZEROKX16 MCS_FA_ZEROKX
 #define MCS_FA_ZEROKX16R MCS_FA_ZEROKX
-// The WaitQueue statistic and the scan's t + 1, at the places the loop touches them: a failed fit
-// (WAITQ: a head that joins the WaitQueue counts as waited, once: s43 tells a retry), the placed
-// WaitQueue head at the pass bound's end (WAITP), the scalar the LDS-slot scans read as t + 1 (TNEXT)
-// and the exit (XWAITED).  W16Q has its own of each, with the streamed W16R loop's macros below.
-#define MCS_FA_WAITQ_                                                                             \
-    "s_sub_u32 s76, 1, s43\n\t"                                                                   \
-    "s_add_u32 s82, s82, s76\n\t"                                                                 \
-    "s_mov_b32 s43, 1\n\t"
-#define MCS_FA_TNEXT_ "s_add_u32 s74, s40, 1\n\t"
-#define MCS_FA_XWAITED_ "s_mov_b32 %[waited], s82\n\t"
-#define MCS_FA_WAITQ32 MCS_FA_WAITQ_
-#define MCS_FA_WAITQ16 MCS_FA_WAITQ_
-#define MCS_FA_WAITQ16R MCS_FA_WAITQ_
-#define MCS_FA_WAITQ16S MCS_FA_WAITQ_
-#define MCS_FA_WAITP32 ""
-#define MCS_FA_WAITP16 ""
-#define MCS_FA_WAITP16R ""
-#define MCS_FA_WAITP16S ""
-#define MCS_FA_TNEXT32 MCS_FA_TNEXT_
-#define MCS_FA_TNEXT16 MCS_FA_TNEXT_
-#define MCS_FA_TNEXT16R MCS_FA_TNEXT_
-#define MCS_FA_TNEXT16S MCS_FA_TNEXT_
-#define MCS_FA_XWAITED32 MCS_FA_XWAITED_
-#define MCS_FA_XWAITED16 MCS_FA_XWAITED_
-#define MCS_FA_XWAITED16R MCS_FA_XWAITED_
-#define MCS_FA_XWAITED16S MCS_FA_XWAITED_
-// The runaway guard (GUARD0 at the entry, GUARD at a failed fit: SCC = the bound 4J + 256 is passed) and
-// the way from a clock advance to the release scan: TOADV ends the arrival advance and the placed head's
-// sleep (the zero route's sleep is W16Q's own), ADV stands between the failed fit and the scan.  The
-// shared loop counts the failed fits up in s78 against the bound in s79, and every advance jumps to
-// mcsfa_adv, whose test skips the scan when nothing finishes by t.  W16Q has its own of each, below.
+// What the streamed entry and exit (MCS_FA_ENTRY_S / MCS_FA_EXIT_S) take per form, W16C's with its
+// macros below: the runaway guard's start (the shared pass counts the failed fits up in s78 against the
+// bound 4J + 256 in s79), where the loop's head lies right after the entry (W16C places it; nothing falls
+// into it but the entry, once), and the WaitQueue statistic at the exit.
 #define MCS_FA_GUARD0_                                                                            \
     "s_mov_b32 s78, 0\n\t"                                                                        \
     "s_lshl2_add_u32 s79, s42, 0x100\n\t"
-#define MCS_FA_GUARD_                                                                             \
-    "s_add_u32 s78, s78, 1\n\t"                                                                   \
-    "s_cmp_gt_u32 s78, s79\n\t"
-#define MCS_FA_TOADV_ "s_branch mcsfa_adv_%=\n"
-#define MCS_FA_ADV_                                                                               \
-    "mcsfa_adv_%=:\n\t"                                                                           \
-    "s_cmp_lt_u32 s40, s77\n\t" /* nothing finishes by t: no release */                          \
-    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"
 #define MCS_FA_GUARD032 MCS_FA_GUARD0_
 #define MCS_FA_GUARD016 MCS_FA_GUARD0_
-#define MCS_FA_GUARD016R MCS_FA_GUARD0_
 #define MCS_FA_GUARD016S MCS_FA_GUARD0_
-#define MCS_FA_GUARD32 MCS_FA_GUARD_
-#define MCS_FA_GUARD16 MCS_FA_GUARD_
-#define MCS_FA_GUARD16R MCS_FA_GUARD_
-#define MCS_FA_GUARD16S MCS_FA_GUARD_
-#define MCS_FA_TOADV32 MCS_FA_TOADV_
-#define MCS_FA_TOADV16 MCS_FA_TOADV_
-#define MCS_FA_TOADV16R MCS_FA_TOADV_
-#define MCS_FA_TOADV16S MCS_FA_TOADV_
-#define MCS_FA_ADV32 MCS_FA_ADV_
-#define MCS_FA_ADV16 MCS_FA_ADV_
-#define MCS_FA_ADV16R MCS_FA_ADV_
-#define MCS_FA_ADV16S MCS_FA_ADV_
-// where the streamed loop's head (mcsfa_inner) lies, right after the entry (W16Q places it; nothing
-// falls into it but the entry, once)
 #define MCS_FA_HEAD32 ""
 #define MCS_FA_HEAD16 ""
-#define MCS_FA_HEAD16R ""
 #define MCS_FA_HEAD16S ""
+#define MCS_FA_XWAITED_ "s_mov_b32 %[waited], s82\n\t"
+#define MCS_FA_XWAITED32 MCS_FA_XWAITED_
+#define MCS_FA_XWAITED16 MCS_FA_XWAITED_
+#define MCS_FA_XWAITED16S MCS_FA_XWAITED_
 // slots of the pool (64 lanes x P rows)
 #define MCS_FA_POOLMAX32 "64*8"
 #define MCS_FA_POOLMAX16 "64*8"
@@ -570,300 +496,28 @@
 #define MCS_FA_NODEIDX16 MCS_FA_NODEIDX
 #define MCS_FA_NODEIDX16R MCS_FA_NODEIDX
 
-// ---- W16Q: W16R with the insert's slot handed out from a scalar lane mask (streamed loop only) -----
-// (The streamed loop is W16C, below, which shares W16Q's fit test, records, zero route, LDS node copy
-// and counters; the whole of W16Q is still what the MCS_STAMPS probe build runs.)
-// Any free slot serves an insert (a release scans every row, and the node adds commute), so the
-// insert does not look for the lowest lane's lowest free row.  It keeps a current row s49 (R, 0-7)
-// and the lanes whose row R is free and not yet handed out in s[58:59] (CUR): an insert takes CUR's
-// lowest lane with scalar instructions only — no v_cmp / v_ffbl of v89 in the fit test, no v_readlane
-// of the row, no v_xor.  v89 stays the truth for the other rows; bit R of v89 means "row R freed by
-// a release since it became current" (the rows' release is W16R's).  When CUR runs out the insert
-// branches out of line to the re-pick (MCS_FA_REPICK16Q), which takes the next row p = R+1 ... R+8
-// (mod 8) with a free lane: CUR = the lanes with bit p of v89, R = p, bit p cleared.  No such row:
-// the pool is full, CUR stays 0 and the insert runs under an empty exec (peak > 64*8 at the batch
-// end, as W16R).  Only an empty CUR is ever abandoned, so nothing is folded back into v89.
-// Entry: R = 0, CUR = every lane, bit 0 of v89 clear.  The release scan leaves s49 and s[58:59]
-// alone (it clobbers s[50:55], s[60:63], s[86:91]).  s49 = 0x100 and v89's sentinel bit 8 are not
-// used by this form.
-// The fit test is MCS_FA_FIT16 with the pass's finish (s_add s55) as the instruction between the
-// last SDWA-preserve write and the v_perm (hazard table, row 2), so the loop body's own is empty.
-#define MCS_FA_FIT16Q                                                                             \
-    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
-    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
-    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
-    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
-    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "s_add_u32 s55, s40, s46\n\t" /* finish; the wait state the v_perm's read of v81 needs */    \
-    "v_perm_b32 v86, v81, v80, s72\n\t"
-#define MCS_FA_FINISH16Q ""
-#define MCS_FA_ANYFIT16Q MCS_FA_ANYFIT
-// (the record broadcasts stay: one s_load_dwordx4 per job into an SGPR quad, a pass ahead, measured
-// faster at 512 clusters and slower at 4096, where the scalar port pays 7 instructions for the three
-// v_readlane: DESIGN.md §4 "pass trim", profiles/pass_trim/steps_flagged.patch)
-#define MCS_FA_REC16Q MCS_FA_REC16
-// Zero-duration jobs (1 in 600 of the reference's streams) leave the common pass through the test
-// it runs anyway: when a batch is taken, the arrival column v94 gets 0xffffffff in the lanes of
-// zero-duration jobs (the true arrivals stay in v87), so the head's arrival test sends such a job to
-// mcsfa_arrive, which tells it apart by that arrival and takes it out of line (MCS_FA_ZROUTE16Q):
-// the true arrival's test, the fit test, and then mcsfa_nofit or mcsfa_zero.  A retry after a release
-// comes back the same way.  The pass itself has no duration test.  (The clock never reaches
-// 0xffffffff in this loop and no arrival is 0xffffffff: the host bounds last arrival + sum(dur + 1)
-// below it, and streams without that bound run the compiled kernel.  A non-zero job carrying that
-// arrival would still sleep to it as before.)
-#define MCS_FA_ZMASK16Q(SRC)                                                                      \
-    "v_mov_b32 v87, " SRC "\n\t"                                                                  \
-    "v_cmp_eq_u32_e32 vcc, 0, v95\n\t"                                                            \
-    "v_cndmask_b32_e32 v94, " SRC ", v111, vcc\n\t" /* (v111 = -1) */
-#define MCS_FA_TAKE16Q                                                                            \
-    "v_mov_b32 v95, v99\n\t"                                                                      \
-    "v_min_u32 v96, 0x7fff, v100\n\t"                                                             \
-    "v_min_u32 v97, 0x7fff, v101\n\t"                                                             \
-    "v_lshl_or_b32 v96, v97, 16, v96\n\t" MCS_FA_ZMASK16Q("v98")
-#define MCS_FA_ZTEST16Q ""
-#define MCS_FA_ARRIVE16Q                                                                          \
-    "s_cmp_eq_u32 s45, -1\n\t"                                                                    \
-    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"
-#define MCS_FA_ZROUTE16Q(D)                                                                       \
-    "mcsfa_zarr_%=:\n\t"                                                                          \
-    "v_readlane_b32 s76, v87, s47\n\t" /* the true arrival */                                    \
-    "s_cmp_lg_u32 s46, 0\n\t"                                                                     \
-    "s_cselect_b32 s76, s45, s76\n\t" /* (a non-zero job: the arrival it carries) */             \
-    "s_cmp_gt_u32 s76, s40\n\t"                                                                   \
-    "s_cbranch_scc0 mcsfa_zfit_%=\n\t"                                                            \
-    "s_mov_b32 s40, s76\n\t" /* not arrived: sleep to it */                                      \
-    MCS_FA_CNTS_##D MCS_FA_TOADV16Q                                                               \
-    "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT                                             \
-    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
-    "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
-    "s_branch mcsfa_zero_%=\n"
-// The LDS node copy of this form is one 16-byte word per lane, chunk c of lane l at base + 16 * l +
-// 4 * c (v108 = base + 16 * lane, 16-byte aligned): the scan refreshes it with one ds_write_b128 of
-// v[64:67] and reloads it with one ds_read_b128.  The decision's kx (s54) is then the node index
-// lane * 4 + chunk itself: the slot's node address is still base + 4 * kx, and the result batch is
-// stored without a conversion (fa_finish: KXNODE).
-#define MCS_FA_RELOAD16Q "ds_read_b128 v[64:67], v108\n\t"
-#define MCS_FA_ZEROKX16Q                                                                          \
-    "v_readlane_b32 s51, v86, s50\n\t"                                                           \
-    "s_mov_b32 m0, s47\n\t"                                                                      \
-    "s_ff1_i32_b32 s52, s51\n\t"                                                                 \
-    "s_lshr_b32 s53, s52, 3\n\t"                                                                 \
-    "s_lshl2_add_u32 s54, s50, s53\n\t"
-#define MCS_FA_POOLMAX16Q "64*8"
-#define MCS_FA_NODEIDX16Q "v_mov_b32 v126, v91\n\t"
-// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled (the pass
-// bound's end: once per waited job, where the shared loop pays a subtract and an add at every failed
-// fit); a head still waiting when the loop leaves (deadlock, clock overflow, the runaway guard: s43 = 1
-// on exactly those exits, 0 on every other) is added at the exit.  (s43 is set at a failed fit only and
-// cleared after WAITP, before the placed head's own clock step; mcsfa_bend, and the exit from it, is
-// reached only on s43 = 0: from the entry, and from loopend's s_cmp_lg_u32 s43, 0.)  Its scan reads no
-// t + 1 (s74).
-#define MCS_FA_WAITQ16Q "s_mov_b32 s43, 1\n\t"
-#define MCS_FA_WAITP16Q "s_add_u32 s82, s82, 1\n\t"
-#define MCS_FA_TNEXT16Q ""
-#define MCS_FA_XWAITED16Q "s_add_u32 %[waited], s82, s43\n\t"
-// This form's failed fit falls straight into the scan: it has slept to max(t + 1, the earliest finish),
-// so something finishes by t and the advance test could never skip the scan from there.  The test is
-// run by the three paths that can skip it (the arrival advance, the placed head's sleep, the zero
-// route's sleep), each in place of its jump to the test: no release is one taken branch where it was
-// two, a release one as before.  The runaway guard counts s78 down from the bound 4J + 256 and the
-// borrow is its test (the failed fit number 4J + 257 trips it, as the shared loop's s78 > s79); s79 is
-// unused by this form.
-#define MCS_FA_GUARD016Q "s_lshl2_add_u32 s78, s42, 0x100\n\t"
-#define MCS_FA_GUARD16Q "s_sub_u32 s78, s78, 1\n\t"
-#define MCS_FA_TOADV16Q                                                                           \
-    "s_cmp_lt_u32 s40, s77\n\t" /* nothing finishes by t: no release */                          \
-    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"                                                         \
-    "s_branch mcsfa_rel_%=\n"
-#define MCS_FA_ADV16Q "mcsfa_rel_%=:\n\t"
-// The loop's head starts a 64-byte instruction line.  Where the loop lies decides up to 1.8 % of this
-// kernel's time at 4096 clusters and 3.4 % at 512 (the head at each of the eight 4-byte positions of a
-// 32-byte period, profiles/pass_trim/ab_place_*.txt: every edit before or inside the loop used to move
-// it); position 0 is one of the two best at either size, and the alignment keeps it there whatever the
-// entry code before it grows or loses.
-#define MCS_FA_HEAD16Q ".p2align 6\n\t"
-// This form's scan tests its slot rows in pairs: exec = the union of a pair's expiry masks, SCC = any
-// (one s_or_b64; exec is written by the scalar unit only, no vector instruction runs under a pair's
-// union, and exec is set to the full wave after the last pair), so a pair without an expiry, the usual
-// case, falls through on two instructions where its rows took four.  A pair with one branches to its
-// block out of line (MCS_FQ_PBODY), which tests its two rows as MCS_FR_ROW does and runs their bodies
-// (MCS_FQ_REL: every other form's MCS_FR_REL but for the count) in place; the second row's test is the
-// return when that row has no expiry.  tools/scan_rows_model.py counts it on the bench stream: 14.8 scalar and branch instructions
-// per scan where the single row tests and their returns take 17.6, for 0.46 more taken branches.
-#define MCS_FQ_PAIR(k, MA, MB)                                                                    \
-    "s_or_b64 exec, " MA ", " MB "\n\t"                                                          \
-    "s_cbranch_scc1 mcsfa_pb" #k "_%=\n"                                                         \
-    "mcsfa_pr" #k "_%=:\n\t"
-// (MCS_FR_REL counting the released slots out of the running count itself: the peak is taken from s80
-// before the scan and nothing reads s80 inside it, so this form's scan has no released total)
-#define MCS_FQ_REL(p, MASK, F, P, A)                                                              \
-    "s_bcnt1_i32_b64 s76, " MASK "\n\t"                                                          \
-    "ds_add_u32 " A ", " P "\n\t"                                                               \
-    "v_mov_b32 " F ", -1\n\t"                                                                    \
-    "s_sub_u32 s80, s80, s76\n\t"                                                                \
-    "v_or_b32 v89, 1<<" #p ", v89\n\t"
-#define MCS_FQ_PBODY(k, ra, MA, FA, PA, AA, rb, MB, FB, PB, AB)                                   \
-    "mcsfa_pb" #k "_%=:\n\t"                                                                     \
-    "s_and_b64 exec, " MA ", -1\n\t"                                                             \
-    "s_cbranch_scc0 mcsfa_pm" #k "_%=\n\t" MCS_FQ_REL(ra, MA, FA, PA, AA) "\n"                   \
-    "mcsfa_pm" #k "_%=:\n\t"                                                                     \
-    "s_and_b64 exec, " MB ", -1\n\t"                                                             \
-    "s_cbranch_scc0 mcsfa_pr" #k "_%=\n\t" MCS_FQ_REL(rb, MB, FB, PB, AB)                        \
-    "s_branch mcsfa_pr" #k "_%=\n"
-#define MCS_FA_SCAN16Q                                                                            \
-    /* the LDS node copy is refreshed from the registers first (commits do not touch it) */       \
-    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
-    "v_cmp_ge_u32_e64 s[50:51], s40, v32\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[52:53], s40, v33\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[54:55], s40, v34\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[60:61], s40, v35\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[62:63], s40, v36\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[86:87], s40, v37\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[88:89], s40, v38\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[90:91], s40, v39\n\t"                                                    \
-    MCS_FQ_PAIR(0, "s[50:51]", "s[52:53]") MCS_FQ_PAIR(1, "s[54:55]", "s[60:61]")                 \
-    MCS_FQ_PAIR(2, "s[62:63]", "s[86:87]") MCS_FQ_PAIR(3, "s[88:89]", "s[90:91]")                 \
-    "s_mov_b64 exec, -1\n\t" MCS_FA_RELOAD16Q                                                    \
-    /* the lane's earliest remaining finish (released rows now hold -1) */                     \
-    "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
-    "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \
-    "v_min3_u32 v90, v90, v37, v38\n\t"                                                          \
-    "v_min_u32 v90, v90, v39\n\t"
-// The end of this form's scan carries the head job's fit test (MCS_FA_FIT16Q, MCS_FA_ANYFIT) and the
-// pass-head tests in the wait states of the DPP minimum, two instructions per gap where the shared
-// MCS_FA_SCANEND has an s_nop 1: the node reload is waited for right after the lane-minimum tree
-// (the v_mov of the chain is issued under it), and every gap instruction writes registers the chain
-// does not read.  With a head job in the batch that has arrived (s47 < s41 and s45 <= t: after every
-// failed fit and every arrival advance) the scan enters the pass at mcsfa_fitted, after the fit
-// test.  Otherwise (no job left in the batch or the pass bound, or a head that has not arrived after
-// a placed WaitQueue head's sleep: s76 = -1 or a later arrival, a zero-duration job's 0xffffffff
-// included) the fit test's results are dropped (temporaries only: v72-v75, v80, v81, v86, vcc, s55)
-// and the scan ends as the shared one, at the loop's own continuation.  The same instructions are
-// issued either way, so there is one tail.  Hazards (table above): every DPP step reads v120 two
-// instructions after its write; the v_perm reads v81 two instructions (a DPP step, s_add) after
-// the SDWA write preserving its low word; v_readlane reads v120 two scalar instructions after the
-// last DPP step; no register-index region is open.
-#ifdef MCS_STAMPS
-#define MCS_FA_FITTED16Q "mcsfa_fts_%="
-#define MCS_FA_FITSTUB16Q "mcsfa_fts_%=:\n\t" MCS_FA_T1("s94") "s_branch mcsfa_fitted_%=\n"
-#else
-#define MCS_FA_FITTED16Q "mcsfa_fitted_%="
-#define MCS_FA_FITSTUB16Q ""
-#endif
-#define MCS_FA_SCANEND16Q                                                                         \
-    "v_mov_b32 v120, v90\n\t"                                                                     \
-    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
-    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
-    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
-    "v_min_u32_dpp v120, v120, v120 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"                     \
-    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
-    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
-    "v_min_u32_dpp v120, v120, v120 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                     \
-    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_min_u32_dpp v120, v120, v120 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                     \
-    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_min_u32_dpp v120, v120, v120 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                     \
-    "s_add_u32 s55, s40, s46\n\t" /* finish */                                                   \
-    "v_perm_b32 v86, v81, v80, s72\n\t"                                                           \
-    "v_min_u32_dpp v120, v120, v120 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                  \
-    MCS_FA_ANYFIT                                                                                 \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "v_min_u32_dpp v120, v120, v120 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                  \
-    "s_cselect_b32 s76, s45, -1\n\t" /* the head's arrival; none: never */                       \
-    "s_cmp_le_u32 s76, s40\n\t"                                                                   \
-    "v_readlane_b32 s77, v120, 63\n\t"                                                            \
-    "s_cbranch_scc1 " MCS_FA_FITTED16Q "\n\t"
-#define MCS_FA_INIT16Q MCS_FA_ZMASK16Q("v94") /* (batch 0) */                                     \
-    "s_mov_b32 s49, 0\n\t"                                                                       \
-    "s_mov_b64 s[58:59], -1\n\t"                                                                 \
-    "v_mov_b32 v89, 0xfe\n\t"                                                                    \
-    "v_mov_b32 v32, -1\n\t"                                                                      \
-    "v_mov_b32 v33, -1\n\t"                                                                      \
-    "v_mov_b32 v34, -1\n\t"                                                                      \
-    "v_mov_b32 v35, -1\n\t"                                                                      \
-    "v_mov_b32 v36, -1\n\t"                                                                      \
-    "v_mov_b32 v37, -1\n\t"                                                                      \
-    "v_mov_b32 v38, -1\n\t"                                                                      \
-    "v_mov_b32 v39, -1\n\t"
-// MCS_FA_DECIDE16R's single register-index region; the insert lane is CUR's lowest (s_ff1 of an
-// empty CUR is -1: the shift then gives a bit the AND drops), SCC of the AND = a slot exists
-#define MCS_FA_DECIDE16Q                                                                          \
-    "v_readlane_b32 s51, v86, s50\n\t"                                                            \
-    "s_ff1_i32_b64 s85, s[58:59]\n\t"                                                             \
-    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
-    "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
-    "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
-    "s_lshl2_add_u32 s54, s50, s53\n\t" /* kx = the node index, lane * 4 + chunk */             \
-    "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
-    "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
-    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
-    "s_and_b64 exec, s[62:63], s[58:59]\n\t"                                                      \
-    "s_cbranch_scc0 mcsfa_rp_%=\n"                                                                \
-    "mcsfa_ins_%=:\n\t"                                                                           \
-    "s_andn2_b64 s[58:59], s[58:59], s[62:63]\n\t" /* the slot is handed out */                  \
-    "s_lshl2_add_u32 s87, s54, s73\n\t"                                                           \
-    "s_set_gpr_idx_idx s49\n\t"                                                                   \
-    "v_mov_b32 v32, s55\n\t" /* the slot: finish, payload, node address (SGPR sources) */        \
-    "v_mov_b32 v40, s48\n\t"                                                                      \
-    "v_mov_b32 v48, s87\n\t"                                                                      \
-    "s_set_gpr_idx_off\n\t"
-// the re-pick (out of line, entered inside the register-index region with exec empty; returns into
-// it with exec = the insert lane, s[62:63] its mask, CUR and R the new row's).  s86 = the row it
-// started from, s76 / v120 temps.
-#define MCS_FA_REPICK16Q                                                                          \
-    "mcsfa_rp_%=:\n\t"                                                                            \
-    "s_set_gpr_idx_off\n\t"                                                                       \
-    "s_mov_b64 exec, -1\n\t"                                                                      \
-    "s_mov_b32 s86, s49\n"                                                                        \
-    "mcsfa_rpl_%=:\n\t"                                                                           \
-    "s_add_u32 s49, s49, 1\n\t"                                                                   \
-    "s_and_b32 s49, s49, 7\n\t"                                                                   \
-    "s_lshl_b32 s76, 1, s49\n\t"                                                                  \
-    "v_and_b32 v120, s76, v89\n\t"                                                                \
-    "v_cmp_ne_u32_e64 s[58:59], 0, v120\n\t"                                                      \
-    "s_cmp_lg_u64 s[58:59], 0\n\t"                                                                \
-    "s_cbranch_scc1 mcsfa_rpf_%=\n\t"                                                             \
-    "s_cmp_lg_u32 s49, s86\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_rpl_%=\n\t"                                                             \
-    "s_mov_b64 s[62:63], 0\n\t" /* every row empty: the pool is full (R is back at its start) */ \
-    "s_branch mcsfa_rpe_%=\n"                                                                     \
-    "mcsfa_rpf_%=:\n\t"                                                                           \
-    "v_xor_b32 v89, v120, v89\n\t" /* bit R clear in every lane: the row's free lanes are CUR */ \
-    "s_ff1_i32_b64 s85, s[58:59]\n\t"                                                             \
-    "s_lshl_b64 s[62:63], 1, s85\n"                                                               \
-    "mcsfa_rpe_%=:\n\t"                                                                           \
-    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
-    "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
-    "s_branch mcsfa_ins_%=\n"
-#define MCS_FA_RBODY16Q                                                                           \
-    MCS_FQ_PBODY(0, 0, "s[50:51]", "v32", "v40", "v48", 1, "s[52:53]", "v33", "v41", "v49")       \
-    MCS_FQ_PBODY(1, 2, "s[54:55]", "v34", "v42", "v50", 3, "s[60:61]", "v35", "v43", "v51")       \
-    MCS_FQ_PBODY(2, 4, "s[62:63]", "v36", "v44", "v52", 5, "s[86:87]", "v37", "v45", "v53")       \
-    MCS_FQ_PBODY(3, 6, "s[88:89]", "v38", "v46", "v54", 7, "s[90:91]", "v39", "v47", "v55")       \
-    MCS_FA_REPICK16Q MCS_FA_FITSTUB16Q
-
-// ---- W16C: W16Q with calendar slot rows (streamed loop only; DESIGN.md §4 "Calendar rows") ----------
+// ---- W16C: W16R with calendar slot rows (the streamed loop of the 129-256 node shape; DESIGN.md §4
+// "Calendar rows") ------------------------------------------------------------------------------------
 // A slot lives in row finish & 7, so a clock advance to second t compares ONE row, v(32 + (t & 7)),
 // and the wave's earliest finish is not kept at all (no lane-minimum tree, no DPP chain, no s_min per
 // insert).  Invariant, after the clock has been handled at second t: no slot has finish <= t; every
 // slot sits in row finish & 7 but the misplaced ones (their row was full: they took the next row with
 // a free lane); XMIN (s77) <= the earliest finish of any misplaced slot, 0xffffffff when there is none.
+// The free slots are scalar lane masks, one per row, so an insert finds its lane with scalar
+// instructions only (no v_cmp / v_ffbl / v_readlane of a free-row column, and the fit test carries none).
 //   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), read and written by the
 //             insert with s_movrels/s_movreld (m0 = 2r), by a release as static registers
 //   s77 XMIN   s74, s59 the address of row block 0 (512-byte aligned, 64 bytes per block), low and
 //   high word   s[58:59] the block's address (s58 = s74 | 64 * (t & 7))   s[60:61] the insert's FREE[r], s[50:51] without the lane handed
 //   out   s49 r / 64 * (t & 7) / the full scan's released count   s79 the node address of the insert; the seconds left of a failed fit's stepping
-//   v89 and v90 are not used (v90: the exact-minimum fallback's temporary)
+//   s78 the failed fits left of the runaway bound   s82 the WaitQueue heads placed (a head waiting at
+//   the exit is s43)   v87 the batch's true arrival column (v94 holds 0xffffffff for its zero-duration
+//   jobs)   v89 and v90 are not used (v90: the exact-minimum fallback's temporary), nor is s75
 // The clock moves in three ways.  By one second (the placed WaitQueue head, each step of a failed fit's
 // sleep) or to a second nothing can finish before (an arrival one second on, the exact-minimum
 // fallback): mcsfa_adv1, the XMIN test and a computed jump into the row's block (MCS_FC_BLOCK), which
 // compares the row and either leaves at once (mcsfa_norel: no LDS traffic) or releases it and goes to
-// the tail (mcsfa_reltail: node reload, the head's fit test, mcsfa_fitted as W16Q's scan).  By more
+// the tail (mcsfa_reltail: node reload, the head's fit test, and into the pass at mcsfa_fitted).  By more
 // than a second (an arrival gap), or with a misplaced slot due (t >= XMIN): mcsfa_full, every row in
 // turn against t, and after one that XMIN asked for, XMIN rebuilt as the minimum over the slots with
 // finish & 7 != row (free slots hold -1 and drop out; a gap's full scan at t < XMIN releases no
@@ -875,21 +529,74 @@
 // needed) and nothing writes it before s_movreld; s_set_gpr_idx_on / _idx overwrite m0, so both
 // relative moves come before the region, and m0 = the cursor is set after it as in every form; the
 // block's v_cmp writes s[50:51] that only SALU reads (interlocked); the DPP chains keep s_nop 1.
-#define MCS_FA_FIT16C MCS_FA_FIT16Q
+//
+// The fit test is MCS_FA_FIT16 without the insert's free-row lanes: the pass's finish (s_add s55) is
+// the instruction between the last SDWA-preserve write and the v_perm (hazard table, row 2).
+#define MCS_FA_FIT16C                                                                             \
+    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
+    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
+    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
+    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
+    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "s_add_u32 s55, s40, s46\n\t" /* finish; the wait state the v_perm's read of v81 needs */    \
+    "v_perm_b32 v86, v81, v80, s72\n\t"
+// (the record broadcasts stay: one s_load_dwordx4 per job into an SGPR quad, a pass ahead, measured
+// faster at 512 clusters and slower at 4096, where the scalar port pays 7 instructions for the three
+// v_readlane: DESIGN.md §4 "pass trim", profiles/pass_trim/steps_flagged.patch)
 #define MCS_FA_REC16C MCS_FA_REC16
-#define MCS_FA_TAKE16C MCS_FA_TAKE16Q
-#define MCS_FA_RELOAD16C MCS_FA_RELOAD16Q
-#define MCS_FA_ZEROKX16C MCS_FA_ZEROKX16Q
-#define MCS_FA_POOLMAX16C MCS_FA_POOLMAX16Q
-#define MCS_FA_NODEIDX16C MCS_FA_NODEIDX16Q
-#define MCS_FA_XWAITED16C MCS_FA_XWAITED16Q
-#define MCS_FA_GUARD016C MCS_FA_GUARD016Q
-// (the head lies 16 bytes into its 64-byte line: of the eight 4-byte positions of the 32-byte period
-// that one measured best at 4096 and at 512 clusters, 5.758 and 3.904 ms against 5.869 and 4.048 ms on
-// the line itself and 6.078 and 4.293 ms for the loop before; every position beats that loop,
-// profiles/calendar_rows/ab_place_*.txt.  The four s_nop run once, at the entry.)
-#define MCS_FA_HEAD16C MCS_FA_HEAD16Q "s_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
-#define MCS_FA_INIT16C MCS_FA_ZMASK16Q("v94") /* (batch 0) */                                     \
+// Zero-duration jobs (1 in 600 of the reference's streams) leave the common pass through the test
+// it runs anyway: when a batch is taken, the arrival column v94 gets 0xffffffff in the lanes of
+// zero-duration jobs (the true arrivals stay in v87), so the head's arrival test sends such a job to
+// mcsfa_arrive, which tells it apart by that arrival and takes it out of line (MCS_FC_ZROUTE):
+// the true arrival's test, the fit test, and then mcsfa_nofit or mcsfa_zero.  A retry after a release
+// comes back the same way.  The pass itself has no duration test.  (The clock never reaches
+// 0xffffffff in this loop and no arrival is 0xffffffff: the host bounds last arrival + sum(dur + 1)
+// below it, and streams without that bound run the compiled kernel.  A non-zero job carrying that
+// arrival would still sleep to it as before.)
+#define MCS_FA_ZMASK16C(SRC)                                                                      \
+    "v_mov_b32 v87, " SRC "\n\t"                                                                  \
+    "v_cmp_eq_u32_e32 vcc, 0, v95\n\t"                                                            \
+    "v_cndmask_b32_e32 v94, " SRC ", v111, vcc\n\t" /* (v111 = -1) */
+#define MCS_FA_TAKE16C                                                                            \
+    "v_mov_b32 v95, v99\n\t"                                                                      \
+    "v_min_u32 v96, 0x7fff, v100\n\t"                                                             \
+    "v_min_u32 v97, 0x7fff, v101\n\t"                                                             \
+    "v_lshl_or_b32 v96, v97, 16, v96\n\t" MCS_FA_ZMASK16C("v98")
+// The LDS node copy of this form is one 16-byte word per lane, chunk c of lane l at base + 16 * l +
+// 4 * c (v108 = base + 16 * lane, 16-byte aligned): a release refreshes it with one ds_write_b128 of
+// v[64:67] and reloads it with one ds_read_b128.  The decision's kx (s54) is then the node index
+// lane * 4 + chunk itself: the slot's node address is still base + 4 * kx, and the result batch is
+// stored without a conversion (fa_finish: KXNODE).
+#define MCS_FA_RELOAD16C "ds_read_b128 v[64:67], v108\n\t"
+#define MCS_FA_ZEROKX16C                                                                          \
+    "v_readlane_b32 s51, v86, s50\n\t"                                                           \
+    "s_mov_b32 m0, s47\n\t"                                                                      \
+    "s_ff1_i32_b32 s52, s51\n\t"                                                                 \
+    "s_lshr_b32 s53, s52, 3\n\t"                                                                 \
+    "s_lshl2_add_u32 s54, s50, s53\n\t"
+#define MCS_FA_POOLMAX16C "64*8"
+#define MCS_FA_NODEIDX16C "v_mov_b32 v126, v91\n\t"
+// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled (the pass
+// bound's end in MCS_FC_PASS: once per waited job, where the shared loop pays a subtract and an add at
+// every failed fit); a head still waiting when the loop leaves (deadlock, clock overflow, the runaway
+// guard: s43 = 1 on exactly those exits, 0 on every other) is added at the exit.
+#define MCS_FA_XWAITED16C "s_add_u32 %[waited], s82, s43\n\t"
+// The runaway guard counts s78 down from the bound 4J + 256 and the borrow is its test (the failed fit
+// number 4J + 257 trips it, as the shared loop's s78 > s79); s79 has another use in this form.
+#define MCS_FA_GUARD016C "s_lshl2_add_u32 s78, s42, 0x100\n\t"
+// The loop's head starts 16 bytes into a 64-byte instruction line.  Where the loop lies decides up to
+// 1.8 % of this kernel's time at 4096 clusters and 3.4 % at 512 (the head at each of the eight 4-byte
+// positions of a 32-byte period, profiles/pass_trim/ab_place_*.txt: every edit before or inside the loop
+// used to move it), and the alignment keeps it in place whatever the entry code before it grows or
+// loses.  Of the eight positions this one measured best at 4096 and at 512 clusters, 5.758 and 3.904 ms
+// against 5.869 and 4.048 ms on the line itself and 6.078 and 4.293 ms for the loop before calendar rows;
+// every position beats that loop, profiles/calendar_rows/ab_place_*.txt.  The four s_nop run once, at
+// the entry.
+#define MCS_FA_HEAD16C ".p2align 6\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
+#define MCS_FA_INIT16C MCS_FA_ZMASK16C("v94") /* (batch 0) */                                     \
     "s_mov_b64 s[86:87], -1\n\t"                                                                 \
     "s_mov_b64 s[88:89], -1\n\t"                                                                 \
     "s_mov_b64 s[90:91], -1\n\t"                                                                 \
@@ -910,7 +617,7 @@
     "v_mov_b32 v37, -1\n\t"                                                                      \
     "v_mov_b32 v38, -1\n\t"                                                                      \
     "v_mov_b32 v39, -1\n\t"
-// MCS_FA_DECIDE16Q's single register-index region; the slot is the lowest free lane of row
+// MCS_FA_DECIDE16R's single register-index region; the slot is the lowest free lane of row
 // r = finish & 7 (s_ff1 of an empty FREE[r] is -1: the shift then gives a bit the AND drops, SCC of
 // the AND = a slot exists; none: the spill, out of line)
 #define MCS_FA_DECIDE16C                                                                          \
@@ -940,7 +647,7 @@
     "s_set_gpr_idx_off\n\t"
 // the spill (out of line; returns to mcsfa_ins with s49 the row, s[62:63] the lane's mask): the first
 // row r+1 ... r+7 (mod 8) with a free lane, XMIN = min(XMIN, finish); none: the pool is full, the
-// insert runs under an empty exec (peak > 64*8 at the batch end, as W16Q)
+// insert runs under an empty exec (peak > 64*8 at the batch end, as W16R)
 #define MCS_FC_SPILL                                                                              \
     "mcsfa_sp_%=:\n\t"                                                                            \
     "s_and_b32 s76, s55, 7\n"                                                                     \
@@ -1038,7 +745,8 @@
     "s_cmp_eq_u32 s49, 0\n\t"                                                                     \
     "s_cbranch_scc1 mcsfa_norel_%=\n\t"                                                           \
     "s_branch mcsfa_reltail_%=\n"
-// the zero route's sleep to the true arrival (MCS_FA_ZROUTE16Q with this form's advance)
+// the zero route (out of line, from mcsfa_arrive): the true arrival's test and the sleep to it, or the
+// fit test and mcsfa_nofit / mcsfa_zero
 #define MCS_FC_ZROUTE(D)                                                                          \
     "mcsfa_zarr_%=:\n\t"                                                                          \
     "v_readlane_b32 s76, v87, s47\n\t" /* the true arrival */                                    \
@@ -1052,15 +760,15 @@
     "s_cmp_lg_u32 s49, 1\n\t"                                                                     \
     "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
     "s_branch mcsfa_adv1_%=\n"                                                                    \
-    "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT                                             \
+    "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT                                             \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
     "s_branch mcsfa_zero_%=\n"
-// the passes of this form (MCS_FA_PASS's, with its own clock advances)
+// the passes of this form (mcs_fifo_asm.hip's MCS_FA_PASS, with its own clock advances)
 #define MCS_FC_PASS(D)                                                                            \
     "mcsfa_inner_%=:\n\t"                                                                         \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT16Q MCS_FA_ANYFIT "\n"                        \
+    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT "\n"                        \
     "mcsfa_fitted_%=:\n\t" /* (a release enters here, the fit test done in its tail) */          \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
@@ -1079,22 +787,25 @@
     "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
     "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
     "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t" MCS_FA_WAITP16Q                                                 \
+    "s_min_u32 s41, s41, 64\n\t"                                                                  \
+    "s_add_u32 s82, s82, 1\n\t" /* waited: counted here, once per placed WaitQueue head */        \
     "s_mov_b32 s43, 0\n\t"                                                                        \
     "s_add_u32 s40, s40, 1\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
     "s_branch mcsfa_adv1_%=\n"                                                                    \
                                                                                                   \
-    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16Q                                                        \
+    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
     "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "s_branch mcsfa_placed_%=\n"                                                                  \
                                                                                                   \
     /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
     /* time; after eight seconds without one, to the exact earliest finish */                    \
-    "mcsfa_nofit_%=:\n\t" MCS_FA_WAITQ16Q                                                        \
+    "mcsfa_nofit_%=:\n\t"                                                                        \
+    "s_mov_b32 s43, 1\n\t"                                                                        \
     "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
-    MCS_FA_CNTS_##D MCS_FA_GUARD16Q                                                               \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_sub_u32 s78, s78, 1\n\t" /* the runaway guard counts down: the borrow trips it */          \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
     "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
@@ -1114,7 +825,9 @@
     "s_max_u32 s40, s40, s76\n\t"                                                                 \
     "s_branch mcsfa_adv1_%=\n"                                                                    \
                                                                                                   \
-    "mcsfa_arrive_%=:\n\t" MCS_FA_ARRIVE16Q                                                      \
+    "mcsfa_arrive_%=:\n\t"                                                                       \
+    "s_cmp_eq_u32 s45, -1\n\t" /* the arrival 0xffffffff marks a zero-duration job */             \
+    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
     "s_sub_u32 s76, s45, s40\n\t"                                                                 \
     "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
     MCS_FA_CNTS_##D                                                                               \
@@ -1137,11 +850,16 @@
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
     "s_branch mcsfa_loopend_%=\n"                                                                 \
     /* released (s76 slots; exec any): the peak before the count falls, the node reload, the */  \
-    /* head's fit test and the pass-head tests (MCS_FA_SCANEND16Q's, less the minimum) */        \
+    /* head's fit test and the pass-head tests.  With a head job in the batch that has arrived */ \
+    /* (s47 < s41 and s45 <= t) the tail enters the pass at mcsfa_fitted.  Otherwise (no job */  \
+    /* left in the batch or the pass bound, or a head that has not arrived: s76 = -1 or a later */ \
+    /* arrival, a zero-duration job's 0xffffffff included) the fit test's results are dropped */ \
+    /* (temporaries only: v72-v75, v80, v81, v86, vcc, s55) and the loop goes on at its own */   \
+    /* continuation.  The same instructions are issued either way, so there is one tail. */      \
     "mcsfa_reltail_%=:\n\t" MCS_FA_CNTR_##D                                                      \
     "s_max_u32 s81, s81, s80\n\t"                                                                 \
     "s_mov_b64 exec, -1\n\t"                                                                      \
-    "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16Q                                               \
+    "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16C                                               \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cselect_b32 s76, s45, -1\n\t" /* the head's arrival; none: never */                       \
     "s_add_u32 s55, s40, s46\n\t"    /* finish */                                                \
@@ -1160,12 +878,6 @@
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
     "s_branch mcsfa_loopend_%=\n" MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D) MCS_FC_BLOCKS
-
-// the pass's finish time t + duration, after the fit test (W16Q: inside its fit test)
-#define MCS_FA_FINISH32 "s_add_u32 s55, s40, s46\n\t"
-#define MCS_FA_FINISH16 MCS_FA_FINISH32
-#define MCS_FA_FINISH16R MCS_FA_FINISH32
-#define MCS_FA_FINISH16S MCS_FA_FINISH32
 
 // ---- W16S: W16R for clusters of at most 64 nodes (one chunk, node = lane) and 2 slot rows --------
 // (cluster_small / cluster_big: C1-C3).  The fit bit is bit 15 of one SDWA AND; no chunk pick, and
@@ -1224,14 +936,13 @@
     "s_nop 1\n\t"                                                                                 \
     "v_readlane_b32 s77, v120, 63\n\t"                                                            \
     "s_waitcnt lgkmcnt(0)\n\t"
-#define MCS_FA_SCANEND32 MCS_FA_SCANEND
-#define MCS_FA_SCANEND16 MCS_FA_SCANEND
-#define MCS_FA_SCANEND16R MCS_FA_SCANEND
-#define MCS_FA_SCANEND16S MCS_FA_SCANEND
 
 // ---- MCS_STAMPS probe build (tools/stamp_fa.py): s_memtime cycles per loop segment ------------------
 // s[92:93] segment start, s94 releases, s95 failed fits, s96 batch ends, s97 the whole loop; each
-// stamp waits for its own SMEM read (lgkmcnt, which also drains LDS): read the shares, not the time
+// stamp waits for its own SMEM read (lgkmcnt, which also drains LDS): read the shares, not the time.
+// The forms built on MCS_FA_PASS carry the stamps: W32, W16, W16S and the fused W16R / W16S loops (the
+// streamed three report them, mcs_debug_fa_stamps).  The streamed W16R loop (W16C) has none, because its
+// FREE rows occupy s92-s101: a probe build does not contain it and runs its shape on W16.
 #ifdef MCS_STAMPS
 #define MCS_FA_T0 "s_memtime s[92:93]\n\ts_waitcnt lgkmcnt(0)\n\t"
 #define MCS_FA_T1(acc)                                                                            \

@@ -45,8 +45,7 @@
 //     second at a time, and an advance of more seconds, or one with a misplaced slot due, scans
 //     every row; a release ends with the head job's fit test; its zero-duration jobs leave the
 //     pass through the arrival test, and it counts a waited job where the placed WaitQueue head is
-//     handled (mcs_fa_macros.h).  The probe build (MCS_STAMPS) keeps the loop before it, W16Q: the
-//     rows tested in pairs, any free slot for an insert.
+//     handled (mcs_fa_macros.h).
 //
 // Hazards (wait states are not inserted by the compiler inside asm): DPP reads a VGPR 2 states
 // after its write (s_nop 1), v_readlane reads a VGPR at least 1 instruction after its write, m0
@@ -111,12 +110,12 @@ __device__ unsigned long long g_fa_stamps[4];
     /* ---- one pass = one decision (scheduler.go:216-296) ---- */                               \
     "mcsfa_inner_%=:\n\t"                                                                         \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W MCS_FA_FINISH##W "\n"    \
-    "mcsfa_fitted_%=:\n\t" /* (W16Q's release scan enters here, the fit test done in its tail) */ \
+    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT##W MCS_FA_ANYFIT##W                          \
+    "s_add_u32 s55, s40, s46\n\t" /* finish */                                                   \
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    MCS_FA_ZTEST##W /* a zero-duration job: mcsfa_zero (W16Q: by way of mcsfa_arrive) */           \
-    MCS_FA_DECIDE##W                                                                              \
+    "s_cmp_eq_u32 s46, 0\n\t"    /* a zero-duration job */                                       \
+    "s_cbranch_scc1 mcsfa_zero_%=\n\t" MCS_FA_DECIDE##W                                          \
     "s_min_u32 s77, s77, s55\n\t" /* the wave's earliest finish */                                \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
@@ -125,8 +124,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_writelane_b32 v92, s40, m0\n"                                                              \
     /* next ready job; a WaitQueue head placed sleeps 1 s (:250) */                               \
     "mcsfa_placed_%=:\n\t"                                                                        \
-    "s_add_u32 s47, s47, 1\n\t"                                                                   \
- MCS_FA_REC##W                                                                                   \
+    "s_add_u32 s47, s47, 1\n\t" MCS_FA_REC##W                                                     \
     "mcsfa_loopend_%=:\n\t"                                                                       \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
@@ -135,11 +133,12 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
     "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
     "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t" MCS_FA_WAITP##W                                                 \
+    "s_min_u32 s41, s41, 64\n\t"                                                                  \
     /* (the clock moves by t + 1 here and on a failed fit: the carry is the u32 clock's overflow) */ \
     "s_mov_b32 s43, 0\n\t"                                                                        \
     "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t" MCS_FA_TOADV##W                                          \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
+    "s_branch mcsfa_adv_%=\n"                                                                     \
                                                                                                   \
     /* zero-duration job: committed and released before the next decision (D3) */               \
     "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX##W                                                        \
@@ -147,19 +146,25 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "s_branch mcsfa_placed_%=\n"                                                                  \
                                                                                                   \
-    "mcsfa_arrive_%=:\n\t" MCS_FA_ARRIVE##W                                                      \
+    "mcsfa_arrive_%=:\n\t"                                                                        \
     "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
-    MCS_FA_CNTS_##D MCS_FA_TOADV##W                                                               \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_branch mcsfa_adv_%=\n"                                                                     \
                                                                                                   \
     /* no node fits: WaitQueue append (:264-268), sleep to the next completion (A.3); falls */   \
-    /* through to the release (a failed head sleeps to a completion, so it always releases: */  \
-    /* W16Q falls into the scan itself, the other forms into the advance test) */               \
-    "mcsfa_nofit_%=:\n\t" MCS_FA_T0 MCS_FA_WAITQ##W /* the head waits (s43 = 1) */              \
+    /* through to the advance test (a failed head sleeps to a completion, so it always */       \
+    /* releases).  A head that joins the WaitQueue counts as waited, once: s43 tells a retry */  \
+    "mcsfa_nofit_%=:\n\t" MCS_FA_T0                                                              \
+    "s_sub_u32 s76, 1, s43\n\t"                                                                   \
+    "s_add_u32 s82, s82, s76\n\t"                                                                 \
+    "s_mov_b32 s43, 1\n\t"                                                                        \
     "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
     MCS_FA_CNTS_##D                                                                               \
     /* runaway guard: every advance moves the clock forward and a loop without decisions goes */  \
-    /* through here; at most 2 failed fits per job (one per arrival, one per completion) */      \
-    MCS_FA_GUARD##W                                                                               \
+    /* through here; at most 2 failed fits per job (one per arrival, one per completion), */     \
+    /* counted up in s78 against the bound 4J + 256 in s79 */                                    \
+    "s_add_u32 s78, s78, 1\n\t"                                                                   \
+    "s_cmp_gt_u32 s78, s79\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_cmp_eq_u32 s77, -1\n\t"                                                                    \
     "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
@@ -167,17 +172,20 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
     "s_max_u32 s40, s40, s77\n\t" /* (every running job finishes after t: no wrap) */           \
     MCS_FA_T1("s95")                                                                              \
-    /* the clock has advanced: releases at the new instant (A.2 step 1), unless nothing */       \
-    /* finishes by t (W16Q: tested by the paths that come here, MCS_FA_TOADV16Q) */              \
-    MCS_FA_ADV##W                                                                                 \
+    /* the clock has advanced (every advance comes here): releases at the new instant (A.2 */    \
+    /* step 1), unless nothing finishes by t */                                                  \
+    "mcsfa_adv_%=:\n\t"                                                                           \
+    "s_cmp_lt_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"                                                         \
     /* release every running job with finish <= t (cluster.go:153-157) */                        \
     MCS_FA_CNTR_##D MCS_FA_T0                                                                     \
     "s_max_u32 s81, s81, s80\n\t" /* peak: used only grows between releases */                   \
-    MCS_FA_TNEXT##W MCS_FA_SCAN##W MCS_FA_SCANEND##W MCS_FA_T1("s94")                            \
+    "s_add_u32 s74, s40, 1\n\t"   /* t + 1, read by the LDS-slot scans */                        \
+    MCS_FA_SCAN##W MCS_FA_SCANEND MCS_FA_T1("s94")                                               \
     /* (loopend's test, so the usual continuation is one taken branch) */                        \
     "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W MCS_FA_ZROUTE##W(D)
+    "s_branch mcsfa_loopend_%=\n" MCS_FA_RBODY##W
 
 // the loop's ends, after the passes: the three flagged exits and the batch end
 #define MCS_FA_ENDS(W, F)                                                                         \
@@ -258,302 +266,11 @@ __device__ unsigned long long g_fa_stamps[4];
 
 #define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S(W)
 // the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes, the shared
-// entry, ends and exit; its clobbers add FREE's upper rows (the probe build keeps W16Q, whose segment
-// clocks live in s92-s99)
+// entry, ends and exit; its clobbers add FREE's upper rows.  It carries no MCS_STAMPS segment clocks
+// (its FREE rows occupy s92-s101, where the stamps live), so the probe build does not expand it and
+// runs this shape on W16; the forms with stamps are W32, W16, W16S and the fused W16R / W16S loops
 #define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, S) MCS_FA_EXIT_S(16C)
 #define MCS_FC_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101"
-
-// ---- W16L: W16R with a one-job lookahead (r06; form 22) -----------------------
-// Every pass also tests the NEXT job's request (s92, read one record ahead) against the nodes as they
-// stand before this pass's commit (v76-v79 / v82-v83 -> byte masks v87, lanes s[94:95]), and picks
-// its first fit s58 (kx = chunk * 64 + lane) at the end of the pass.  The next pass decides from s58
-// without a fit test on its chain (the L pass) when nothing has changed since that test but this
-// pass's commit: its node s59 (h) is then the only node whose fit may have changed, and it can only
-// have lost one, so s58 != h is the exact first fit (scheduler.go:127-139: every lower node failed
-// before and still fails; s58 itself is unchanged).  s58 == h (the next job's first fit is the node
-// just committed; also the "no lookahead" code, s58 := s59) runs the full pass (F): W16R's fit test
-// of the job interleaved with the next one's.  A release (nodes gain) and a batch end (new records)
-// invalidate; an arrival advance without a release changes no node and keeps the lookahead.
-// The insert's slot (lowest lane with a free row: s85, its row s86, exec mask s[62:63]) is picked at
-// the end of the pass that changed the free rows (and after a release), off the next decision's chain.
-// Each pass type ends with its own copy of the tail, so a pass takes one taken branch, to the next
-// pass of either type.  The L pass commits with one indexed v_subrev (the job fits: the packed
-// halves do not borrow).
-//   s58 lookahead kx   s59 h   s92 next request   s[94:95] lanes where it fits   s96-s98 temps
-//   v76-v79 next diffs   v82-v83 next fit bits   v87 next byte masks
-// (r06 A/B against W16R, profiles/r06_look/: the first form, with the insert's slot on the chain and
-// two taken branches per pass, measured 6.44 vs 4.96 ms at 512 clusters)
-#define MCS_FL_SWEEP_A                                                                            \
-    "v_pk_sub_u16 v76, v64, s92\n\t"                                                              \
-    "v_pk_sub_u16 v77, v65, s92\n\t"                                                              \
-    "v_pk_sub_u16 v78, v66, s92\n\t"                                                              \
-    "v_pk_sub_u16 v79, v67, s92\n\t"                                                              \
-    "v_and_b32_sdwa v82, v76, v76 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v83, v78, v78 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v82, v77, v77 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v83, v79, v79 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t"
-// (two instructions of the caller between A and B: the SDWA-preserve hazard of MCS_FA_FIT16)
-#define MCS_FL_SWEEP_B                                                                            \
-    "v_perm_b32 v87, v83, v82, s72\n\t"                                                           \
-    "v_cmp_ne_u32_e64 s[94:95], 0, v87\n\t"
-// the F pass's two fit tests (the job's: v72-v75 -> v80/v81 -> v86 and vcc; the next one's),
-// interleaved so that each SDWA-preserve write has two instructions before its reader
-#define MCS_FL_FIT2                                                                               \
-    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
-    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
-    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
-    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
-    "v_pk_sub_u16 v76, v64, s92\n\t"                                                              \
-    "v_pk_sub_u16 v77, v65, s92\n\t"                                                              \
-    "v_pk_sub_u16 v78, v66, s92\n\t"                                                              \
-    "v_pk_sub_u16 v79, v67, s92\n\t"                                                              \
-    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v82, v76, v76 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v83, v78, v78 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v82, v77, v77 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v83, v79, v79 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_perm_b32 v86, v81, v80, s72\n\t"                                                           \
-    "v_cmp_ne_u32_e32 vcc, 0, v86\n\t"                                                            \
-    "v_perm_b32 v87, v83, v82, s72\n\t"                                                           \
-    "s_add_u32 s55, s40, s46\n\t"                                                                 \
-    "v_cmp_ne_u32_e64 s[94:95], 0, v87\n\t"
-// the record at the cursor, and the next record's request (lane 64 wraps to lane 0: a batch end
-// invalidates whatever the last pass of the batch looked ahead at)
-#define MCS_FL_REC                                                                                \
-    "v_readlane_b32 s45, v94, s47\n\t"                                                            \
-    "v_readlane_b32 s46, v95, s47\n\t"                                                            \
-    "v_readlane_b32 s48, v96, s47\n\t"                                                            \
-    "s_add_u32 s97, s47, 1\n\t"                                                                   \
-    "s_and_b32 s97, s97, 63\n\t"                                                                  \
-    "v_readlane_b32 s92, v96, s97\n\t"
-// the next insert's slot from the free rows v89 (exec = the full wave): the vector half, then the
-// scalar half a few instructions later (pool full: s[62:63] empty, s86 = 8, as MCS_FA_DECIDE16R)
-#define MCS_FL_INSPICK_V                                                                          \
-    "v_cmp_lt_u32_e64 s[60:61], s49, v89\n\t"                                                    \
-    "v_ffbl_b32 v117, v89\n\t"
-#define MCS_FL_INSPICK_S                                                                          \
-    "s_ff1_i32_b64 s85, s[60:61]\n\t"                                                             \
-    "v_readlane_b32 s86, v117, s85\n\t"                                                           \
-    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
-    "s_and_b64 s[62:63], s[62:63], s[60:61]\n\t"
-// the L pass's decision: node s58 (lane s50); commit + slot insert in one register-index region
-#define MCS_FL_DECIDE_L                                                                           \
-    "s_lshr_b32 s53, s58, 6\n\t"                                                                  \
-    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
-    "s_lshl2_add_u32 s87, s58, s73\n\t"                                                           \
-    "s_mov_b32 s54, s58\n\t"                                                                      \
-    "s_set_gpr_idx_on s53, gpr_idx(SRC1,DST)\n\t"                                                 \
-    "v_subrev_u32 v64, s48, v64\n\t" /* the commit (cluster.go:146-147) */                        \
-    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
-    "s_set_gpr_idx_idx s86\n\t"                                                                   \
-    "v_mov_b32 v32, s55\n\t"                                                                      \
-    "v_mov_b32 v40, s48\n\t"                                                                      \
-    "v_mov_b32 v48, s87\n\t"                                                                      \
-    "s_set_gpr_idx_off\n\t"                                                                       \
-    "s_lshl_b32 s76, 1, s86\n\t"                                                                  \
-    "v_xor_b32 v89, s76, v89\n\t"
-// the F pass's decision: MCS_FA_DECIDE16R with the insert's slot already picked
-#define MCS_FL_DECIDE_F                                                                           \
-    "v_readlane_b32 s51, v86, s50\n\t"                                                            \
-    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
-    "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
-    "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
-    "s_lshl3_add_u32 s54, s52, s50\n\t"                                                           \
-    "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
-    "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
-    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
-    "s_lshl2_add_u32 s87, s54, s73\n\t"                                                           \
-    "s_set_gpr_idx_idx s86\n\t"                                                                   \
-    "v_mov_b32 v32, s55\n\t"                                                                      \
-    "v_mov_b32 v40, s48\n\t"                                                                      \
-    "v_mov_b32 v48, s87\n\t"                                                                      \
-    "s_set_gpr_idx_off\n\t"                                                                       \
-    "s_lshl_b32 s76, 1, s86\n\t"                                                                  \
-    "v_xor_b32 v89, s76, v89\n\t"
-// the end of a placing pass of type X (L or F): exec back, the next insert's slot, counters and
-// results, the next job's first fit from the sweep (none: s58 = h, the next pass is an F pass),
-// and the branch to the next pass (cursor past the pass bound: mcsfl_pend)
-#define MCS_FL_TAIL(X, BACK)                                                                      \
-    "s_mov_b32 s59, s54\n\t" /* h: the node this pass committed */                                \
-    "s_mov_b64 exec, -1\n\t" MCS_FL_INSPICK_V                                                    \
-    "s_min_u32 s77, s77, s55\n\t" /* the wave's earliest finish */                                \
-    "s_mov_b32 m0, s47\n\t"                                                                       \
-    "s_add_u32 s80, s80, 1\n\t"                                                                   \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n"                                                              \
-    "mcsfl_pick" X "_%=:\n\t"                                                                     \
-    "s_mov_b32 s58, s59\n\t"                                                                      \
-    "s_cmp_lg_u64 s[94:95], 0\n\t"                                                                \
-    "s_cbranch_scc0 mcsfl_nopick_%=\n\t"                                                          \
-    "s_ff1_i32_b64 s96, s[94:95]\n\t"                                                             \
-    "v_readlane_b32 s98, v87, s96\n\t" MCS_FL_INSPICK_S                                          \
-    "s_add_u32 s47, s47, 1\n\t" MCS_FL_REC                                                        \
-    "s_ff1_i32_b32 s98, s98\n\t"                                                                  \
-    "s_lshl3_add_u32 s58, s98, s96\n\t"                                                           \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc0 mcsfl_pend_%=\n\t"                                                            \
-    "s_cmp_eq_u32 s58, s59\n\t" BACK
-#define MCS_FL_BACK_L "s_cbranch_scc0 mcsfl_innerL_%=\n\ts_branch mcsfl_innerF_%=\n"
-#define MCS_FL_BACK_F "s_cbranch_scc1 mcsfl_innerF_%=\n\ts_branch mcsfl_innerL_%=\n"
-
-// W16R's release scan with the next insert's slot picked after its rows (they free slot rows)
-#define MCS_FL_SCAN                                                                               \
-    "ds_write_b32 v108, v64 offset:0\n\t"                                                        \
-    "ds_write_b32 v108, v65 offset:256\n\t"                                                      \
-    "ds_write_b32 v108, v66 offset:512\n\t"                                                      \
-    "ds_write_b32 v108, v67 offset:768\n\t"                                                      \
-    "s_mov_b32 s75, 0\n\t"                                                                       \
-    "v_cmp_ge_u32_e64 s[50:51], s40, v32\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[52:53], s40, v33\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[54:55], s40, v34\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[60:61], s40, v35\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[62:63], s40, v36\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[86:87], s40, v37\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[88:89], s40, v38\n\t"                                                    \
-    "v_cmp_ge_u32_e64 s[90:91], s40, v39\n\t"                                                    \
-    MCS_FR_ROW(0, "s[50:51]", "v32", "v40", "v48") MCS_FR_ROW(1, "s[52:53]", "v33", "v41", "v49")  \
-    MCS_FR_ROW(2, "s[54:55]", "v34", "v42", "v50") MCS_FR_ROW(3, "s[60:61]", "v35", "v43", "v51")  \
-    MCS_FR_ROW(4, "s[62:63]", "v36", "v44", "v52") MCS_FR_ROW(5, "s[86:87]", "v37", "v45", "v53")  \
-    MCS_FR_ROW(6, "s[88:89]", "v38", "v46", "v54") MCS_FR_ROW(7, "s[90:91]", "v39", "v47", "v55")  \
-    "s_mov_b64 exec, -1\n\t" MCS_FL_INSPICK_V                                                    \
-    "s_sub_u32 s80, s80, s75\n\t" MCS_FA_RELOAD16                                               \
-    "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
-    "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \
-    "v_min3_u32 v90, v90, v37, v38\n\t"                                                          \
-    "v_min_u32 v90, v90, v39\n\t" MCS_FA_SCANEND16R MCS_FL_INSPICK_S
-
-#define MCS_FL_ENTRY                                                                              \
-    "s_mov_b32 s58, -1\n\t"                                                                       \
-    "s_mov_b32 s59, -1\n\t" MCS_FA_ENTRY_S(16R)
-// (MCS_FA_ENTRY_S(16R) ends with MCS_FA_REC16R and a branch to the batch end when the first batch is
-// empty; the first pass also needs the next request and the insert's slot)
-#define MCS_FL_BODY(D)                                                                            \
-    "s_add_u32 s97, s47, 1\n\t"                                                                   \
-    "s_and_b32 s97, s97, 63\n\t"                                                                  \
-    "v_readlane_b32 s92, v96, s97\n\t" MCS_FL_INSPICK_V                                          \
-    "s_nop 4\n\t" MCS_FL_INSPICK_S                                                                \
-    "s_branch mcsfa_inner_%=\n"                                                                   \
-    "mcsfa_loopend_%=:\n\t"                                                                       \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc0 mcsfl_pend_%=\n"                                                              \
-    "mcsfa_inner_%=:\n\t"                                                                         \
-    "s_cmp_eq_u32 s58, s59\n\t" /* no usable lookahead: the F pass */                            \
-    "s_cbranch_scc1 mcsfl_innerF_%=\n"                                                            \
-    /* ---- L pass: the job's first fit is s58 ---- */                                            \
-    "mcsfl_innerL_%=:\n\t"                                                                        \
-    "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FL_SWEEP_A                                          \
-    "s_add_u32 s55, s40, s46\n\t"                                                                 \
-    "s_and_b32 s50, s58, 63\n\t" MCS_FL_SWEEP_B                                                  \
-    "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfl_lzero_%=\n\t" MCS_FL_DECIDE_L MCS_FL_TAIL("L", MCS_FL_BACK_L)          \
-    "mcsfl_lzero_%=:\n\t"                                                                         \
-    "s_mov_b32 m0, s47\n\t"                                                                       \
-    "s_mov_b32 s54, s58\n\t"                                                                      \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
-    "s_branch mcsfl_pickL_%=\n"                                                                   \
-    /* ---- F pass: W16R's fit test of the job, with the next one's ---- */                      \
-    "mcsfl_innerF_%=:\n\t"                                                                        \
-    "s_cmp_gt_u32 s45, s40\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FL_FIT2                                             \
-    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
-    "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    "s_cmp_eq_u32 s46, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_zero_%=\n\t" MCS_FL_DECIDE_F MCS_FL_TAIL("F", MCS_FL_BACK_F)           \
-    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16R                                                        \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
-    "s_branch mcsfl_pickF_%=\n"                                                                   \
-    /* a pass whose next job fits no node (before the commit, so none after it either) */        \
-    "mcsfl_nopick_%=:\n\t" MCS_FL_INSPICK_S                                                       \
-    "s_add_u32 s47, s47, 1\n\t" MCS_FL_REC                                                        \
-    "s_branch mcsfa_loopend_%=\n"                                                                 \
-    /* the cursor reached the pass bound: a placed WaitQueue head sleeps 1 s (:250), or the */    \
-    /* batch ends */                                                                              \
-    "mcsfl_pend_%=:\n\t"                                                                          \
-    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
-    "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t"                                                                  \
-    "s_mov_b32 s43, 0\n\t"                                                                        \
-    "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_branch mcsfa_adv_%=\n"                                                                     \
-                                                                                                  \
-    "mcsfa_arrive_%=:\n\t"                                                                        \
-    "s_mov_b32 s40, s45\n\t"                                                                      \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_branch mcsfa_adv_%=\n"                                                                     \
-                                                                                                  \
-    "mcsfa_nofit_%=:\n\t"                                                                         \
-    "s_sub_u32 s76, 1, s43\n\t"                                                                   \
-    "s_add_u32 s82, s82, s76\n\t"                                                                 \
-    "s_mov_b32 s43, 1\n\t"                                                                        \
-    "s_add_u32 s41, s47, 1\n\t"                                                                   \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_add_u32 s78, s78, 1\n\t"                                                                   \
-    "s_cmp_gt_u32 s78, s79\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
-    "s_cmp_eq_u32 s77, -1\n\t"                                                                    \
-    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
-    "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_max_u32 s40, s40, s77\n"                                                                   \
-    "mcsfa_adv_%=:\n\t"                                                                           \
-    "s_cmp_lt_u32 s40, s77\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_loopend_%=\n\t"                                                         \
-    MCS_FA_CNTR_##D                                                                               \
-    "s_max_u32 s81, s81, s80\n\t"                                                                 \
-    "s_mov_b32 s58, s59\n\t" /* a release: the lookahead is void */                               \
-    "s_add_u32 s74, s40, 1\n\t" MCS_FL_SCAN                                                      \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfl_innerF_%=\n\t"                                                          \
-    "s_branch mcsfl_pend_%=\n" MCS_FA_RBODY16R                                                    \
-                                                                                                  \
-    "mcsfa_deadlock_%=:\n\t"                                                                      \
-    "s_or_b32 s44, s44, %[fdl]\n\t"                                                               \
-    "s_branch mcsfa_exit_%=\n"                                                                    \
-    "mcsfa_clkovf_%=:\n\t"                                                                        \
-    "s_mov_b32 s40, -1\n\t"                                                                       \
-    "s_or_b32 s44, s44, %[fck]\n\t"                                                               \
-    "s_branch mcsfa_exit_%=\n"                                                                    \
-    "mcsfa_poolovf_%=:\n\t"                                                                       \
-    "s_or_b32 s44, s44, %[fov]\n\t"                                                               \
-    "s_branch mcsfa_exit_%=\n"                                                                    \
-                                                                                                  \
-    "mcsfa_bend_%=:\n\t"                                                                          \
-    "s_max_u32 s81, s81, s80\n\t"                                                                 \
-    "s_cmp_gt_u32 s81, 64*8\n\t"                                                                  \
-    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
-    "s_add_u32 s76, s57, s47\n\t"                                                                 \
-    "s_cmp_ge_u32 s76, s42\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_exit_%=\n\t"                                                            \
-    "s_waitcnt vmcnt(0)\n\t"                                                                      \
-    "v_add_u32 v125, s57, v110\n\t"                                                               \
-    "v_lshlrev_b32 v125, 2, v125\n\t" MCS_FA_NODEIDX                                              \
-    "global_store_dword v125, v126, s[66:67] nt\n\t"                                              \
-    "global_store_dword v125, v92, s[68:69] nt\n\t"                                               \
-    "v_add_u32 v93, v92, v95\n\t"                                                                 \
-    "global_store_dword v125, v93, s[70:71] nt\n\t"                                               \
-    "s_add_u32 s57, s57, 64\n\t" MCS_FA_PRIO("mcsfa_") MCS_FA_TAKE16                              \
-    "v_add_u32 v121, s57, v110\n\t"                                                               \
-    "v_lshlrev_b32 v121, 4, v121\n\t"                                                             \
-    "v_add_u32 v121, 0x400, v121\n\t"                                                             \
-    "global_load_dwordx4 v[98:101], v121, s[64:65]\n\t"                                           \
-    "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t"                                                                  \
-    "s_mov_b32 s47, 0\n\t"                                                                        \
-    "s_mov_b32 s58, s59\n\t" /* new records: the lookahead is void */                            \
-    MCS_FL_REC                                                                                    \
-    "s_branch mcsfl_innerF_%=\n"
-#define MCS_FL_LOOP(D) MCS_FL_ENTRY MCS_FL_BODY(D) MCS_FA_EXIT_S(16R)
-// the lookahead loop's clobbers: W16R's plus its own (no probe build of this form: MCS_STAMPS uses
-// s92-s99 for its segment clocks)
-#define MCS_FL_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98"
 
 // ---- the loop with the job stream synthesised in the kernel (mcs_gen_params.fused) ---------------
 // The statement runs one batch of records and ends at its batch end with s59 = 1 (or at the end of
@@ -667,20 +384,18 @@ __device__ __forceinline__ void fa_finish(const FifoArgs& a, uint32_t ci, uint32
 // (NPL nodes per lane, P slot rows: 4/8 for 129-256 node clusters, 1/2 for at most 64 nodes)
 // (DIAG: count the passes without a decision and the release scans into mcs_cluster_stats; the
 // production launches skip them, 1.6 % of the C4 loop)
-// (LOOK: the W16L lookahead loop, W16R's shape only)
-// (the streamed W16R loop, W16Q: LDS holds the node words alone, [64] lanes x [4] chunks, one 16-byte
+// (the streamed W16R loop, W16C: LDS holds the node words alone, [64] lanes x [4] chunks, one 16-byte
 // word per lane; its kx is the node index)
-template <int W, bool RS, int NPL, int P, bool DIAG, bool LOOK = false>
+template <int W, bool RS, int NPL, int P, bool DIAG>
 __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     static_assert(W == 16 || !RS, "register slots: 16-bit node format only");
-    static_assert(!LOOK || (W == 16 && RS && NPL == 4 && P == 8), "lookahead: the W16R shape");
     static_assert((NPL == 4 && P == 8) || (NPL == 1 && P == 2 && W == 16 && RS), "loop shapes");
     const uint32_t item = blockIdx.x;
     const uint32_t ci = a.cluster_list ? a.cluster_list[item] : item;
     const uint32_t lane = threadIdx.x;
 
-    constexpr bool QF = W == 16 && RS && NPL == 4 && !LOOK;  // the W16Q macro set
-    __shared__ alignas(QF ? 16 : 8) uint64_t lds[QF ? NPL * kWave / 2 : NPL * kWave + 2 * P * kWave];
+    constexpr bool CAL = W == 16 && RS && NPL == 4;  // W16C: calendar slot rows, 16-byte node words
+    __shared__ alignas(CAL ? 16 : 8) uint64_t lds[CAL ? NPL * kWave / 2 : NPL * kWave + 2 * P * kWave];
 
     constexpr uint32_t kGuard = W == 32 ? 0x80000000u : 0x8000u;
     constexpr uint32_t kClamp = kGuard - 1u;  // request clamp and padding value
@@ -698,7 +413,7 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
         if constexpr (W == 32)
             lds[c * kWave + lane] = (uint64_t)v.x | ((uint64_t)v.y << 32);
         else
-            reinterpret_cast<uint32_t*>(lds)[QF ? node : c * kWave + lane] = v.x | (v.y << 16);
+            reinterpret_cast<uint32_t*>(lds)[CAL ? node : c * kWave + lane] = v.x | (v.y << 16);
     }
     if constexpr (!RS) {
         uint64_t* const pay_nf = lds + NPL * kWave + P * kWave;
@@ -720,8 +435,8 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     __syncthreads();  // (one wave: orders the LDS initialisation before the node reads in the asm)
 
     const uint32_t base = lds_addr(lds);
-    const uint32_t v_pay = QF ? 0u : base + 2048u + lane * 8u;  // (W16Q: no LDS slot rows)
-    const uint32_t v_nb = base + lane * (QF ? 16u : W / 4u);
+    const uint32_t v_pay = CAL ? 0u : base + 2048u + lane * 8u;  // (W16C: no LDS slot rows)
+    const uint32_t v_nb = base + lane * (CAL ? 16u : W / 4u);
     const uint32_t v_nbase = base;
     // perm selectors: W32 gathers chunk pairs 0/1 and 2/3, W16 all four chunks at once
     const uint32_t sel0 = W == 32 ? 0x0c0c0b09u : NPL == 1 ? 0x7fffu : 0x0b0a0908u;
@@ -729,8 +444,8 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
 
     uint32_t t = 0, r = 0, flags = 0, have_w = 0;
     // free slot rows of the lane (W16 forms: plus the sentinel bit 8, so the lowest free row of a
-    // full lane reads as 8, a register index still in range; the streamed W16R loop sets its own,
-    // MCS_FA_INIT16Q)
+    // full lane reads as 8, a register index still in range; the streamed W16R loop keeps its free
+    // lanes in SGPRs and does not use it, MCS_FA_INIT16C)
     uint32_t frm = (1u << P) - 1u + (W == 16 ? 0x100u : 0u), lmin = kEmpty;
     uint32_t used = 0, peak = 0, waited = 0, n_slow = 0, n_rel = 0;
     uint32_t on = 0, os = 0, of = 0;
@@ -751,32 +466,22 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
       [sel1] "s"(sel1), [fdl] "i"(MCS_FLAG_DEADLOCK), [fck] "i"(MCS_FLAG_CLOCK_OVERFLOW),        \
       [fov] "i"(MCS_FLAG_OVERFLOW)
 #define MCS_FA_OPERANDS MCS_FA_OPERANDS_IO : MCS_FA_CLOBBERS
-#define MCS_FL_OPERANDS MCS_FA_OPERANDS_IO : MCS_FL_CLOBBERS
 #define MCS_FC_OPERANDS MCS_FA_OPERANDS_IO : MCS_FC_CLOBBERS
-    if constexpr (LOOK) {
-#ifndef MCS_STAMPS
-        if constexpr (DIAG) asm volatile(MCS_FL_LOOP(D1) MCS_FL_OPERANDS);
-        else asm volatile(MCS_FL_LOOP(D0) MCS_FL_OPERANDS);
-#endif
-    } else if constexpr (W == 32)
+    if constexpr (W == 32)
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(32, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(32, D0) MCS_FA_OPERANDS);
     else if constexpr (NPL == 1)
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16S, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16S, D0) MCS_FA_OPERANDS);
-    else if constexpr (RS)  // (the streamed W16R loop keeps calendar slot rows: W16C)
-#ifdef MCS_STAMPS
-        if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16Q, D1) MCS_FA_OPERANDS);
-        else asm volatile(MCS_FA_LOOP(16Q, D0) MCS_FA_OPERANDS);
-#else
+    else if constexpr (RS) {  // the streamed W16R loop keeps calendar slot rows (W16C; no probe build)
+#ifndef MCS_STAMPS
         if constexpr (DIAG) asm volatile(MCS_FC_LOOP(D1) MCS_FC_OPERANDS);
         else asm volatile(MCS_FC_LOOP(D0) MCS_FC_OPERANDS);
 #endif
-    else
+    } else
         if constexpr (DIAG) asm volatile(MCS_FA_LOOP(16, D1) MCS_FA_OPERANDS);
         else asm volatile(MCS_FA_LOOP(16, D0) MCS_FA_OPERANDS);
 #undef MCS_FA_OPERANDS
-#undef MCS_FL_OPERANDS
 #undef MCS_FC_OPERANDS
 #undef MCS_FA_OPERANDS_IO
 #pragma clang diagnostic pop
@@ -789,12 +494,12 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
         atomicAdd(&g_fa_stamps[3], (unsigned long long)st3);
     }
 #endif
-    // W16Q marks a zero-duration job by the arrival 0xffffffff, which is only safe while the clock
+    // W16C marks a zero-duration job by the arrival 0xffffffff, which is only safe while the clock
     // stays below it (the host's bound): a clock that got there anyway hands the cluster to the
     // compiled kernel, like a pool overflow
-    if constexpr (QF)
+    if constexpr (CAL)
         if (t == 0xffffffffu) flags |= MCS_FLAG_OVERFLOW;
-    fa_finish<NPL, P, QF>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
+    fa_finish<NPL, P, CAL>(a, ci, lane, J, t, r, flags, waited, peak, n_slow, n_rel, on, os, of, o_node, o_start, o_finish);
 }
 
 typedef uint32_t mcs_u32x8 __attribute__((ext_vector_type(8)));
@@ -914,12 +619,11 @@ FifoForm fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor) {
     // register slots: one LDS round trip per release instead of 2 + rows; measured faster than LDS
     // slots at every occupancy from 1 to 16 cluster waves per CU
     if ((a.guard_ok & 2u) && want != 32) {
-        if (want == 16) return kFormW16;
-        // the one-job lookahead loop (W16L) for grids of at most kLookMaxItems clusters (one cluster
-        // wave per SIMD and fewer); MCS_FIFO_LOOK=0|1 forces either
-        const char* look = getenv("MCS_FIFO_LOOK");
-        const bool l = look ? atoi(look) != 0 : a.n_items <= kLookMaxItems;
-        return l ? kFormW16L : kFormW16R;
+#ifdef MCS_STAMPS
+        return kFormW16;  // the streamed W16R loop carries no segment clocks (MCS_FC_LOOP)
+#else
+        return want == 16 ? kFormW16 : kFormW16R;
+#endif
     }
     return (a.guard_ok & 1u) ? kFormW32 : kFormCompiled;
 }
@@ -934,9 +638,8 @@ static hipError_t launch_form(const FifoArgs& a, FifoForm form, hipStream_t s) {
         case kFormW16SFused: hipLaunchKernelGGL((fifo_asm_fused_kernel<1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
         case kFormW16RFused: hipLaunchKernelGGL((fifo_asm_fused_kernel<4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
         case kFormW16S: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 1, 2, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
-        case kFormW16R: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
 #ifndef MCS_STAMPS
-        case kFormW16L: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG, true>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
+        case kFormW16R: hipLaunchKernelGGL((fifo_asm_kernel<16, true, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
 #endif
         case kFormW16: hipLaunchKernelGGL((fifo_asm_kernel<16, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
         case kFormW32: hipLaunchKernelGGL((fifo_asm_kernel<32, false, 4, 8, DIAG>), dim3(a.n_items), dim3(kWave), 0, s, a); break;
@@ -952,7 +655,6 @@ const char* fifo_form_name(FifoForm form) {
         case kFormW16RFused: return "mcs::fifo_asm_fused_kernel<4, 8>";
         case kFormW16S: return "mcs::fifo_asm_kernel<16, true, 1, 2>";
         case kFormW16R: return "mcs::fifo_asm_kernel<16, true, 4, 8>";
-        case kFormW16L: return "mcs::fifo_asm_kernel<16, true, 4, 8, look>";
         case kFormW16: return "mcs::fifo_asm_kernel<16, false, 4, 8>";
         case kFormW32: return "mcs::fifo_asm_kernel<32, false, 4, 8>";
         case kFormCompiled: break;

@@ -18,8 +18,6 @@ constexpr int kWave = 64;
 constexpr int kMaxNpl = 16;   // nodes per lane -> at most 1024 nodes per cluster in ABI v1
 constexpr int kMaxPool = 32;  // running-slot registers per lane -> 2048 slots per cluster
 constexpr uint32_t kAsmMaxJobs = (1u << 28) - 128u;  // hand-scheduled loop: 32-bit record offsets
-// the W16L lookahead loop: picked for grids of at most this many clusters (0: only MCS_FIFO_LOOK=1)
-constexpr uint32_t kLookMaxItems = 0u;
 constexpr uint32_t kJobPad = 128;  // records of slack after the job array (unmasked batch loads)
 
 struct Totals {  // device-side accumulation of mcs_stats (only clusters that did not overflow)
@@ -188,7 +186,8 @@ bool fifo_variant_exists(int npl, int pool);
 // the hand-scheduled decision loop (mcs_fifo_asm.hip): NPL 4 / P 8 or NPL 1 / P 2, streamed
 // batch runs; MCS_FIFO_ASM=0 turns it off
 bool fifo_asm_eligible(const FifoArgs& a, int npl, int pool, bool hor);
-// the kernel a FIFO batch run takes (the numbers are the form codes of DESIGN.md and profiles/)
+// the kernel a FIFO batch run takes (the numbers are the form codes of DESIGN.md and profiles/; 21,
+// the duo loop, and 22, the one-job lookahead, are retired)
 enum FifoForm : int {
     kFormCompiled = 0,    // fifo_kernel (mcs_kernels.hip)
     kFormW16 = 16,        // 16-bit node format, running slots in LDS (MCS_FIFO_ASM=16 only)
@@ -196,7 +195,6 @@ enum FifoForm : int {
     kFormW16S = 18,       // W16R for clusters of at most 64 nodes: NPL 1 / P 2
     kFormW16RFused = 19,  // W16R / W16S on a fused job stream
     kFormW16SFused = 20,
-    kFormW16L = 22,       // W16R with a one-job lookahead (MCS_FIFO_LOOK=1 only)
     kFormW32 = 32,        // 32-bit node format, running slots in LDS
 };
 FifoForm fifo_asm_form(const FifoArgs& a, int npl, int pool, bool hor);

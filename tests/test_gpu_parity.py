@@ -18,21 +18,11 @@ pytestmark = pytest.mark.gpu
 KATS = load_kats()
 
 
-
+# the kernel the engine picks for a streamed 129-256-node launch in the 16-bit format.  (Three tests
+# below had a "form" parameter that chose between this loop and the removed one-job lookahead; their
+# cases keep the ids they had with form "0", so the suite's records of them stay comparable.)
 W16R = "mcs::fifo_asm_kernel<16, true, 4, 8>"
-LOOK = "mcs::fifo_asm_kernel<16, true, 4, 8, look>"
 
-
-def w16r_form(n_clusters):
-    """The kernel the engine picks for a streamed 129-256-node launch of n_clusters in the 16-bit
-    format: W16R, or the one-job lookahead loop W16L under MCS_FIFO_LOOK=1 (no grid picks it by
-    default: kLookMaxItems = 0)."""
-    return LOOK if os.environ.get("MCS_FIFO_LOOK") == "1" else W16R
-
-
-def set_form(monkeypatch, form):
-    """form: "0" W16R, "look" the lookahead loop (the parametrisations below)."""
-    monkeypatch.setenv("MCS_FIFO_LOOK", "1" if form == "look" else "0")
 
 def run_engine(eng, arrays, streams):
     eng.load_clusters(arrays)
@@ -162,24 +152,21 @@ def test_config3_small_replicas(engine):
     assert_parity(arrays, streams, node, start, fin, cs)
 
 
-@pytest.mark.parametrize("form", ["0", "look"])
-@pytest.mark.parametrize("kind", ["n256", "n256_hot"])
-def test_config4_shape_reduced(engine, kind, form, monkeypatch):
-    """BASELINE config 4 shape (256 nodes, scaled arrivals) at 128 clusters x 6k jobs (W16R and the
-    lookahead loop)."""
-    set_form(monkeypatch, form)
+@pytest.mark.parametrize("kind", ["n256", "n256_hot"], ids=["n256-0", "n256_hot-0"])  # (ids: see W16R)
+def test_config4_shape_reduced(engine, kind):
+    """BASELINE config 4 shape (256 nodes, scaled arrivals) at 128 clusters x 6k jobs (W16R)."""
     arrays, streams, _ = seeded_workload(kind, 128, 6000)
     node, start, fin, st, cs = run_engine(engine, arrays, streams)
-    assert engine.last_kernel == w16r_form(128)
+    assert engine.last_kernel == W16R
     assert_parity(arrays, streams, node, start, fin, cs)
 
 
-def test_config4_strong_shard_512_lookahead(monkeypatch):
-    """The strong shard an 8-GPU node runs (512 of C4's 4096 clusters, full streams) through the
-    lookahead loop: every cluster bit-exact against the oracle."""
+def test_config4_strong_shard_512():
+    """The strong shard an 8-GPU node runs (512 of C4's 4096 clusters, full streams: two cluster waves
+    per CU, a lone wave per SIMD) through the loop the engine picks for it, W16R: every cluster
+    bit-exact against the oracle."""
     from mcs_amd.engine import scaled_lambda
 
-    monkeypatch.setenv("MCS_FIFO_LOOK", "1")
     n, J = 512, 16384
     arrays = replicate(uniform_cluster(256), n)
     gp = GenParams(seed=0x4D43535F53494D31, arrival_mode=1, lam=scaled_lambda(256, load=0.9))
@@ -188,7 +175,7 @@ def test_config4_strong_shard_512_lookahead(monkeypatch):
         eng.set_shard(3, 8)  # rank 3 of 8: global clusters 1536..2047
         eng.generate_jobs(gp, J)
         st = eng.run()
-        assert eng.last_kernel == LOOK
+        assert eng.last_kernel == W16R
         assert st.placed == n * J
         node, start, fin = eng.placements()
         jobs = eng.read_jobs()
@@ -309,9 +296,8 @@ def test_heterogeneous_cluster_sizes(engine):
 
 
 @pytest.mark.parametrize("sizes", [[0, 1, 5, 63, 64, 65, 130, 200, 256], [0, 1, 2, 5, 33, 63, 64]],
-                         ids=["asm_4x8", "asm_1x2"])
-@pytest.mark.parametrize("form", ["0", "look"])
-def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, form, monkeypatch):
+                         ids=["0-asm_4x8", "0-asm_1x2"])  # (ids: see W16R)
+def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes):
     """Clusters of many sizes in one launch of each hand-scheduled loop shape (the largest picks it:
     129-256 nodes -> 4 chunks x 8 slot rows, <= 64 nodes -> 1 chunk x 2 rows): padding nodes, an
     empty cluster (its first job deadlocks), partial JSON availability, zero-duration jobs."""
@@ -334,22 +320,20 @@ def test_heterogeneous_cluster_sizes_hand_scheduled(engine, sizes, form, monkeyp
     arrays = pack_clusters(clusters)
     off = np.arange(len(parts) + 1, dtype=np.uint64) * J
     s = JobStreams(*(np.concatenate([p[f] for p in parts]) for f in range(4)), off)
-    set_form(monkeypatch, form)
     node, start, fin, st, cs = run_engine(engine, arrays, s)
     if max(sizes) > 64:
-        assert engine.last_kernel == w16r_form(len(sizes))
+        assert engine.last_kernel == W16R
     else:
         assert engine.last_kernel == "mcs::fifo_asm_kernel<16, true, 1, 2>"
     assert_parity(arrays, s, node, start, fin, cs)
     assert cs[0]["flags"] & L.MCS_FLAG_DEADLOCK  # zero nodes: the first job never fits
 
 
-@pytest.mark.parametrize("nodes,form", [(256, "0"), (256, "look"), (5, "0")])
-def test_hand_scheduled_diag_build(nodes, form, monkeypatch):
+@pytest.mark.parametrize("nodes", [256, 5], ids=["256-0", "5-0"])  # (ids: see W16R)
+def test_hand_scheduled_diag_build(nodes):
     """MCS_FIFO_DIAG=1 launches the counting build of the hand-scheduled loop: the same placements
     and per-cluster results, plus the pass and release-scan counters (which the production build
     leaves at the decision count and 0)."""
-    set_form(monkeypatch, form)
     arrays, streams, _ = seeded_workload("n256" if nodes == 256 else "small", 64, 3000)
     res = {}
     for diag in ("0", "1"):
@@ -357,7 +341,7 @@ def test_hand_scheduled_diag_build(nodes, form, monkeypatch):
         try:
             with Engine(0) as eng:
                 res[diag] = run_engine(eng, arrays, streams)
-                assert eng.last_kernel == (w16r_form(64) if nodes == 256 else "mcs::fifo_asm_kernel<16, true, 1, 2>")
+                assert eng.last_kernel == (W16R if nodes == 256 else "mcs::fifo_asm_kernel<16, true, 1, 2>")
         finally:
             os.environ.pop("MCS_FIFO_DIAG", None)
     for i in range(3):
@@ -370,18 +354,17 @@ def test_hand_scheduled_diag_build(nodes, form, monkeypatch):
     assert_parity(arrays, streams, *res["1"][:3], c1)
 
 
-@pytest.mark.parametrize("shape", ["w16s", "w16r", "look", "w32"])
+@pytest.mark.parametrize("shape", ["w16s", "w16r", "w32"])
 @pytest.mark.parametrize("seed", [1, 2, 3, 4, 5, 6])
-def test_hand_scheduled_fuzz(engine, shape, seed, monkeypatch):
+def test_hand_scheduled_fuzz(engine, shape, seed):
     """Randomised clusters and streams through each hand-scheduled loop form, bit-exact against the
     oracle: node counts across the shape's range (padding lanes and chunks), random JSON
     availability, bursts of simultaneous arrivals, zero-duration and zero-resource jobs, requests
     equal to a node's free value, and one request per cluster that fits no node (a head-of-line
     deadlock at a random point of the stream)."""
-    set_form(monkeypatch, "look" if shape == "look" else "0")
-    arrays, s = fuzz_workload("w16r" if shape == "look" else shape, seed)
+    arrays, s = fuzz_workload(shape, seed)
     node, start, fin, st, cs = run_engine(engine, arrays, s)
-    want = {"w16s": "mcs::fifo_asm_kernel<16, true, 1, 2>", "w16r": W16R, "look": LOOK,
+    want = {"w16s": "mcs::fifo_asm_kernel<16, true, 1, 2>", "w16r": W16R,
             "w32": "mcs::fifo_asm_kernel<32, false, 4, 8>"}[shape]
     if st.escalations == 0:
         assert engine.last_kernel == want
@@ -490,7 +473,7 @@ def test_hand_scheduled_loop_field_bounds(engine, free):
     off = np.arange(len(parts) + 1, dtype=np.uint64) * J
     s = JobStreams(*(np.concatenate([p[f] for p in parts]) for f in range(4)), off)
     node, start, fin, st, cs = run_engine(engine, arrays, s)
-    assert engine.last_kernel == (w16r_form(len(clusters)) if free < 0x7FFF
+    assert engine.last_kernel == (W16R if free < 0x7FFF
                                   else "mcs::fifo_asm_kernel<32, false, 4, 8>")
     assert_parity(arrays, s, node, start, fin, cs)
     assert (cs["flags"] & L.MCS_FLAG_DEADLOCK).all()  # every cluster's last request fits nowhere
@@ -517,16 +500,13 @@ def test_every_kernel_variant(policy):
             # clusters), with LDS slots (MCS_FIFO_ASM=16) and its 32-bit one (=32; =0 turns the loop
             # off), and the compiled kernel's two (the low-occupancy one is picked for small grids;
             # MCS_FIFO_LAT forces either)
-            # (and the lookahead loop, MCS_FIFO_LOOK=1, the register-slot form's W16L variant)
-            for fused, lat, asm, form in ((False, "1", "0", None), (False, "0", "0", None), (False, None, "1", "0"),
-                                         (False, None, "1", "look"),
-                                         (False, None, "16", None), (False, None, "32", None),
-                                         (True, None, None, None)):
+            for fused, lat, asm in ((False, "1", "0"), (False, "0", "0"), (False, None, "1"),
+                                   (False, None, "16"), (False, None, "32"), (True, None, None)):
                 if policy == "DELAY" and lat == "0":
                     continue
                 if policy == "DELAY" and asm in ("1", "16", "32"):
                     continue
-                env = {"MCS_FIFO_LAT": lat, "MCS_FIFO_ASM": asm, "MCS_FIFO_LOOK": "1" if form == "look" else None}
+                env = {"MCS_FIFO_LAT": lat, "MCS_FIFO_ASM": asm}
                 old = {k: os.environ.get(k) for k in env}
                 for k, v in env.items():
                     if v is not None:
@@ -544,7 +524,7 @@ def test_every_kernel_variant(policy):
                             os.environ.pop(k, None)
                         else:
                             os.environ[k] = v
-                tag = f"nodes {nn} pool {pool} fused {fused} lat {lat} asm {asm} form {form}"
+                tag = f"nodes {nn} pool {pool} fused {fused} lat {lat} asm {asm}"
                 np.testing.assert_array_equal(node, oracle[0], err_msg=tag)
                 np.testing.assert_array_equal(start, oracle[1], err_msg=tag)
                 np.testing.assert_array_equal(fin, oracle[2], err_msg=tag)

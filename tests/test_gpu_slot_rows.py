@@ -1,5 +1,7 @@
-"""The streamed W16R loop's running-slot rows: an insert takes a lane of the
-current row from a scalar mask and re-picks a row when the mask runs out.  Which slot a job gets
+"""The streamed W16R loop's running-slot rows: written for the loop before calendar
+rows, whose insert took a lane of the current row from a scalar mask and re-picked a row when the
+mask ran out; the calendar loop takes a lane of row finish & 7 and spills to the next row with a free
+lane, and the same streams fill and cycle its rows.  Which slot a job gets
 never shows in a result, so each case is a plain parity run against the oracle (node, start, finish
 and the per-cluster statistics, bit-exact) on a stream that drives the pool through the paths of the
 re-pick: rows cycling with the pool near full, the pool exactly full and then a release, and

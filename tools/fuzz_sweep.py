@@ -21,43 +21,12 @@ import test_gpu_trade as TT  # noqa: E402
 from mcs_amd import Engine  # noqa: E402
 
 
-
-class _MonkeyPatch:
-    """The part of pytest's monkeypatch fixture the fuzz tests use (environment variables)."""
-
-    def __init__(self):
-        self.saved = {}
-
-    def setenv(self, k, v):
-        self.saved.setdefault(k, os.environ.get(k))
-        os.environ[k] = v
-
-    def delenv(self, k, raising=True):
-        self.saved.setdefault(k, os.environ.get(k))
-        os.environ.pop(k, None)
-
-    def undo(self):
-        for k, v in self.saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def fifo_fuzz(eng, shape, seed):
-    mp = _MonkeyPatch()
-    try:
-        TP.test_hand_scheduled_fuzz(eng, shape, seed, mp)
-    finally:
-        mp.undo()
-
-
 base, count = int(sys.argv[1]), int(sys.argv[2])
 fails, runs = [], 0
 t0 = time.time()
 with Engine(0) as eng, Engine(0, policy="DELAY") as deng:
     for seed in range(base, base + count):
-        cases = [(f"fifo/{s}", lambda s=s: fifo_fuzz(eng, s, seed)) for s in ("w16s", "w16r", "look", "w32")]
+        cases = [(f"fifo/{s}", lambda s=s: TP.test_hand_scheduled_fuzz(eng, s, seed)) for s in ("w16s", "w16r", "w32")]
         cases += [(f"delay/{s}", lambda s=s: TD.test_gpu_delay_fuzz(deng, s, seed)) for s in ("w16s", "mid", "w16r", "w32")]
         cases += [(f"fused/{p}", lambda p=p: TF.test_fused_fuzz(p, seed)) for p in ("FIFO", "DELAY")]
         cases += [(f"online/{p}/{s}", lambda p=p, s=s: TO.test_online_fuzz_slices_equal_batch_and_oracle(p, s, seed))

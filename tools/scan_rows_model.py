@@ -1,5 +1,6 @@
 """Which slot rows expire in a release scan of the streamed W16R loop (W16Q), from the
 oracle's placements of the C4 stream, and what testing the rows in pairs would issue.
+(The loop modelled here, W16Q, was removed once calendar rows replaced it; its last tree is e98c6d7.)
 
 The loop's control flow is replayed from the oracle's start and finish seconds: the clock moves to a
 head's arrival, from a failed fit to max(t + 1, the earliest finish) until the head's start second,

@@ -1,5 +1,6 @@
 """How often the row-wise slot insert of the streamed W16R loop (W16Q) has to re-pick a
 row, from the oracle's placements of the C4 stream (256 nodes, scaled arrivals at 90 % load).
+(The loop modelled here, W16Q, was removed once calendar rows replaced it; its last tree is e98c6d7.)
 
 The model is the kernel's policy on its 64 lanes x 8 rows of running slots: a current row R and the
 set CUR of lanes whose row R is free and not yet handed out; an insert takes CUR's lowest lane; a

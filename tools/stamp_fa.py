@@ -3,6 +3,9 @@ mcs_fifo_asm.hip (tools/variant.sh stamps csrc/mcs_fifo_asm.hip -DMCS_STAMPS): p
 the cycles spent in release scans, failed fits, batch ends and the rest (decisions and arrival
 advances), at several cluster counts (waves per CU), with the counting build's pass / release counts.
 s_memtime stamps wait for their SMEM read, which also drains LDS: read the shares, not the time.
+The forms that carry stamps are W32, W16, W16S and the fused W16R / W16S loops.  The streamed W16R loop
+has none, because its FREE rows occupy s92-s101, where the stamps live: a probe build does not contain it
+and runs the 129-256 node shape measured here on W16 (LDS slots).  Each line names the kernel it measured.
 usage: python tools/stamp_fa.py variants/libmcs_stamps.so [clusters ...]"""
 import json
 import os
