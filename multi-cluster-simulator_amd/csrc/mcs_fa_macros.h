@@ -13,6 +13,9 @@
 //  VALU writes VGPR -> DPP reads it                  2     every DPP min/max chain (SCANEND,   s_nop 1 between the steps; before
 //                                                          W16C's MCS_FC_WMIN, the DELAY       the first: s_nop 1, or (DELAY rel)
 //                                                          filter)                             s_mov s96 + s_nop 0
+//                                                          W16C's shifted record columns       v94's write, three v_mov and s_nop 1
+//                                                          (MCS_FC_SHIFT: v_mov_b32_dpp        before the first; v95 / v96 are
+//                                                          wave_shl:1 of v94, v95, v96)        written earlier still
 //  SDWA / op_sel write preserving the other word     1     MCS_FA_FIT16: v80/v81 (WORD_1,      v_cmp_lt s[60:61] + v_ffbl v117
 //    -> VALU reads that VGPR (DstSelForwarding)            UNUSED_PRESERVE) -> v_perm          between (found by measurement,
 //                                                                                              tools/asm_debug.py); MCS_FA_FIT16C:
@@ -21,22 +24,30 @@
 //                                                                                              W16C's release tail (the same
 //                                                                                              pair): s_cmp_le_u32 between
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
-//    uses it as the lane select                            written                             from s_add/s_mov)
+//    uses it as the lane select                            written                             from s_add/s_mov; the placed head's
+//                                                                                              restore reads s45 from v_readlane
+//                                                                                              as DATA of v_writelane: s_nop 3)
 //  SALU writes M0 -> v_writelane with an M0 lane     1*    result writes at a Level0 decision  >= 1 other instruction between
 //    select (*not in the ISA table; kept anyway)           (HEAD, ZEROKX)                      (s_add s80 / s_ff1, s_lshl3_add)
 //                                                          DELAY G list (MCS_FD_ENUM: m0 =     s_add s86 between
 //                                                          cursor -> v_writelane v113/v118)
+//                                                          W16C's record read (MCS_FC_RECNEXT: s_add s80 + two v_writelane between;
+//                                                          v_readlane with m0 the lane select)  after mcsfa_zero: the same two
 //  VALU writes VGPR -> v_readlane / v_readfirstlane  1     DECIDE16R / DECIDE16C / ZEROKX      >= 3 instructions between every
 //    reads it (gfx950)                                     read v86, v117; REC16 after TAKE16; pair; SCANEND, WMIN: s_nop 1;
 //                                                          SCANEND, MCS_FC_WMIN v120;          v87: a batch's passes apart
 //                                                          MCS_FC_ZROUTE v87 (written at the
 //                                                          batch's TAKE16C)
+//                                                          W16C's v89 / v90 / v107 (written    s_mov s47 + three v_readlane after
+//                                                          per batch, MCS_FC_SHIFT; v89 also   the batch's; >= 8 instructions after
+//                                                          by the mark and its restore)        the mark or the restore
 //                                                          DELAY G pass (r04): v_cndmask v113  >= 6 (GTEST's scalar prologue)
 //                                                          -> GTEST's v_readlane v113; v123
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
 //                                                                                              s_cmp)
-//  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch             (interlocked on gfx9; SALU
-//                                                                                              instructions between anyway)
+//  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch; W16C's    (interlocked on gfx9; the pass's
+//                                                          row compare (v_cmp vcc, then        head and the row compare branch
+//                                                          s_cbranch_vccz, copies and scan)    right after the v_cmp)
 //  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16C's row
 //                                                                                              blocks: s_mov_b64 exec)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
@@ -54,11 +65,13 @@
 //  s_set_gpr_idx_on / _idx overwrite M0            -     W16C's insert                       both relative moves come before the
 //                                                                                              region; m0 = the cursor is set
 //                                                                                              after it, as in every form
-//  VALU writes SGPR -> SALU reads it               0     W16C's row blocks and full scan      (interlocked: v_cmp s[50:51] ->
-//                                                          (s_cmp_lg_u64 right after v_cmp)    s_cmp / s_mov exec)
-//  s_setpc_b64 to a computed address               -     W16C's mcsfa_adv1                    the eight row blocks are 64 bytes
-//                                                                                              apart from a 512-byte line, so
-//                                                                                              s74 | 64 * (t & 7) never carries
+//  VALU writes SGPR -> SALU reads it               0     W16C's row compares (vcc -> s_mov   (interlocked)
+//                                                          exec / s_bcnt1 / s_or), the record
+//                                                          read's s45 -> s_cmp
+//  s_setpc_b64 to a computed address               -     W16C's MCS_FC_RET                    the table of branches starts on a
+//                                                                                              256-byte line and is 224 bytes, so
+//                                                                                              s74 + 32 * entry + 4 * (t & 7) never
+//                                                                                              carries into s59
 // A reorder that moves a consumer next to its producer in the table must add the s_nop.
 
 // progress-based wave priority at each batch end: the fewer of its jobs a wave has decided, the higher
@@ -507,17 +520,21 @@
 // instructions only (no v_cmp / v_ffbl / v_readlane of a free-row column, and the fit test carries none).
 //   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), read and written by the
 //             insert with s_movrels/s_movreld (m0 = 2r), by a release as static registers
-//   s77 XMIN   s74, s59 the address of row block 0 (512-byte aligned, 64 bytes per block), low and
-//   high word   s[58:59] the block's address (s58 = s74 | 64 * (t & 7))   s[60:61] the insert's FREE[r], s[50:51] without the lane handed
-//   out   s49 r / 64 * (t & 7) / the full scan's released count   s79 the node address of the insert; the seconds left of a failed fit's stepping
+//   s77 XMIN   s74, s59 the address of the copies' table of branches (MCS_FC_RET; on a 256-byte line),
+//   low and high word   s[58:59] a computed jump's target   s[60:61] the insert's FREE[r], s[50:51] without
+//   the lane handed out   s49 r / a computed jump's t & 7 / the full scan's released count   s79 the node
+//   address of the insert; the seconds left of a failed fit's stepping   s41 min(64, J - cb), read where a
+//   batch is taken only   v89, v90, v107 the record columns shifted by one lane (MCS_FC_SHIFT)   m0 after a
+//   placement: the lane of the job placed, the record read's lane select
 //   s78 the failed fits left of the runaway bound   s82 the WaitQueue heads placed (a head waiting at
 //   the exit is s43)   v87 the batch's true arrival column (v94 holds 0xffffffff for its zero-duration
-//   jobs)   v89 and v90 are not used (v90: the exact-minimum fallback's temporary), nor is s75
+//   jobs; both 0xffffffff in the lanes past the stream's end)   s75 is not used
 // The clock moves in three ways.  By one second (the placed WaitQueue head, each step of a failed fit's
 // sleep) or to a second nothing can finish before (an arrival one second on, the exact-minimum
-// fallback): mcsfa_adv1, the XMIN test and a computed jump into the row's block (MCS_FC_BLOCK), which
-// compares the row and either leaves at once (mcsfa_norel: no LDS traffic) or releases it and goes to
-// the tail (mcsfa_reltail: node reload, the head's fit test, and into the pass at mcsfa_fitted).  By more
+// fallback): the XMIN test and the row block of the copy of that second (MCS_FC_COPY: the next copy's
+// after a one-second advance, through mcsfa_adv1's computed jump otherwise), which compares the row
+// and either leaves at once (mcsfa_norel: no LDS traffic) or releases it and falls into the tail
+// (mcsfa_reltail: node reload, the head's fit test, and into the pass at mcsfa_fitted).  By more
 // than a second (an arrival gap), or with a misplaced slot due (t >= XMIN): mcsfa_full, every row in
 // turn against t, and after one that XMIN asked for, XMIN rebuilt as the minimum over the slots with
 // finish & 7 != row (free slots hold -1 and drop out; a gap's full scan at t < XMIN releases no
@@ -528,7 +545,7 @@
 // Hazards (table above): m0 is written two instructions before s_movrels reads it (one wait state
 // needed) and nothing writes it before s_movreld; s_set_gpr_idx_on / _idx overwrite m0, so both
 // relative moves come before the region, and m0 = the cursor is set after it as in every form; the
-// block's v_cmp writes s[50:51] that only SALU reads (interlocked); the DPP chains keep s_nop 1.
+// row compare writes vcc, which s_cbranch_vccz and SALU read (interlocked); the DPP chains keep s_nop 1.
 //
 // The fit test is MCS_FA_FIT16 without the insert's free-row lanes: the pass's finish (s_add s55) is
 // the instruction between the last SDWA-preserve write and the v_perm (hazard table, row 2).
@@ -565,6 +582,29 @@
     "v_min_u32 v96, 0x7fff, v100\n\t"                                                             \
     "v_min_u32 v97, 0x7fff, v101\n\t"                                                             \
     "v_lshl_or_b32 v96, v97, 16, v96\n\t" MCS_FA_ZMASK16C("v98")
+// The record read after a placement takes the NEXT job's record from the lane of the job just placed
+// (m0), out of copies of the three record columns shifted down by one lane: v89 arrival, v90 duration,
+// v107 request.  The arrival column carries 0xffffffff in every lane without a job (s41 = min(64, J - cb)
+// on, in the last batch), and lane 63 of its shifted copy holds 0xffffffff too: "no next job in this
+// batch" reads as an arrival that never comes, so the pass ends on the arrival test alone and
+// mcsfa_arrive's out-of-line route (MCS_FC_ZROUTE) tells a batch end from a zero-duration job.  Built
+// once per batch (the v_mov of v89 / v90 / v107 are the two wait states the DPP read of v94 needs, the
+// s_nop 1 kept anyway; lane 63 of a wave_shl has no source and keeps the destination's -1).
+#define MCS_FC_SHIFT                                                                              \
+    "v_cmp_le_u32_e32 vcc, s41, v110\n\t"                                                         \
+    "v_cndmask_b32_e32 v94, v94, v111, vcc\n\t" /* (v111 = -1) */                                 \
+    "v_mov_b32 v89, -1\n\t"                                                                       \
+    "v_mov_b32 v90, 0\n\t"                                                                        \
+    "v_mov_b32 v107, 0\n\t"                                                                       \
+    "s_nop 1\n\t"                                                                                 \
+    "v_mov_b32_dpp v89, v94 wave_shl:1 row_mask:0xf bank_mask:0xf\n\t"                            \
+    "v_mov_b32_dpp v90, v95 wave_shl:1 row_mask:0xf bank_mask:0xf\n\t"                            \
+    "v_mov_b32_dpp v107, v96 wave_shl:1 row_mask:0xf bank_mask:0xf\n\t"
+// the next job's record from the lane of the job just placed (m0)
+#define MCS_FC_RECNEXT                                                                            \
+    "v_readlane_b32 s45, v89, m0\n\t"                                                             \
+    "v_readlane_b32 s46, v90, m0\n\t"                                                             \
+    "v_readlane_b32 s48, v107, m0\n\t"
 // The LDS node copy of this form is one 16-byte word per lane, chunk c of lane l at base + 16 * l +
 // 4 * c (v108 = base + 16 * lane, 16-byte aligned): a release refreshes it with one ds_write_b128 of
 // v[64:67] and reloads it with one ds_read_b128.  The decision's kx (s54) is then the node index
@@ -579,24 +619,22 @@
     "s_lshl2_add_u32 s54, s50, s53\n\t"
 #define MCS_FA_POOLMAX16C "64*8"
 #define MCS_FA_NODEIDX16C "v_mov_b32 v126, v91\n\t"
-// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled (the pass
-// bound's end in MCS_FC_PASS: once per waited job, where the shared loop pays a subtract and an add at
+// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled
+// (mcsfa_zarrp in MCS_FC_COPY: once per waited job, where the shared loop pays a subtract and an add at
 // every failed fit); a head still waiting when the loop leaves (deadlock, clock overflow, the runaway
 // guard: s43 = 1 on exactly those exits, 0 on every other) is added at the exit.
 #define MCS_FA_XWAITED16C "s_add_u32 %[waited], s82, s43\n\t"
 // The runaway guard counts s78 down from the bound 4J + 256 and the borrow is its test (the failed fit
 // number 4J + 257 trips it, as the shared loop's s78 > s79); s79 has another use in this form.
 #define MCS_FA_GUARD016C "s_lshl2_add_u32 s78, s42, 0x100\n\t"
-// The loop's head starts 16 bytes into a 64-byte instruction line.  Where the loop lies decides up to
-// 1.8 % of this kernel's time at 4096 clusters and 3.4 % at 512 (the head at each of the eight 4-byte
-// positions of a 32-byte period, profiles/pass_trim/ab_place_*.txt: every edit before or inside the loop
-// used to move it), and the alignment keeps it in place whatever the entry code before it grows or
-// loses.  Of the eight positions this one measured best at 4096 and at 512 clusters, 5.758 and 3.904 ms
-// against 5.869 and 4.048 ms on the line itself and 6.078 and 4.293 ms for the loop before calendar rows;
-// every position beats that loop, profiles/calendar_rows/ab_place_*.txt.  The four s_nop run once, at
-// the entry.
-#define MCS_FA_HEAD16C ".p2align 6\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\t"
+// The entry needs no padding: it reaches the copy of its clock through the table of branches, and each
+// copy places its own head 16 bytes into a 64-byte instruction line (MCS_FC_COPY), the position that
+// measured best of the eight 4-byte positions for the single loop at 4096 and at 512 clusters (where the
+// loop lies decided up to 1.8 % and 3.4 % of its time, profiles/pass_trim/ab_place_*.txt and
+// profiles/calendar_rows/ab_place_*.txt).
+#define MCS_FA_HEAD16C ""
 #define MCS_FA_INIT16C MCS_FA_ZMASK16C("v94") /* (batch 0) */                                     \
+    "s_min_u32 s41, s42, 64\n\t" MCS_FC_SHIFT                                                     \
     "s_mov_b64 s[86:87], -1\n\t"                                                                 \
     "s_mov_b64 s[88:89], -1\n\t"                                                                 \
     "s_mov_b64 s[90:91], -1\n\t"                                                                 \
@@ -607,7 +645,7 @@
     "s_mov_b64 s[100:101], -1\n\t"                                                               \
     "s_getpc_b64 s[58:59]\n"                                                                      \
     "mcsfa_pc_%=:\n\t"                                                                            \
-    "s_add_u32 s74, s58, mcsfa_blk0_%=-mcsfa_pc_%=\n\t"                                           \
+    "s_add_u32 s74, s58, mcsfa_tbl_%=-mcsfa_pc_%=\n\t"                                           \
     "s_addc_u32 s59, s59, 0\n\t"                                                                      \
     "v_mov_b32 v32, -1\n\t"                                                                      \
     "v_mov_b32 v33, -1\n\t"                                                                      \
@@ -620,7 +658,7 @@
 // MCS_FA_DECIDE16R's single register-index region; the slot is the lowest free lane of row
 // r = finish & 7 (s_ff1 of an empty FREE[r] is -1: the shift then gives a bit the AND drops, SCC of
 // the AND = a slot exists; none: the spill, out of line)
-#define MCS_FA_DECIDE16C                                                                          \
+#define MCS_FA_DECIDE16C(k)                                                                       \
     "s_and_b32 s49, s55, 7\n\t"                                                                   \
     "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
     "v_readlane_b32 s51, v86, s50\n\t"                                                            \
@@ -635,7 +673,7 @@
     "s_and_b64 s[62:63], s[62:63], s[60:61]\n\t"                                                  \
     "s_cbranch_scc0 mcsfa_sp_%=\n\t"                                                              \
     "s_movreld_b64 s[86:87], s[50:51]\n" /* the slot is handed out */                            \
-    "mcsfa_ins_%=:\n\t"                                                                           \
+    "mcsfa_ins" #k "_%=:\n\t"                                                                           \
     "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
     "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
     "s_mov_b64 exec, s[62:63]\n\t"                                                                \
@@ -686,38 +724,16 @@
     "v_min_u32_dpp v120, v120, v120 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                  \
     "s_nop 1\n\t"                                                                                 \
     "v_readlane_b32 " DST ", v120, 63\n\t"
-// row p's block of the computed jump (64 bytes apart): the row against t; an expiry refreshes the LDS
-// node copy under the full wave, then hands the payloads back under exec = the expiry mask
-#define MCS_FC_BLOCK(p, F, P, A, FREE)                                                            \
-    ".p2align 6\n"                                                                                \
-    "mcsfa_blk" #p "_%=:\n\t"                                                                     \
-    "v_cmp_ge_u32_e64 s[50:51], s40, " F "\n\t"                                                  \
-    "s_cmp_lg_u64 s[50:51], 0\n\t"                                                                \
-    "s_cbranch_scc0 mcsfa_norel_%=\n\t"                                                           \
-    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
-    "s_mov_b64 exec, s[50:51]\n\t"                                                                \
-    "s_bcnt1_i32_b64 s76, s[50:51]\n\t"                                                          \
-    "ds_add_u32 " A ", " P "\n\t"                                                               \
-    "v_mov_b32 " F ", -1\n\t"                                                                    \
-    "s_or_b64 " FREE ", " FREE ", s[50:51]\n\t"                                                  \
-    "s_branch mcsfa_reltail_%=\n"
-#define MCS_FC_BLOCKS                                                                             \
-    ".p2align 9\n" MCS_FC_BLOCK(0, "v32", "v40", "v48", "s[86:87]")                              \
-    MCS_FC_BLOCK(1, "v33", "v41", "v49", "s[88:89]") MCS_FC_BLOCK(2, "v34", "v42", "v50", "s[90:91]") \
-    MCS_FC_BLOCK(3, "v35", "v43", "v51", "s[92:93]") MCS_FC_BLOCK(4, "v36", "v44", "v52", "s[94:95]") \
-    MCS_FC_BLOCK(5, "v37", "v45", "v53", "s[96:97]") MCS_FC_BLOCK(6, "v38", "v46", "v54", "s[98:99]") \
-    MCS_FC_BLOCK(7, "v39", "v47", "v55", "s[100:101]")
 // the full scan's rows, one after the other (the slow path: no compare ahead of its row)
 #define MCS_FC_FROW(p, F, P, A, FREE)                                                             \
-    "v_cmp_ge_u32_e64 s[50:51], s40, " F "\n\t" /* (under the full wave) */                     \
-    "s_cmp_lg_u64 s[50:51], 0\n\t"                                                                \
-    "s_cbranch_scc0 mcsfa_fr" #p "_%=\n\t"                                                       \
-    "s_mov_b64 exec, s[50:51]\n\t"                                                                \
-    "s_bcnt1_i32_b64 s76, s[50:51]\n\t"                                                          \
+    "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t" /* (under the full wave) */                          \
+    "s_cbranch_vccz mcsfa_fr" #p "_%=\n\t"                                                       \
+    "s_mov_b64 exec, vcc\n\t"                                                                     \
+    "s_bcnt1_i32_b64 s76, vcc\n\t"                                                               \
     "ds_add_u32 " A ", " P "\n\t"                                                               \
     "v_mov_b32 " F ", -1\n\t"                                                                    \
     "s_add_u32 s49, s49, s76\n\t"                                                                \
-    "s_or_b64 " FREE ", " FREE ", s[50:51]\n\t"                                                  \
+    "s_or_b64 " FREE ", " FREE ", vcc\n\t"                                                       \
     "s_mov_b64 exec, -1\n"                                                    \
     "mcsfa_fr" #p "_%=:\n\t"
 // (a slot of row p counts towards XMIN when finish & 7 != p; v111 = -1)
@@ -749,6 +765,11 @@
 // fit test and mcsfa_nofit / mcsfa_zero
 #define MCS_FC_ZROUTE(D)                                                                          \
     "mcsfa_zarr_%=:\n\t"                                                                          \
+    "s_cmp_eq_u32 s47, 64\n\t" /* no job left in the batch, or in the stream: the batch end */  \
+    "s_cbranch_scc1 mcsfa_bend_%=\n\t"                                                            \
+    "s_add_u32 s76, s57, s47\n\t"                                                                 \
+    "s_cmp_ge_u32 s76, s42\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_bend_%=\n\t"                                                            \
     "v_readlane_b32 s76, v87, s47\n\t" /* the true arrival */                                    \
     "s_cmp_lg_u32 s46, 0\n\t"                                                                     \
     "s_cselect_b32 s76, s45, s76\n\t" /* (a non-zero job: the arrival it carries) */             \
@@ -764,105 +785,60 @@
     "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
     "s_branch mcsfa_zero_%=\n"
-// the passes of this form (mcs_fifo_asm.hip's MCS_FA_PASS, with its own clock advances)
-#define MCS_FC_PASS(D)                                                                            \
-    "mcsfa_inner_%=:\n\t"                                                                         \
-    "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
-    "s_cbranch_scc1 mcsfa_arrive_%=\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT "\n"                        \
-    "mcsfa_fitted_%=:\n\t" /* (a release enters here, the fit test done in its tail) */          \
-    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
-    "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    MCS_FA_DECIDE16C                                                                              \
-    "s_mov_b64 exec, -1\n\t"                                                                      \
-    "s_mov_b32 m0, s47\n\t"                                                                       \
-    "s_add_u32 s80, s80, 1\n\t"                                                                   \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n"                                                              \
-    /* next ready job; a WaitQueue head placed sleeps 1 s (:250) */                               \
-    "mcsfa_placed_%=:\n\t"                                                                        \
-    "s_add_u32 s47, s47, 1\n\t" MCS_FA_REC16                                                      \
-    "mcsfa_loopend_%=:\n\t"                                                                       \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc0 mcsfa_bend_%=\n\t"                                                            \
-    "s_sub_u32 s41, s42, s57\n\t"                                                                 \
-    "s_min_u32 s41, s41, 64\n\t"                                                                  \
-    "s_add_u32 s82, s82, 1\n\t" /* waited: counted here, once per placed WaitQueue head */        \
-    "s_mov_b32 s43, 0\n\t"                                                                        \
-    "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_branch mcsfa_adv1_%=\n"                                                                    \
-                                                                                                  \
-    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
-    "s_branch mcsfa_placed_%=\n"                                                                  \
-                                                                                                  \
-    /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
-    /* time; after eight seconds without one, to the exact earliest finish */                    \
-    "mcsfa_nofit_%=:\n\t"                                                                        \
-    "s_mov_b32 s43, 1\n\t"                                                                        \
-    "s_add_u32 s41, s47, 1\n\t" /* the passes stop right after this head is placed */             \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_sub_u32 s78, s78, 1\n\t" /* the runaway guard counts down: the borrow trips it */          \
-    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
-    "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
-    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
-    "s_mov_b32 s79, 8\n"                                                                          \
-    "mcsfa_step_%=:\n\t"                                                                          \
-    "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_sub_u32 s79, s79, 1\n\t"                                                                   \
-    "s_cbranch_scc0 mcsfa_adv1_%=\n\t"                                                            \
-    "v_min3_u32 v90, v32, v33, v34\n\t"                                                          \
-    "v_min3_u32 v90, v90, v35, v36\n\t"                                                          \
-    "v_min3_u32 v90, v90, v37, v38\n\t"                                                          \
-    "v_min3_u32 v120, v90, v39, v39\n\t" MCS_FC_WMIN("s76")                                      \
-    "s_mov_b32 s79, 8\n\t"                                                                        \
-    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
-    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
-    "s_max_u32 s40, s40, s76\n\t"                                                                 \
-    "s_branch mcsfa_adv1_%=\n"                                                                    \
-                                                                                                  \
-    "mcsfa_arrive_%=:\n\t"                                                                       \
-    "s_cmp_eq_u32 s45, -1\n\t" /* the arrival 0xffffffff marks a zero-duration job */             \
-    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
-    "s_sub_u32 s76, s45, s40\n\t"                                                                 \
-    "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
-    MCS_FA_CNTS_##D                                                                               \
-    "s_cmp_lg_u32 s76, 1\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_full_%=\n"                                                              \
-    /* the clock has moved to a second nothing but its own row's slots, or a misplaced one, can */ \
-    /* have finished by */                                                                        \
-    "mcsfa_adv1_%=:\n\t"                                                                          \
+// One copy of the loop per clock residue ("One loop test per pass"): the wave runs copy
+// t & 7, whose row block compares its row's registers, named in the text.  Whatever advances the clock by
+// one second goes on at the next copy's row block: a failed fit's step falls through into it, the placed
+// WaitQueue head's sleep and an arrival one second on branch there; only the XMIN test stays at the
+// advance.  The paths that set the clock to any second, or that all copies share (the full scan, the
+// exact-minimum fallback, the batch end, the spill, the zero route), are single and come back through a
+// table of branches, eight per entry point (MCS_FC_RET: s74 | 32 * entry + 4 * (t & 7), the table on a
+// 256-byte line so the OR never carries).  The padding in front of a copy's mcsfa_norel lies behind an
+// unconditional branch and is never run; it puts the pass's head (mcsfa_fit) 16 bytes into a 64-byte
+// line, the position MCS_FA_HEAD16C kept for the single loop.
+#define MCS_FC_RET(TMP, e)                                                                        \
+    "s_and_b32 " TMP ", s40, 7\n\t"                                                               \
+    "s_lshl2_add_u32 s58, " TMP ", s74\n\t"                                                       \
+    "s_add_u32 s58, s58, 32*" #e "\n\t"                                                           \
+    "s_setpc_b64 s[58:59]\n"
+#define MCS_FC_TBL(name)                                                                          \
+    "s_branch mcsfa_" name "0_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "1_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "2_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "3_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "4_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "5_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "6_%=\n\t"                                                             \
+    "s_branch mcsfa_" name "7_%=\n\t"
+// the XMIN test of a one-second advance into copy n: a misplaced slot due goes to the full scan
+#define MCS_FC_ADV(n)                                                                             \
     "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
-    "s_and_b32 s49, s40, 7\n\t"                                                                   \
-    "s_lshl_b32 s49, s49, 6\n\t"                                                                  \
-    "s_or_b32 s58, s74, s49\n\t"                                                                  \
-    "s_setpc_b64 s[58:59]\n"                                                                      \
-    /* nothing released: a failed fit's sleep goes on, every other advance ends */               \
-    "mcsfa_norel_%=:\n\t"                                                                         \
-    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_step_%=\n\t"                                                            \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_branch mcsfa_loopend_%=\n"                                                                 \
+    "s_branch mcsfa_blk" #n "_%=\n"
+// copy k (row k: finish F, payload P, node address A, free lanes FREE), n = k + 1 mod 8; TAIL closes the
+// failed fit's step: nothing where the next copy follows, a branch to copy 0 after copy 7
+#define MCS_FC_COPY(D, k, n, F, P, A, FREE, TAIL)                                                 \
+    /* the row against t; an expiry refreshes the LDS node copy under the full wave, then hands */ \
+    /* the payloads back under exec = the expiry mask (vcc) and falls into the tail */           \
+    "mcsfa_blk" #k "_%=:\n\t"                                                                     \
+    "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
+    "s_cbranch_vccz mcsfa_norel" #k "_%=\n\t"                                                     \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b64 exec, vcc\n\t"                                                                     \
+    "s_bcnt1_i32_b64 s76, vcc\n\t"                                                               \
+    "ds_add_u32 " A ", " P "\n\t"                                                               \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_or_b64 " FREE ", " FREE ", vcc\n"                                                         \
     /* released (s76 slots; exec any): the peak before the count falls, the node reload, the */  \
-    /* head's fit test and the pass-head tests.  With a head job in the batch that has arrived */ \
-    /* (s47 < s41 and s45 <= t) the tail enters the pass at mcsfa_fitted.  Otherwise (no job */  \
-    /* left in the batch or the pass bound, or a head that has not arrived: s76 = -1 or a later */ \
-    /* arrival, a zero-duration job's 0xffffffff included) the fit test's results are dropped */ \
-    /* (temporaries only: v72-v75, v80, v81, v86, vcc, s55) and the loop goes on at its own */   \
-    /* continuation.  The same instructions are issued either way, so there is one tail. */      \
-    "mcsfa_reltail_%=:\n\t" MCS_FA_CNTR_##D                                                      \
+    /* head's fit test and the arrival test.  A head that has arrived (s45 <= t) enters the pass */ \
+    /* at mcsfa_fitted.  Otherwise (no job left in the batch, the mark of a waiting head's */    \
+    /* successor, a zero-duration job: 0xffffffff; or a later arrival) the fit test's results */  \
+    /* are dropped (temporaries only: v72-v75, v80, v81, v86, vcc, s55) and the loop goes on */   \
+    /* at mcsfa_arrive.  The same instructions are issued either way, so there is one tail. */    \
+    "mcsfa_reltail" #k "_%=:\n\t" MCS_FA_CNTR_##D                                                \
     "s_max_u32 s81, s81, s80\n\t"                                                                 \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16C                                               \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cselect_b32 s76, s45, -1\n\t" /* the head's arrival; none: never */                       \
-    "s_add_u32 s55, s40, s46\n\t"    /* finish */                                                \
+    "s_add_u32 s55, s40, s46\n\t" /* finish */                                                   \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
     "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
     "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
@@ -872,12 +848,128 @@
     "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
     "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
     "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "s_cmp_le_u32 s76, s40\n\t" /* (the wait state the v_perm's read of v81 needs) */            \
+    "s_cmp_le_u32 s45, s40\n\t" /* (the wait state the v_perm's read of v81 needs) */            \
     "v_perm_b32 v86, v81, v80, s72\n\t" MCS_FA_ANYFIT                                            \
-    "s_cbranch_scc1 mcsfa_fitted_%=\n\t"                                                          \
-    "s_cmp_lt_u32 s47, s41\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_inner_%=\n\t"                                                           \
-    "s_branch mcsfa_loopend_%=\n" MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D) MCS_FC_BLOCKS
+    "s_cbranch_scc1 mcsfa_fitted" #k "_%=\n\t"                                                    \
+    "s_branch mcsfa_arrive" #k "_%=\n"                                                            \
+    ".p2align 6\n"                                                                                \
+    /* nothing released: a failed fit's sleep goes on, every other advance ends */               \
+    "mcsfa_norel" #k "_%=:\n\t"                                                                   \
+    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_step" #k "_%=\n"                                                        \
+    "mcsfa_inner" #k "_%=:\n\t"                                                                   \
+    "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
+    "s_cbranch_scc1 mcsfa_arrive" #k "_%=\n"                                                      \
+    "mcsfa_fit" #k "_%=:\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT "\n"                                   \
+    "mcsfa_fitted" #k "_%=:\n\t" /* (a release enters here, the fit test done in its tail) */    \
+    "s_cbranch_vccz mcsfa_nofit" #k "_%=\n\t"                                                     \
+    "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
+    MCS_FA_DECIDE16C(k)                                                                           \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_mov_b32 m0, s47\n\t"                                                                       \
+    "s_add_u32 s80, s80, 1\n\t"                                                                   \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n"                                                              \
+    /* next ready job; a WaitQueue head placed sleeps 1 s (:250) */                               \
+    /* (m0 = the lane of the job just placed; no next job in the batch, a zero-duration one and */ \
+    /* the mark of a placed WaitQueue head all read as the arrival 0xffffffff: one bottom test) */ \
+    "mcsfa_placed" #k "_%=:\n\t" MCS_FC_RECNEXT                                                  \
+    "s_add_u32 s47, s47, 1\n\t"                                                                   \
+    "s_cmp_le_u32 s45, s40\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_fit" #k "_%=\n\t"                                                       \
+    "s_cmp_eq_u32 s45, -1\n\t"                                                                    \
+    "s_cbranch_scc1 mcsfa_zarrp" #k "_%=\n"                                                       \
+    /* a later arrival: sleep to it; more than a second on, every row is scanned */              \
+    "mcsfa_arr2" #k "_%=:\n\t"                                                                    \
+    "s_sub_u32 s76, s45, s40\n\t"                                                                 \
+    "s_mov_b32 s40, s45\n\t" /* (> t) */                                                         \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_cmp_lg_u32 s76, 1\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_ADV(n)                                              \
+    /* (from the pass's head and a release's tail) */                                            \
+    "mcsfa_arrive" #k "_%=:\n\t"                                                                  \
+    "s_cmp_eq_u32 s45, -1\n\t" /* 0xffffffff: a zero-duration job, or no job: out of line */      \
+    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
+    "s_branch mcsfa_arr2" #k "_%=\n"                                                              \
+    /* 0xffffffff from the record read after a placement: with a WaitQueue head placed (s43 = 1; */ \
+    /* m0 = its lane, s47 the next job's) it is, or covers, the mark.  The head is counted as */  \
+    /* waited, the next job's arrival goes back over the mark (v94's own, 0xffffffff where the */ \
+    /* batch has no next job: what s45 holds already), and the head sleeps a second (:250) */    \
+    "mcsfa_zarrp" #k "_%=:\n\t"                                                                   \
+    "s_cmp_eq_u32 s43, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
+    "s_add_u32 s82, s82, 1\n\t"                                                                   \
+    "s_mov_b32 s43, 0\n\t"                                                                        \
+    "s_cmp_eq_u32 s47, 64\n\t"                                                                    \
+    "s_cbranch_scc1 mcsfa_headsl" #k "_%=\n\t"                                                    \
+    "v_readlane_b32 s45, v94, s47\n\t"                                                            \
+    "s_nop 3\n\t"                                                                                 \
+    "v_writelane_b32 v89, s45, m0\n"                                                              \
+    "mcsfa_headsl" #k "_%=:\n\t"                                                                  \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t" MCS_FC_ADV(n)                                            \
+    /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
+    /* time; after eight seconds without one, to the exact earliest finish */                    \
+    "mcsfa_nofit" #k "_%=:\n\t"                                                                   \
+    "s_mov_b32 s43, 1\n\t"                                                                        \
+    /* the mark: the job after this head reads as "never", so the passes stop right after the */ \
+    /* head is placed (lane 63: the sentinel already there; a head failing again: the same write) */ \
+    "v_writelane_b32 v89, -1, s47\n\t"                                                            \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_sub_u32 s78, s78, 1\n\t" /* the runaway guard counts down: the borrow trips it */          \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
+    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
+    "s_mov_b32 s79, 8\n"                                                                          \
+    "mcsfa_step" #k "_%=:\n\t"                                                                    \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
+    "s_sub_u32 s79, s79, 1\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_exact_%=\n\t"                                                           \
+    "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_full_%=\n" TAIL
+// the passes of this form (mcs_fifo_asm.hip's MCS_FA_PASS, with its own clock advances): the entry goes
+// to the copy of its clock through the table, as the batch end does
+#define MCS_FC_PASS(D)                                                                            \
+    "s_branch mcsfa_inner_%=\n"                                                                   \
+    ".p2align 6\n"                                                                                \
+    MCS_FC_COPY(D, 0, 1, "v32", "v40", "v48", "s[86:87]", "")                                     \
+    MCS_FC_COPY(D, 1, 2, "v33", "v41", "v49", "s[88:89]", "")                                     \
+    MCS_FC_COPY(D, 2, 3, "v34", "v42", "v50", "s[90:91]", "")                                     \
+    MCS_FC_COPY(D, 3, 4, "v35", "v43", "v51", "s[92:93]", "")                                     \
+    MCS_FC_COPY(D, 4, 5, "v36", "v44", "v52", "s[94:95]", "")                                     \
+    MCS_FC_COPY(D, 5, 6, "v37", "v45", "v53", "s[96:97]", "")                                     \
+    MCS_FC_COPY(D, 6, 7, "v38", "v46", "v54", "s[98:99]", "")                                     \
+    MCS_FC_COPY(D, 7, 0, "v39", "v47", "v55", "s[100:101]", "\ts_branch mcsfa_blk0_%=\n")        \
+    /* ---- the single paths ---- */                                                              \
+    /* zero-duration job: committed and released before the next decision (D3) */               \
+    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n\t" MCS_FC_RET("s49", 4)                                      \
+    /* a failed fit's ninth step: the clock jumps to the exact earliest finish */                \
+    "mcsfa_exact_%=:\n\t"                                                                         \
+    "v_min3_u32 v121, v32, v33, v34\n\t"                                                         \
+    "v_min3_u32 v121, v121, v35, v36\n\t"                                                        \
+    "v_min3_u32 v121, v121, v37, v38\n\t"                                                        \
+    "v_min3_u32 v120, v121, v39, v39\n\t" MCS_FC_WMIN("s76")                                     \
+    "s_mov_b32 s79, 8\n\t"                                                                        \
+    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_max_u32 s40, s40, s76\n"                                                                   \
+    /* the clock has moved to a second nothing but its own row's slots, or a misplaced one, can */ \
+    /* have finished by */                                                                        \
+    "mcsfa_adv1_%=:\n\t"                                                                          \
+    "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 0)                                      \
+    "mcsfa_norel_%=:\n\t" MCS_FC_RET("s49", 1)                                                   \
+    "mcsfa_reltail_%=:\n\t" MCS_FC_RET("s49", 2)                                                 \
+    "mcsfa_inner_%=:\n\t" MCS_FC_RET("s49", 3)                                                   \
+    "mcsfa_ins_%=:\n\t" MCS_FC_RET("s76", 5) /* (s49 is the spill's row) */                      \
+    "mcsfa_nofit_%=:\n\t" MCS_FC_RET("s49", 6)                                                   \
+    MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D)                                                     \
+    ".p2align 8\n"                                                                                \
+    "mcsfa_tbl_%=:\n\t" MCS_FC_TBL("blk") MCS_FC_TBL("norel") MCS_FC_TBL("reltail")              \
+    MCS_FC_TBL("inner") MCS_FC_TBL("placed") MCS_FC_TBL("ins") MCS_FC_TBL("nofit") "\n"
 
 // ---- W16S: W16R for clusters of at most 64 nodes (one chunk, node = lane) and 2 slot rows --------
 // (cluster_small / cluster_big: C1-C3).  The fit bit is bit 15 of one SDWA AND; no chunk pick, and

@@ -41,7 +41,9 @@
 //     (chunk * 64 + lane) and converts it to the node index when it is stored.  The streamed
 //     W16R loop (W16C) keeps its LDS node copy as one 16-byte word per lane, so its index is the
 //     node index itself; a clock advance of one second compares the one slot row of that second
-//     (a computed jump into eight row blocks) and keeps no earliest finish, a failed fit sleeps a
+//     (the loop is laid out once per t & 7, and a one-second advance goes on in the next copy; the
+//     record read after a placement takes the next job's record from shifted columns, with the
+//     arrival 0xffffffff where the pass has to end) and keeps no earliest finish, a failed fit sleeps a
 //     second at a time, and an advance of more seconds, or one with a misplaced slot due, scans
 //     every row; a release ends with the head job's fit test; its zero-duration jobs leave the
 //     pass through the arrival test, and it counts a waited job where the placed WaitQueue head is
@@ -231,6 +233,17 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_min_u32 s41, s41, 64\n\t"                                                                  \
     "s_mov_b32 s47, 0\n\t" MCS_FA_REC##W MCS_FA_T1("s96")                                         \
     "s_branch mcsfa_inner_%=\n"
+// the streamed W16R loop (W16C): the same, with the batch's bound known before the records are taken
+// (MCS_FC_SHIFT marks the lanes without a job and builds the shifted record columns)
+#define MCS_FA_BENDTAIL_C(W)                                                                      \
+    "s_sub_u32 s41, s42, s57\n\t"                                                                 \
+    "s_min_u32 s41, s41, 64\n\t" MCS_FA_TAKE##W                                                   \
+    "v_add_u32 v121, s57, v110\n\t"                                                               \
+    "v_lshlrev_b32 v121, 4, v121\n\t"                                                             \
+    "v_add_u32 v121, 0x400, v121\n\t"                                                             \
+    "global_load_dwordx4 v[98:101], v121, s[64:65]\n\t" MCS_FC_SHIFT                              \
+    "s_mov_b32 s47, 0\n\t" MCS_FA_REC##W                                                          \
+    "s_branch mcsfa_inner_%=\n"
 // fused records: the statement ends with s59 = 1 and the kernel synthesises the next batch
 #define MCS_FA_BENDTAIL_F(W)                                                                      \
     "s_mov_b32 s47, 0\n\t"                                                                        \
@@ -265,11 +278,11 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_nop 1"
 
 #define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S(W)
-// the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes, the shared
-// entry, ends and exit; its clobbers add FREE's upper rows.  It carries no MCS_STAMPS segment clocks
+// the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes (eight copies,
+// one per clock residue) and batch-end tail, the shared entry, ends and exit; its clobbers add FREE's upper rows.  It carries no MCS_STAMPS segment clocks
 // (its FREE rows occupy s92-s101, where the stamps live), so the probe build does not expand it and
 // runs this shape on W16; the forms with stamps are W32, W16, W16S and the fused W16R / W16S loops
-#define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, S) MCS_FA_EXIT_S(16C)
+#define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, C) MCS_FA_EXIT_S(16C)
 #define MCS_FC_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101"
 
 // ---- the loop with the job stream synthesised in the kernel (mcs_gen_params.fused) ---------------

@@ -34,13 +34,15 @@ N, J, LANES, ROWS = 256, 16384, 64, 8
 
 # instructions issued, from the listing (scalar and branch | vector | LDS)
 COST = {
-    # mcsfa_adv1 (6) + the row's block with an expiry (6 | 2 | 2) + mcsfa_reltail (9 | 10 | 1)
-    "one-row scan": {"scalar": 6 + 6 + 9, "vector": 2 + 10, "lds": 3},
-    # mcsfa_adv1 + the block's compare and two scalar + mcsfa_norel (2 and the next step's 4 after a failed
-    # fit, the usual case; 4 or 5 else)
-    "empty compare": {"scalar": 6 + 2 + 6, "vector": 1, "lds": 0},
-    # MCS_FC_FULL: the advance's test (2-4) + 8 x (2 | 1) + per expiring row (6 | 1 | 1) + 5 + mcsfa_reltail
-    "full scan": {"scalar": 4 + 1 + 16 + 6 * 1.7 + 5 + 9, "vector": 8 + 1.7 + 10, "lds": 2 + 1.7},
+    # the advance's XMIN test (2; a branch more from the placed head and an arrival) + the copy's row block
+    # with an expiry (4 | 2 | 2) + mcsfa_reltail (7 | 10 | 1)
+    "one-row scan": {"scalar": 2 + 4 + 7, "vector": 2 + 10, "lds": 3},
+    # the XMIN test + the block's compare and its branch + mcsfa_norel (2 and the next step's 4 after a failed
+    # fit, the usual case; 2 or 3 else)
+    "empty compare": {"scalar": 2 + 1 + 6, "vector": 1, "lds": 0},
+    # MCS_FC_FULL: the advance's test (2-4) + 8 x (1 | 1) + per expiring row (5 | 1 | 1) + 5 + the computed
+    # jump back into the copy (4 and the table's branch) + mcsfa_reltail
+    "full scan": {"scalar": 4 + 1 + 8 + 5 * 1.7 + 5 + 5 + 7, "vector": 8 + 1.7 + 10, "lds": 2 + 1.7},
     # ... and XMIN's rebuild after one a misplaced slot asked for (32 vector, v_mov, 6 DPP, v_readlane | 7 s_nop)
     "XMIN rebuild": {"scalar": 7, "vector": 40, "lds": 0},
     # MCS_FA_SCAN16Q + MCS_FA_SCANEND16Q + the pair blocks (tools/scan_rows_model.py: 14.8 scalar and branch
