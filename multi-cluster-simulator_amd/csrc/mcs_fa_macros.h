@@ -24,30 +24,32 @@
 //                                                                                              W16C's release tail (the same
 //                                                                                              pair): s_cmp_le_u32 between
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
-//    uses it as the lane select                            written                             from s_add/s_mov; the placed head's
-//                                                                                              restore reads s45 from v_readlane
-//                                                                                              as DATA of v_writelane: s_nop 3)
+//    uses it as the lane select                            written                             from s_add/s_mov)
 //  SALU writes M0 -> v_writelane with an M0 lane     1*    result writes at a Level0 decision  >= 1 other instruction between
 //    select (*not in the ISA table; kept anyway)           (HEAD, ZEROKX)                      (s_add s80 / s_ff1, s_lshl3_add)
 //                                                          DELAY G list (MCS_FD_ENUM: m0 =     s_add s86 between
 //                                                          cursor -> v_writelane v113/v118)
-//                                                          W16C's record read (MCS_FC_RECNEXT: s_add s80 + two v_writelane between;
-//                                                          v_readlane with m0 the lane select)  after mcsfa_zero: the same two
+//                                                          W16C's record read (MCS_FC_RECNEXT: s_add s80 + two v_writelane between,
+//                                                          v_readlane with m0 the lane select;  in the waiting-head section s_add s82
+//                                                          the pass, the waiting-head section   and s_mov s43 more; after mcsfa_zero
+//                                                          and mcsfa_zhead alike)               the two v_writelane at least
 //  VALU writes VGPR -> v_readlane / v_readfirstlane  1     DECIDE16R / DECIDE16C / ZEROKX      >= 3 instructions between every
 //    reads it (gfx950)                                     read v86, v117; REC16 after TAKE16; pair; SCANEND, WMIN: s_nop 1;
 //                                                          SCANEND, MCS_FC_WMIN v120;          v87: a batch's passes apart
 //                                                          MCS_FC_ZROUTE v87 (written at the
 //                                                          batch's TAKE16C)
 //                                                          W16C's v89 / v90 / v107 (written    s_mov s47 + three v_readlane after
-//                                                          per batch, MCS_FC_SHIFT; v89 also   the batch's; >= 8 instructions after
-//                                                          by the mark and its restore)        the mark or the restore
+//                                                          per batch only, MCS_FC_SHIFT)       the batch's
+//                                                          W16C's sections: v72-v75, v80, v81,  the pass's own distances (the same
+//                                                          v86 of MCS_FA_FIT16C in the tail     macros: FIT16C, DECIDE16C)
 //                                                          DELAY G pass (r04): v_cndmask v113  >= 6 (GTEST's scalar prologue)
 //                                                          -> GTEST's v_readlane v113; v123
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
 //                                                                                              s_cmp)
 //  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch; W16C's    (interlocked on gfx9; the pass's
 //                                                          row compare (v_cmp vcc, then        head and the row compare branch
-//                                                          s_cbranch_vccz, copies and scan)    right after the v_cmp)
+//                                                          s_cbranch_vccz, copies and scan;    right after the v_cmp)
+//                                                          s_cbranch_vccnz in the sleep chain)
 //  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16C's row
 //                                                                                              blocks: s_mov_b64 exec)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
@@ -68,9 +70,10 @@
 //  VALU writes SGPR -> SALU reads it               0     W16C's row compares (vcc -> s_mov   (interlocked)
 //                                                          exec / s_bcnt1 / s_or), the record
 //                                                          read's s45 -> s_cmp
-//  s_setpc_b64 to a computed address               -     W16C's MCS_FC_RET                    the table of branches starts on a
-//                                                                                              256-byte line and is 224 bytes, so
-//                                                                                              s74 + 32 * entry + 4 * (t & 7) never
+//  s_setpc_b64 to a computed address               -     W16C's MCS_FC_RET / MCS_FC_RETW      the table of branches starts on a
+//                                                                                              512-byte line and is 384 bytes, so
+//                                                                                              s74 + 32 * entry + 4 * (t & 7), with
+//                                                                                              32 * s43 (s43 <= 2) more, never
 //                                                                                              carries into s59
 // A reorder that moves a consumer next to its producer in the table must add the s_nop.
 
@@ -520,28 +523,31 @@
 // instructions only (no v_cmp / v_ffbl / v_readlane of a free-row column, and the fit test carries none).
 //   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), read and written by the
 //             insert with s_movrels/s_movreld (m0 = 2r), by a release as static registers
-//   s77 XMIN   s74, s59 the address of the copies' table of branches (MCS_FC_RET; on a 256-byte line),
+//   s77 XMIN   s74, s59 the address of the copies' table of branches (MCS_FC_RET; on a 512-byte line),
 //   low and high word   s[58:59] a computed jump's target   s[60:61] the insert's FREE[r], s[50:51] without
 //   the lane handed out   s49 r / a computed jump's t & 7 / the full scan's released count   s79 the node
-//   address of the insert; the seconds left of a failed fit's stepping   s41 min(64, J - cb), read where a
+//   address of the insert; the limit of a waiting head's sleep, min(XMIN, t + 9)   s43 1 while a head waits in
+//   a copy's section, 2 while a zero-duration job waits out of line, else 0   s41 min(64, J - cb), read where a
 //   batch is taken only   v89, v90, v107 the record columns shifted by one lane (MCS_FC_SHIFT)   m0 after a
 //   placement: the lane of the job placed, the record read's lane select
 //   s78 the failed fits left of the runaway bound   s82 the WaitQueue heads placed (a head waiting at
 //   the exit is s43)   v87 the batch's true arrival column (v94 holds 0xffffffff for its zero-duration
 //   jobs; both 0xffffffff in the lanes past the stream's end)   s75 is not used
-// The clock moves in three ways.  By one second (the placed WaitQueue head, each step of a failed fit's
-// sleep) or to a second nothing can finish before (an arrival one second on, the exact-minimum
-// fallback): the XMIN test and the row block of the copy of that second (MCS_FC_COPY: the next copy's
+// The clock moves in three ways.  By one second (the placed WaitQueue head; each step of a failed fit's
+// sleep has a block of its own, MCS_FC_WSL) or to a second nothing can finish before (an arrival one
+// second on): the XMIN test and the row block of the copy of that second (MCS_FC_COPY: the next copy's
 // after a one-second advance, through mcsfa_adv1's computed jump otherwise), which compares the row
 // and either leaves at once (mcsfa_norel: no LDS traffic) or releases it and falls into the tail
 // (mcsfa_reltail: node reload, the head's fit test, and into the pass at mcsfa_fitted).  By more
 // than a second (an arrival gap), or with a misplaced slot due (t >= XMIN): mcsfa_full, every row in
 // turn against t, and after one that XMIN asked for, XMIN rebuilt as the minimum over the slots with
 // finish & 7 != row (free slots hold -1 and drop out; a gap's full scan at t < XMIN releases no
-// misplaced slot, so XMIN stands, and stays exact).  A failed fit steps second by second (each step the row compare and the XMIN
-// test); after eight steps without a release every row has been compared, and the clock jumps to the
+// misplaced slot, so XMIN stands, and stays exact).  A failed fit steps second by second in its copy's
+// waiting-head section (each step the row compare and one test against min(XMIN, t + 9): MCS_FC_COPY,
+// MCS_FC_WSL); after eight steps without a release every row has been compared, and the clock jumps to the
 // exact earliest finish (lane-minimum tree + DPP, as every other form's scan end).  Nothing running
-// is s80 == 0.  A release scan is counted where something is released (mcsfa_reltail).
+// is s80 == 0.  A release scan is counted where something is released (mcsfa_reltail, mcsfa_wreltail,
+// mcsfa_zreltail).
 // Hazards (table above): m0 is written two instructions before s_movrels reads it (one wait state
 // needed) and nothing writes it before s_movreld; s_set_gpr_idx_on / _idx overwrite m0, so both
 // relative moves come before the region, and m0 = the cursor is set after it as in every form; the
@@ -568,8 +574,8 @@
 // it runs anyway: when a batch is taken, the arrival column v94 gets 0xffffffff in the lanes of
 // zero-duration jobs (the true arrivals stay in v87), so the head's arrival test sends such a job to
 // mcsfa_arrive, which tells it apart by that arrival and takes it out of line (MCS_FC_ZROUTE):
-// the true arrival's test, the fit test, and then mcsfa_nofit or mcsfa_zero.  A retry after a release
-// comes back the same way.  The pass itself has no duration test.  (The clock never reaches
+// the true arrival's test, the fit test, and then mcsfa_znofit (it waits out of line) or mcsfa_zero.
+// The pass itself has no duration test.  (The clock never reaches
 // 0xffffffff in this loop and no arrival is 0xffffffff: the host bounds last arrival + sum(dur + 1)
 // below it, and streams without that bound run the compiled kernel.  A non-zero job carrying that
 // arrival would still sleep to it as before.)
@@ -619,11 +625,13 @@
     "s_lshl2_add_u32 s54, s50, s53\n\t"
 #define MCS_FA_POOLMAX16C "64*8"
 #define MCS_FA_NODEIDX16C "v_mov_b32 v126, v91\n\t"
-// The WaitQueue statistic of this form is counted where the placed WaitQueue head is handled
-// (mcsfa_zarrp in MCS_FC_COPY: once per waited job, where the shared loop pays a subtract and an add at
-// every failed fit); a head still waiting when the loop leaves (deadlock, clock overflow, the runaway
-// guard: s43 = 1 on exactly those exits, 0 on every other) is added at the exit.
-#define MCS_FA_XWAITED16C "s_add_u32 %[waited], s82, s43\n\t"
+// The WaitQueue statistic of this form is counted where the WaitQueue head is placed (the waiting-head
+// section of MCS_FC_COPY, mcsfa_zhead: once per waited job, where the shared loop pays a subtract and an
+// add at every failed fit); a head still waiting when the loop leaves (deadlock, the runaway guard:
+// s43 = 1, or 2 for a zero-duration job, on exactly those exits, 0 on every other) is added at the exit.
+#define MCS_FA_XWAITED16C                                                                         \
+    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
+    "s_addc_u32 %[waited], s82, 0\n\t"
 // The runaway guard counts s78 down from the bound 4J + 256 and the borrow is its test (the failed fit
 // number 4J + 257 trips it, as the shared loop's s78 > s79); s79 has another use in this form.
 #define MCS_FA_GUARD016C "s_lshl2_add_u32 s78, s42, 0x100\n\t"
@@ -657,8 +665,9 @@
     "v_mov_b32 v39, -1\n\t"
 // MCS_FA_DECIDE16R's single register-index region; the slot is the lowest free lane of row
 // r = finish & 7 (s_ff1 of an empty FREE[r] is -1: the shift then gives a bit the AND drops, SCC of
-// the AND = a slot exists; none: the spill, out of line)
-#define MCS_FA_DECIDE16C(k)                                                                       \
+// the AND = a slot exists; none: the spill, out of line); L names the label the spill returns to: "ins"
+// in a copy's pass, "wins" in its waiting-head section
+#define MCS_FA_DECIDE16C(L, k)                                                                    \
     "s_and_b32 s49, s55, 7\n\t"                                                                   \
     "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
     "v_readlane_b32 s51, v86, s50\n\t"                                                            \
@@ -673,7 +682,7 @@
     "s_and_b64 s[62:63], s[62:63], s[60:61]\n\t"                                                  \
     "s_cbranch_scc0 mcsfa_sp_%=\n\t"                                                              \
     "s_movreld_b64 s[86:87], s[50:51]\n" /* the slot is handed out */                            \
-    "mcsfa_ins" #k "_%=:\n\t"                                                                           \
+    "mcsfa_" L #k "_%=:\n\t"                                                                      \
     "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
     "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
     "s_mov_b64 exec, s[62:63]\n\t"                                                                \
@@ -761,8 +770,21 @@
     "s_cmp_eq_u32 s49, 0\n\t"                                                                     \
     "s_cbranch_scc1 mcsfa_norel_%=\n\t"                                                           \
     "s_branch mcsfa_reltail_%=\n"
+// every running slot's earliest finish into s76 (lane-minimum tree + DPP; free slots hold -1)
+#define MCS_FC_EXACTMIN                                                                           \
+    "v_min3_u32 v121, v32, v33, v34\n\t"                                                         \
+    "v_min3_u32 v121, v121, v35, v36\n\t"                                                        \
+    "v_min3_u32 v121, v121, v37, v38\n\t"                                                        \
+    "v_min3_u32 v120, v121, v39, v39\n\t" MCS_FC_WMIN("s76")
 // the zero route (out of line, from mcsfa_arrive): the true arrival's test and the sleep to it, or the
-// fit test and mcsfa_nofit / mcsfa_zero
+// fit test and mcsfa_zero.  A zero-duration job that fits nowhere waits out of line as well
+// (mcsfa_znofit, s43 = 2; 1 in 600 jobs has zero duration and few of those wait, so the copies' waiting-
+// head sections know nothing of it): counted and guarded as every failed fit, then the clock jumps to
+// the exact earliest finish, every row is scanned (mcsfa_full, which comes back to mcsfa_zreltail
+// through the table: s43 selects the entry), and the release's bookkeeping ends in mcsfa_zfit again.
+// The seconds in between have no completion, so the releases, the failed fits and both counters are
+// those of a sleep taken second by second.  Placed (mcsfa_zero, which tests s43), it is counted as
+// waited, the next job's record is read and the head sleeps its second (mcsfa_zhead).
 #define MCS_FC_ZROUTE(D)                                                                          \
     "mcsfa_zarr_%=:\n\t"                                                                          \
     "s_cmp_eq_u32 s47, 64\n\t" /* no job left in the batch, or in the stream: the batch end */  \
@@ -782,24 +804,84 @@
     "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
     "s_branch mcsfa_adv1_%=\n"                                                                    \
     "mcsfa_zfit_%=:\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT                                             \
-    "s_cbranch_vccz mcsfa_nofit_%=\n\t"                                                           \
+    "s_cbranch_vccz mcsfa_znofit_%=\n\t"                                                          \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
-    "s_branch mcsfa_zero_%=\n"
+    "s_branch mcsfa_zero_%=\n"                                                                    \
+    "mcsfa_znofit_%=:\n\t"                                                                        \
+    "s_mov_b32 s43, 2\n\t"                                                                        \
+    MCS_FA_CNTS_##D                                                                               \
+    "s_sub_u32 s78, s78, 1\n\t" /* the runaway guard */                                          \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
+    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t" MCS_FC_EXACTMIN                                        \
+    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_max_u32 s40, s40, s76\n\t"                                                                 \
+    "s_branch mcsfa_full_%=\n"                                                                    \
+    "mcsfa_zreltail_%=:\n\t" MCS_FA_CNTR_##D                                                     \
+    "s_max_u32 s81, s81, s80\n\t"                                                                 \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16C                                               \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    "s_branch mcsfa_zfit_%=\n"                                                                    \
+    "mcsfa_zhead_%=:\n\t" /* (m0 = the head's lane, from mcsfa_zero) */                          \
+    "s_add_u32 s82, s82, 1\n\t"                                                                   \
+    "s_mov_b32 s43, 0\n\t" MCS_FC_RECNEXT                                                        \
+    "s_add_u32 s47, s47, 1\n\t"                                                                   \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_branch mcsfa_adv1_%=\n"
 // One copy of the loop per clock residue ("One loop test per pass"): the wave runs copy
 // t & 7, whose row block compares its row's registers, named in the text.  Whatever advances the clock by
-// one second goes on at the next copy's row block: a failed fit's step falls through into it, the placed
-// WaitQueue head's sleep and an arrival one second on branch there; only the XMIN test stays at the
-// advance.  The paths that set the clock to any second, or that all copies share (the full scan, the
+// one second goes on at the next copy's row block: the placed WaitQueue head's sleep falls through into it,
+// an arrival one second on branches there; only the XMIN test stays at the advance.  The paths that set the clock to any second, or that all copies share (the full scan, the
 // exact-minimum fallback, the batch end, the spill, the zero route), are single and come back through a
-// table of branches, eight per entry point (MCS_FC_RET: s74 | 32 * entry + 4 * (t & 7), the table on a
-// 256-byte line so the OR never carries).  The padding in front of a copy's mcsfa_norel lies behind an
-// unconditional branch and is never run; it puts the pass's head (mcsfa_fit) 16 bytes into a 64-byte
-// line, the position MCS_FA_HEAD16C kept for the single loop.
+// table of branches, eight per entry point (MCS_FC_RET: s74 + 32 * entry + 4 * (t & 7), the table on a
+// 512-byte line and 384 bytes long, so the sum never carries).  The padding in front of a copy's
+// mcsfa_norel lies behind an unconditional branch and is never run; it puts the pass's head (mcsfa_fit)
+// 16 bytes into a 64-byte line, the position MCS_FA_HEAD16C kept for the single loop.
+//
+// A waiting WaitQueue head has a section of its own in each copy ("The waiting head"),
+// entered at the failed fit (mcsfa_nofit<k>) and left when the head is placed; nothing else runs while
+// s43 = 1.  Its sleep is a chain of eight blocks, one per residue, laid out one after the other behind the
+// copies (MCS_FC_WSL): a step is the clock's s_add, one compare against the limit s79 = min(XMIN, t + 9)
+// formed at the failed fit (XMIN cannot change in a sleep: nothing is inserted, and a full scan comes
+// back through mcsfa_wnorel or the failed fit, which form the limit again), the row's v_cmp and the
+// branch to the section's release, and falls into the next residue's block.  At the limit (mcsfa_wslow) a
+// misplaced slot is due (the full scan) or eight rows have been compared for nothing (mcsfa_exact: the
+// jump to the exact earliest finish).  The section's release (mcsfa_wrel<k>) is the row block's body and
+// the tail without the arrival compare: the head has arrived.  A failed re-test is a failed fit again
+// (the guard counts, the limit is formed again).  The head's placement is the pass's decision and
+// result writes, then without a test: it is counted as waited, s43 = 0, the next job's record, the
+// one-second sleep (:250), the XMIN test, and the next copy's ordinary row block.  The single paths a
+// waiting head can take (the full scan, the spill) return through MCS_FC_RETW, whose table entry is
+// e + s43: the waiting head's entry follows the ordinary one, a waiting zero-duration job's (s43 = 2,
+// MCS_FC_ZROUTE) that one.
+// The one-second advances carry no overflow branch: the host bounds last arrival + sum(dur + 1) below
+// 2^32 - 1 for every stream that runs this loop (mcs_submit_jobs, mcs_generate_jobs; unchecked_horizon
+// runs the compiled kernel), and no clock of the run exceeds that sum; a clock that did reach
+// 0xffffffff is still flagged after the loop (fifo_asm_kernel).
+// Table entries: 0 blk, 1 norel, 2 wnorel, 3 (zero job, no release: cannot be, flagged), 4 reltail,
+// 5 wreltail, 6 zreltail, 7 ins, 8 wins, 9 wblk, 10 inner, 11 placed.
 #define MCS_FC_RET(TMP, e)                                                                        \
     "s_and_b32 " TMP ", s40, 7\n\t"                                                               \
     "s_lshl2_add_u32 s58, " TMP ", s74\n\t"                                                       \
     "s_add_u32 s58, s58, 32*" #e "\n\t"                                                           \
     "s_setpc_b64 s[58:59]\n"
+#define MCS_FC_RETW(TMP, e)                                                                       \
+    "s_and_b32 " TMP ", s40, 7\n\t"                                                               \
+    "s_lshl3_add_u32 " TMP ", s43, " TMP "\n\t"                                                   \
+    "s_lshl2_add_u32 s58, " TMP ", s74\n\t"                                                       \
+    "s_add_u32 s58, s58, 32*" #e "\n\t"                                                           \
+    "s_setpc_b64 s[58:59]\n"
+#define MCS_FC_TBL1(name)                                                                         \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"                                                              \
+    "s_branch mcsfa_" name "_%=\n\t"
 #define MCS_FC_TBL(name)                                                                          \
     "s_branch mcsfa_" name "0_%=\n\t"                                                             \
     "s_branch mcsfa_" name "1_%=\n\t"                                                             \
@@ -815,7 +897,7 @@
     "s_cbranch_scc1 mcsfa_full_%=\n\t"                                                            \
     "s_branch mcsfa_blk" #n "_%=\n"
 // copy k (row k: finish F, payload P, node address A, free lanes FREE), n = k + 1 mod 8; TAIL closes the
-// failed fit's step: nothing where the next copy follows, a branch to copy 0 after copy 7
+// placed head's sleep: nothing where the next copy's row block follows, a branch to copy 0 after copy 7
 #define MCS_FC_COPY(D, k, n, F, P, A, FREE, TAIL)                                                 \
     /* the row against t; an expiry refreshes the LDS node copy under the full wave, then hands */ \
     /* the payloads back under exec = the expiry mask (vcc) and falls into the tail */           \
@@ -830,10 +912,10 @@
     "s_or_b64 " FREE ", " FREE ", vcc\n"                                                         \
     /* released (s76 slots; exec any): the peak before the count falls, the node reload, the */  \
     /* head's fit test and the arrival test.  A head that has arrived (s45 <= t) enters the pass */ \
-    /* at mcsfa_fitted.  Otherwise (no job left in the batch, the mark of a waiting head's */    \
-    /* successor, a zero-duration job: 0xffffffff; or a later arrival) the fit test's results */  \
-    /* are dropped (temporaries only: v72-v75, v80, v81, v86, vcc, s55) and the loop goes on */   \
-    /* at mcsfa_arrive.  The same instructions are issued either way, so there is one tail. */    \
+    /* at mcsfa_fitted.  Otherwise (no job left in the batch, a zero-duration job: 0xffffffff; */  \
+    /* or a later arrival) the fit test's results are dropped (temporaries only: v72-v75, v80, */  \
+    /* v81, v86, vcc, s55) and the loop goes on at mcsfa_arrive.  The same instructions are */    \
+    /* issued either way, so there is one tail.  (No head waits here: its section has a tail.) */      \
     "mcsfa_reltail" #k "_%=:\n\t" MCS_FA_CNTR_##D                                                \
     "s_max_u32 s81, s81, s80\n\t"                                                                 \
     "s_mov_b64 exec, -1\n\t"                                                                      \
@@ -852,11 +934,11 @@
     "v_perm_b32 v86, v81, v80, s72\n\t" MCS_FA_ANYFIT                                            \
     "s_cbranch_scc1 mcsfa_fitted" #k "_%=\n\t"                                                    \
     "s_branch mcsfa_arrive" #k "_%=\n"                                                            \
-    ".p2align 6\n"                                                                                \
-    /* nothing released: a failed fit's sleep goes on, every other advance ends */               \
-    "mcsfa_norel" #k "_%=:\n\t"                                                                   \
-    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_step" #k "_%=\n"                                                        \
+    ".p2align 6\n\t"                                                                              \
+    "s_nop 0\n\t" /* (never run: mcsfa_fit 16 bytes into the line) */                            \
+    "s_nop 0\n"                                                                                   \
+    /* nothing released: the advance ends (a sleeping head never comes here) */                  \
+    "mcsfa_norel" #k "_%=:\n"                                                                     \
     "mcsfa_inner" #k "_%=:\n\t"                                                                   \
     "s_cmp_gt_u32 s45, s40\n\t" /* ready head not arrived: sleep to it */                         \
     "s_cbranch_scc1 mcsfa_arrive" #k "_%=\n"                                                      \
@@ -864,21 +946,21 @@
     "mcsfa_fitted" #k "_%=:\n\t" /* (a release enters here, the fit test done in its tail) */    \
     "s_cbranch_vccz mcsfa_nofit" #k "_%=\n\t"                                                     \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    MCS_FA_DECIDE16C(k)                                                                           \
+    MCS_FA_DECIDE16C("ins", k)                                                                    \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
     "v_writelane_b32 v92, s40, m0\n"                                                              \
-    /* next ready job; a WaitQueue head placed sleeps 1 s (:250) */                               \
-    /* (m0 = the lane of the job just placed; no next job in the batch, a zero-duration one and */ \
-    /* the mark of a placed WaitQueue head all read as the arrival 0xffffffff: one bottom test) */ \
+    /* next ready job */                                                                          \
+    /* (m0 = the lane of the job just placed; no next job in the batch and a zero-duration one */ \
+    /* both read as the arrival 0xffffffff: one bottom test) */                                   \
     "mcsfa_placed" #k "_%=:\n\t" MCS_FC_RECNEXT                                                  \
     "s_add_u32 s47, s47, 1\n\t"                                                                   \
     "s_cmp_le_u32 s45, s40\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_fit" #k "_%=\n\t"                                                       \
     "s_cmp_eq_u32 s45, -1\n\t"                                                                    \
-    "s_cbranch_scc1 mcsfa_zarrp" #k "_%=\n"                                                       \
+    "s_cbranch_scc1 mcsfa_zarr_%=\n"                                                              \
     /* a later arrival: sleep to it; more than a second on, every row is scanned */              \
     "mcsfa_arr2" #k "_%=:\n\t"                                                                    \
     "s_sub_u32 s76, s45, s40\n\t"                                                                 \
@@ -891,43 +973,66 @@
     "s_cmp_eq_u32 s45, -1\n\t" /* 0xffffffff: a zero-duration job, or no job: out of line */      \
     "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
     "s_branch mcsfa_arr2" #k "_%=\n"                                                              \
-    /* 0xffffffff from the record read after a placement: with a WaitQueue head placed (s43 = 1; */ \
-    /* m0 = its lane, s47 the next job's) it is, or covers, the mark.  The head is counted as */  \
-    /* waited, the next job's arrival goes back over the mark (v94's own, 0xffffffff where the */ \
-    /* batch has no next job: what s45 holds already), and the head sleeps a second (:250) */    \
-    "mcsfa_zarrp" #k "_%=:\n\t"                                                                   \
-    "s_cmp_eq_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
-    "s_add_u32 s82, s82, 1\n\t"                                                                   \
-    "s_mov_b32 s43, 0\n\t"                                                                        \
-    "s_cmp_eq_u32 s47, 64\n\t"                                                                    \
-    "s_cbranch_scc1 mcsfa_headsl" #k "_%=\n\t"                                                    \
-    "v_readlane_b32 s45, v94, s47\n\t"                                                            \
-    "s_nop 3\n\t"                                                                                 \
-    "v_writelane_b32 v89, s45, m0\n"                                                              \
-    "mcsfa_headsl" #k "_%=:\n\t"                                                                  \
-    "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t" MCS_FC_ADV(n)                                            \
+    /* ---- the copy's waiting-head section (after the copy's text; entered by branches only) ---- */ \
     /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
-    /* time; after eight seconds without one, to the exact earliest finish */                    \
+    /* time up to the limit s79 = min(XMIN, t + 9), in the chain of sleep blocks (MCS_FC_WSL) */   \
     "mcsfa_nofit" #k "_%=:\n\t"                                                                   \
     "s_mov_b32 s43, 1\n\t"                                                                        \
-    /* the mark: the job after this head reads as "never", so the passes stop right after the */ \
-    /* head is placed (lane 63: the sentinel already there; a head failing again: the same write) */ \
-    "v_writelane_b32 v89, -1, s47\n\t"                                                            \
     MCS_FA_CNTS_##D                                                                               \
     "s_sub_u32 s78, s78, 1\n\t" /* the runaway guard counts down: the borrow trips it */          \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
+    "s_add_u32 s79, s40, 9\n\t"                                                                   \
+    "s_min_u32 s79, s79, s77\n\t"                                                                 \
     "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
-    "s_cbranch_scc1 mcsfa_deadlock_%=\n\t"                                                        \
-    "s_mov_b32 s79, 8\n"                                                                          \
-    "mcsfa_step" #k "_%=:\n\t"                                                                    \
+    "s_cbranch_scc0 mcsfa_wsl" #n "_%=\n\t"                                                       \
+    "s_branch mcsfa_deadlock_%=\n"                                                                \
+    /* (a full scan at this second released nothing: the sleep goes on under a new limit) */      \
+    "mcsfa_wnorel" #k "_%=:\n\t"                                                                  \
+    "s_add_u32 s79, s40, 9\n\t"                                                                   \
+    "s_min_u32 s79, s79, s77\n\t"                                                                 \
+    "s_branch mcsfa_wsl" #n "_%=\n"                                                               \
+    /* the section's release: the row block's body, and the tail for a head that has arrived */  \
+    /* (vcc = the row's expiry mask; a full scan enters at mcsfa_wreltail with s76 its count) */  \
+    "mcsfa_wrel" #k "_%=:\n\t"                                                                    \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b64 exec, vcc\n\t"                                                                     \
+    "s_bcnt1_i32_b64 s76, vcc\n\t"                                                               \
+    "ds_add_u32 " A ", " P "\n\t"                                                               \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_or_b64 " FREE ", " FREE ", vcc\n"                                                         \
+    "mcsfa_wreltail" #k "_%=:\n\t" MCS_FA_CNTR_##D                                               \
+    "s_max_u32 s81, s81, s80\n\t"                                                                 \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16C                                               \
+    "s_waitcnt lgkmcnt(0)\n\t" MCS_FA_FIT16C MCS_FA_ANYFIT                                       \
+    "s_cbranch_vccz mcsfa_nofit" #k "_%=\n\t" /* fails again: a failed fit like the first */     \
+    /* the head's placement: the pass's decision and result writes; then it is counted as */     \
+    /* waited, the next job's record is read (m0 = the head's lane), and the head sleeps a */    \
+    /* second (:250) into the next copy's ordinary row block */                                  \
+    "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
+    MCS_FA_DECIDE16C("wins", k)                                                                   \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_mov_b32 m0, s47\n\t"                                                                       \
+    "s_add_u32 s80, s80, 1\n\t"                                                                   \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
+    "s_add_u32 s82, s82, 1\n\t"                                                                   \
+    "s_mov_b32 s43, 0\n\t" MCS_FC_RECNEXT                                                        \
+    "s_add_u32 s47, s47, 1\n\t"                                                                   \
     "s_add_u32 s40, s40, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_clkovf_%=\n\t"                                                          \
-    "s_sub_u32 s79, s79, 1\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_exact_%=\n\t"                                                           \
     "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_full_%=\n" TAIL
+// one block of the sleep chain: the step into a second of residue k, then row k against it.  The blocks
+// of the eight residues follow one another (MCS_FC_PASS), so a step that finds nothing falls into the
+// next; mcsfa_wblk<k> is where the exact-minimum jump lands
+#define MCS_FC_WSL(k, F)                                                                          \
+    "mcsfa_wsl" #k "_%=:\n\t"                                                                     \
+    "s_add_u32 s40, s40, 1\n\t"                                                                   \
+    "s_cmp_ge_u32 s40, s79\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_wslow_%=\n"                                                             \
+    "mcsfa_wblk" #k "_%=:\n\t"                                                                    \
+    "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
+    "s_cbranch_vccnz mcsfa_wrel" #k "_%=\n"
 // the passes of this form (mcs_fifo_asm.hip's MCS_FA_PASS, with its own clock advances): the entry goes
 // to the copy of its clock through the table, as the batch end does
 #define MCS_FC_PASS(D)                                                                            \
@@ -940,36 +1045,47 @@
     MCS_FC_COPY(D, 4, 5, "v36", "v44", "v52", "s[94:95]", "")                                     \
     MCS_FC_COPY(D, 5, 6, "v37", "v45", "v53", "s[96:97]", "")                                     \
     MCS_FC_COPY(D, 6, 7, "v38", "v46", "v54", "s[98:99]", "")                                     \
-    MCS_FC_COPY(D, 7, 0, "v39", "v47", "v55", "s[100:101]", "\ts_branch mcsfa_blk0_%=\n")        \
+    MCS_FC_COPY(D, 7, 0, "v39", "v47", "v55", "s[100:101]", "\ts_branch mcsfa_blk0_%=\n")         \
+    /* ---- the sleep chain of the waiting-head sections ---- */                                 \
+    MCS_FC_WSL(0, "v32") MCS_FC_WSL(1, "v33") MCS_FC_WSL(2, "v34") MCS_FC_WSL(3, "v35")           \
+    MCS_FC_WSL(4, "v36") MCS_FC_WSL(5, "v37") MCS_FC_WSL(6, "v38") MCS_FC_WSL(7, "v39")           \
+    "\ts_branch mcsfa_wsl0_%=\n"                                                                  \
     /* ---- the single paths ---- */                                                              \
-    /* zero-duration job: committed and released before the next decision (D3) */               \
-    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
-    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t" MCS_FC_RET("s49", 4)                                      \
-    /* a failed fit's ninth step: the clock jumps to the exact earliest finish */                \
-    "mcsfa_exact_%=:\n\t"                                                                         \
-    "v_min3_u32 v121, v32, v33, v34\n\t"                                                         \
-    "v_min3_u32 v121, v121, v35, v36\n\t"                                                        \
-    "v_min3_u32 v121, v121, v37, v38\n\t"                                                        \
-    "v_min3_u32 v120, v121, v39, v39\n\t" MCS_FC_WMIN("s76")                                     \
-    "s_mov_b32 s79, 8\n\t"                                                                        \
+    /* the sleep has reached its limit: a misplaced slot is due (every row is scanned), or eight */ \
+    /* rows were compared for nothing and the clock jumps to the exact earliest finish */        \
+    "mcsfa_wslow_%=:\n\t"                                                                         \
+    "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_full_%=\n"                                                              \
+    "mcsfa_exact_%=:\n\t" MCS_FC_EXACTMIN                                                         \
     "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
-    "s_max_u32 s40, s40, s76\n"                                                                   \
+    "s_max_u32 s40, s40, s76\n\t"                                                                 \
+    "s_add_u32 s79, s40, 9\n\t"                                                                   \
+    "s_min_u32 s79, s79, s77\n\t"                                                                 \
+    "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 9)                                      \
+    /* zero-duration job: committed and released before the next decision (D3); one that waited */ \
+    /* (s43 = 2) goes on as a placed head (MCS_FC_ZROUTE) */                                      \
+    "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
+    "v_writelane_b32 v91, s54, m0\n\t"                                                            \
+    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
+    "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
+    "s_cbranch_scc1 mcsfa_zhead_%=\n\t" MCS_FC_RET("s49", 11)                                    \
     /* the clock has moved to a second nothing but its own row's slots, or a misplaced one, can */ \
-    /* have finished by */                                                                        \
+    /* have finished by (no head waits) */                                                        \
     "mcsfa_adv1_%=:\n\t"                                                                          \
     "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 0)                                      \
-    "mcsfa_norel_%=:\n\t" MCS_FC_RET("s49", 1)                                                   \
-    "mcsfa_reltail_%=:\n\t" MCS_FC_RET("s49", 2)                                                 \
-    "mcsfa_inner_%=:\n\t" MCS_FC_RET("s49", 3)                                                   \
-    "mcsfa_ins_%=:\n\t" MCS_FC_RET("s76", 5) /* (s49 is the spill's row) */                      \
-    "mcsfa_nofit_%=:\n\t" MCS_FC_RET("s49", 6)                                                   \
+    "mcsfa_norel_%=:\n\t" MCS_FC_RETW("s49", 1)                                                  \
+    "mcsfa_reltail_%=:\n\t" MCS_FC_RETW("s49", 4)                                                \
+    "mcsfa_inner_%=:\n\t" MCS_FC_RET("s49", 10)                                                  \
+    "mcsfa_ins_%=:\n\t" MCS_FC_RETW("s76", 7) /* (s49 is the spill's row) */                     \
     MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D)                                                     \
-    ".p2align 8\n"                                                                                \
-    "mcsfa_tbl_%=:\n\t" MCS_FC_TBL("blk") MCS_FC_TBL("norel") MCS_FC_TBL("reltail")              \
-    MCS_FC_TBL("inner") MCS_FC_TBL("placed") MCS_FC_TBL("ins") MCS_FC_TBL("nofit") "\n"
+    ".p2align 9\n"                                                                                \
+    "mcsfa_tbl_%=:\n\t" MCS_FC_TBL("blk") MCS_FC_TBL("norel") MCS_FC_TBL("wnorel")               \
+    MCS_FC_TBL1("poolovf") MCS_FC_TBL("reltail") MCS_FC_TBL("wreltail") MCS_FC_TBL1("zreltail") \
+    MCS_FC_TBL("ins") MCS_FC_TBL("wins") MCS_FC_TBL("wblk") MCS_FC_TBL("inner")                  \
+    MCS_FC_TBL("placed") "\n"
 
 // ---- W16S: W16R for clusters of at most 64 nodes (one chunk, node = lane) and 2 slot rows --------
 // (cluster_small / cluster_big: C1-C3).  The fit bit is bit 15 of one SDWA AND; no chunk pick, and

@@ -46,8 +46,16 @@
 //     arrival 0xffffffff where the pass has to end) and keeps no earliest finish, a failed fit sleeps a
 //     second at a time, and an advance of more seconds, or one with a misplaced slot due, scans
 //     every row; a release ends with the head job's fit test; its zero-duration jobs leave the
-//     pass through the arrival test, and it counts a waited job where the placed WaitQueue head is
-//     handled (mcs_fa_macros.h).
+//     pass through the arrival test.  A waiting WaitQueue head runs in a section of its own in each
+//     copy, from the failed fit to its placement: the sleep is a chain of blocks, one per residue
+//     (the clock's add, one compare against min(XMIN, t + 9), the row compare), the release carries
+//     no arrival test, and the placement counts the waited job, reads the next record and sleeps its
+//     second without a test; the single paths come back into the section through the table of
+//     branches (s43 selects the entry), and a waiting zero-duration job stays out of line.  Its
+//     one-second advances carry no overflow branch: the host bounds last arrival + sum(dur + 1)
+//     below 2^32 - 1 for every stream that runs this loop (mcs_submit_jobs, mcs_generate_jobs;
+//     unchecked_horizon streams run the compiled kernel), and a clock at 0xffffffff is still
+//     flagged after the loop (mcs_fa_macros.h).
 //
 // Hazards (wait states are not inserted by the compiler inside asm): DPP reads a VGPR 2 states
 // after its write (s_nop 1), v_readlane reads a VGPR at least 1 instruction after its write, m0
@@ -279,7 +287,10 @@ __device__ unsigned long long g_fa_stamps[4];
 
 #define MCS_FA_LOOP(W, D) MCS_FA_ENTRY_S(W) MCS_FA_BODY(W, D, S) MCS_FA_EXIT_S(W)
 // the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes (eight copies,
-// one per clock residue) and batch-end tail, the shared entry, ends and exit; its clobbers add FREE's upper rows.  It carries no MCS_STAMPS segment clocks
+// one per clock residue, each with its waiting-head section; the sections' sleep chain and the single
+// paths behind them) and batch-end tail, the shared entry, ends and exit (a head still waiting at the exit
+// is s43 != 0); its clobbers add FREE's upper rows; the sections use no register of their own (s79 is the
+// sleep's limit between a failed fit and the head's placement).  It carries no MCS_STAMPS segment clocks
 // (its FREE rows occupy s92-s101, where the stamps live), so the probe build does not expand it and
 // runs this shape on W16; the forms with stamps are W32, W16, W16S and the fused W16R / W16S loops
 #define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, C) MCS_FA_EXIT_S(16C)

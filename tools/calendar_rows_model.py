@@ -10,7 +10,9 @@ completion, and by one second after a placed WaitQueue head), with the slot poli
             t >= XMIN -> the full scan (every row, then XMIN rebuilt), else row t & 7 alone;
             an arrival more than one second on: the full scan (XMIN rebuilt only if t >= XMIN);
   failed    the head steps a second at a time until a step releases something; after eight steps
-  fit       without a release the clock jumps to the exact earliest finish.
+  fit       without a release the clock jumps to the exact earliest finish.  The steps, the release that
+            ends them and the head's placement run in the waiting-head section of the copy (DESIGN.md §4,
+            "The waiting head"; WAIT below holds its counts beside those of the loop before it).
 Printed per job: release scans and what they compared, spills, failed fits and the seconds their sleeps
 cross, the compares that release nothing, the running slots; and the instructions a scan issues, counted
 from the listing of the loop as built (COST below; the pair scan of the loop before it from
@@ -37,9 +39,10 @@ COST = {
     # the advance's XMIN test (2; a branch more from the placed head and an arrival) + the copy's row block
     # with an expiry (4 | 2 | 2) + mcsfa_reltail (7 | 10 | 1)
     "one-row scan": {"scalar": 2 + 4 + 7, "vector": 2 + 10, "lds": 3},
-    # the XMIN test + the block's compare and its branch + mcsfa_norel (2 and the next step's 4 after a failed
-    # fit, the usual case; 2 or 3 else)
-    "empty compare": {"scalar": 2 + 1 + 6, "vector": 1, "lds": 0},
+    # a step of a waiting head's sleep that finds nothing (the usual empty compare): s_add, the limit's compare
+    # and branch, the row's branch; after a placed head or an arrival: the XMIN test (2, a branch more from an
+    # arrival) and the block's branch, mcsfa_norel being empty
+    "empty compare": {"scalar": 4, "vector": 1, "lds": 0},
     # MCS_FC_FULL: the advance's test (2-4) + 8 x (1 | 1) + per expiring row (5 | 1 | 1) + 5 + the computed
     # jump back into the copy (4 and the table's branch) + mcsfa_reltail
     "full scan": {"scalar": 4 + 1 + 8 + 5 * 1.7 + 5 + 5 + 7, "vector": 8 + 1.7 + 10, "lds": 2 + 1.7},
@@ -49,6 +52,23 @@ COST = {
     # for the pairs) + the peak and exec (2) + two instructions of a row's body scalar, two vector, per
     # expiring row (1.63) + the tail's 6 scalar, 4 + 7 vector of the minimum and 10 of the fit test
     "pair scan before": {"scalar": 14.8 + 2 + 2 * 1.63 + 6, "vector": 8 + 2 * 1.63 + 4 + 7 + 10, "lds": 2 + 1.63},
+}
+
+
+# the paths of a waiting WaitQueue head, per event: (scalar and branch, vector) before the waiting-head section
+# and with it, from the two listings.  The step before: s_add, the carry branch, the countdown and its
+# branch, the XMIN test (2), the row's branch; with it: s_add, the limit's compare and branch, the row's branch.
+# The release that ends a sleep: mcsfa_reltail's 7 and mcsfa_fitted's branch before, the section's tail of 6
+# with it.  The placed head: the record read's two tests (4), mcsfa_zarrp (6), the restore (s_nop and two
+# lane accesses), the step with its carry branch (2), the XMIN test and the branch (3); with it: the two
+# counts, s47, the step, the XMIN test (and a branch after copy 7).
+WAIT = {
+    "failed-fit entry": ("failed fits", (6, 1), (7, 0)),
+    "sleep step": ("sleep steps", (7, 1), (4, 1)),
+    "mcsfa_norel after a step on an empty row": ("empty compares: failed fit", (2, 0), (0, 0)),
+    "release that ends a sleep": ("failed fits", (8, 10), (6, 10)),
+    "placed head": ("waited", (17, 5), (7.125, 3)),
+    "mcsfa_norel of the other advances": ("empty compares: other", (2, 0), (0, 0)),
 }
 
 
@@ -117,6 +137,7 @@ def replay(arr, dur, start, finish, st):
                     break
                 t += 1
                 steps += 1
+                st["sleep steps"] += 1
                 if adv1("failed fit"):
                     break
             st["longest sleep"] = max(st["longest sleep"], t - sleep0)
@@ -170,6 +191,11 @@ def main():
                + st["full scans: a misplaced slot is due"] * COST["XMIN rebuild"][f] + emp * COST["empty compare"][f]) / jobs
         old = scans * COST["pair scan before"][f] / jobs
         out.setdefault("clock_advance_instructions_per_job", {})[f] = {"calendar rows": round(new, 2), "pair scan before": round(old, 2)}
+    st["empty compares: other"] = st["empty compares: placed head"] + st["empty compares: arrival"]
+    rows = {k: {"per_job": round(st[n] / jobs, 4), "before": list(b), "with the section": list(a)} for k, (n, b, a) in WAIT.items()}
+    for i, f in enumerate(("scalar", "vector")):
+        rows["change per job: " + f] = round(sum(st[n] * (a[i] - b[i]) for n, b, a in WAIT.values()) / jobs, 2)
+    out["waiting_head_paths"] = rows
     print(json.dumps(out, indent=1))
 
 
