@@ -47,9 +47,9 @@
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
 //                                                                                              s_cmp)
 //  VALU writes VCC -> s_cbranch_vccz/vccnz           0     ANYFIT -> the fit branch; W16C's    (interlocked on gfx9; the pass's
-//                                                          row compare (v_cmp vcc, then        head and the row compare branch
-//                                                          s_cbranch_vccz, copies and scan;    right after the v_cmp)
-//                                                          s_cbranch_vccnz in the sleep chain)
+//                                                          row and LIVE compares (v_cmp vcc,   head and the compares branch
+//                                                          then s_cbranch_vccz / vccnz: copies, right after the v_cmp)
+//                                                          scan, sleep chain, bulk move)
 //  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16C's row
 //                                                                                              blocks: s_mov_b64 exec)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
@@ -58,20 +58,30 @@
 //    soffset)                                              are SALU-written
 //  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16C / COMMIT16 /   (the indexed moves sit between
 //                                                          INSERT16R (none is open in a        on and off; no non-indexed VALU
-//                                                          release scan or its tail)           read inside a region: W16C's spill
-//                                                                                              is scalar and returns before
-//                                                                                              DECIDE16C opens its region)
-//  SALU writes M0 -> s_movrels / s_movreld         1     W16C's insert (FREE[r], m0 = 2r) and   v_readlane + s_lshl_b64 exec between
-//    reads it                                              its spill                           (the spill: s_nop 0); s_movreld
-//                                                                                              follows with m0 untouched
-//  s_set_gpr_idx_on / _idx overwrite M0            -     W16C's insert                       both relative moves come before the
-//                                                                                              region; m0 = the cursor is set
-//                                                                                              after it, as in every form
-//  VALU writes SGPR -> SALU reads it               0     W16C's row compares (vcc -> s_mov   (interlocked)
-//                                                          exec / s_bcnt1 / s_or), the record
-//                                                          read's s45 -> s_cmp
+//                                                          release scan or its tail); W16C's   read inside a region)
+//                                                          surplus insert (MCS_FC_BMOVE_OOL)
+//  SALU writes M0 -> s_movrels / s_movreld         1     W16C's surplus insert at a batch end   s_nop 0 between; s_movreld follows
+//    reads it                                              (FREE[r], m0 = 2r)                  with m0 untouched
+//  s_set_gpr_idx_on overwrites M0                  -     DECIDE16C; W16C's surplus insert     m0 = the cursor is set after the
+//                                                                                              decision's region, as in every
+//                                                                                              form; the surplus insert's relative
+//                                                                                              moves come before its region
+//  VALU writes SGPR -> SALU reads it               0     W16C's row and LIVE compares (vcc   (interlocked)
+//                                                          -> s_mov exec / s_bcnt1 / s_or), the
+//                                                          record read's s45 -> s_cmp, the bulk
+//                                                          move's masks (s[60:61] -> s_bcnt1,
+//                                                          s_and exec)
+//  VALU writes SGPR -> VALU reads it as a constant  0     the bulk move: v_cmp s[60:61] ->     (interlocked; not a lane select)
+//                                                          v_mbcnt / v_cndmask
+//  LDS instruction issued -> its address / data      0     the bulk move: v120 is formed again  (not in the ISA's table of required
+//    VGPRs rewritten                                       right after each ds_read_b128        wait states, whose one row of this
+//                                                          (its address only: a read has no     kind is the VMEM store above; beyond
+//                                                          data VGPRs to be read later)         that it rests on the GPU parity runs
+//                                                                                              of tests/test_gpu_deferred_insert.py's
+//                                                                                              bulk-move cases, which differ per
+//                                                                                              entry in finish, request and node)
 //  s_setpc_b64 to a computed address               -     W16C's MCS_FC_RET / MCS_FC_RETW      the table of branches starts on a
-//                                                                                              512-byte line and is 384 bytes, so
+//                                                                                              512-byte line and is 320 bytes, so
 //                                                                                              s74 + 32 * entry + 4 * (t & 7), with
 //                                                                                              32 * s43 (s43 <= 2) more, never
 //                                                                                              carries into s59
@@ -132,7 +142,8 @@
 //   v118 frm - 1  v120 DPP min / scan temp  v121 address  v[122:123] payload  v124 lane minimum
 //   v125-v127 store temps
 // (W16C, the streamed W16R loop: s49, s[58:59], s74, s77-s79, s82 and s[86:101] have their own
-// meaning, v87 holds a column, v89 and s75 nothing: see "W16C" below)
+// meaning, v87 holds a column, v106 the LIVE column, v89 nothing, s75 and v56-v63, v102-v105 are the bulk
+// move's: see "W16C" below)
 #define MCS_FA_CLOBBERS                                                                            \
     "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53",  \
         "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",     \
@@ -519,14 +530,21 @@
 // insert).  Invariant, after the clock has been handled at second t: no slot has finish <= t; every
 // slot sits in row finish & 7 but the misplaced ones (their row was full: they took the next row with
 // a free lane); XMIN (s77) <= the earliest finish of any misplaced slot, 0xffffffff when there is none.
-// The free slots are scalar lane masks, one per row, so an insert finds its lane with scalar
-// instructions only (no v_cmp / v_ffbl / v_readlane of a free-row column, and the fit test carries none).
-//   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), read and written by the
-//             insert with s_movrels/s_movreld (m0 = 2r), by a release as static registers
+// The free slots are scalar lane masks, one per row.  A placement takes no slot: the job stays in its
+// batch lane, its finish in the LIVE column v106 (-1 in every lane without a running job of the current
+// batch), its node in v91 and its request in v96 as the result batch and the records hold them anyway.
+// Whatever compares a calendar row against t compares LIVE first (the copies' row blocks, the sleep chain,
+// the full scan as a ninth row, the exact minimum); a lane that expires hands its request back out of line
+// (MCS_FC_BREL).  At the batch end the live lanes go into their rows together (MCS_FC_BMOVE), so the
+// invariant above holds for the slots, and for LIVE: no lane has finish <= t.  A batch-lane job is compared
+// every second and is never misplaced: XMIN knows nothing of it.
+//   s[86:101] FREE[0..7]: the free lanes of each row (row r: s[86+2r:87+2r]), static registers for a release
+//             and the bulk move, s_movrels/s_movreld (m0 = 2r) for a surplus job's insert
 //   s77 XMIN   s74, s59 the address of the copies' table of branches (MCS_FC_RET; on a 512-byte line),
-//   low and high word   s[58:59] a computed jump's target   s[60:61] the insert's FREE[r], s[50:51] without
-//   the lane handed out   s49 r / a computed jump's t & 7 / the full scan's released count   s79 the node
-//   address of the insert; the limit of a waiting head's sleep, min(XMIN, t + 9)   s43 1 while a head waits in
+//   low and high word   s[58:59] a computed jump's target   s49 a computed jump's t & 7 / the full scan's
+//   released count / a batch-lane release's row count   s79 the limit of a waiting head's sleep,
+//   min(XMIN, t + 9)   s[50:55], s[60:63], s75, s85: the decision's pick (s50-s54) and the bulk move's
+//   temporaries   s43 1 while a head waits in
 //   a copy's section, 2 while a zero-duration job waits out of line, else 0   s41 min(64, J - cb), read where a
 //   batch is taken only   v89, v90, v107 the record columns shifted by one lane (MCS_FC_SHIFT)   m0 after a
 //   placement: the lane of the job placed, the record read's lane select
@@ -546,12 +564,12 @@
 // waiting-head section (each step the row compare and one test against min(XMIN, t + 9): MCS_FC_COPY,
 // MCS_FC_WSL); after eight steps without a release every row has been compared, and the clock jumps to the
 // exact earliest finish (lane-minimum tree + DPP, as every other form's scan end).  Nothing running
-// is s80 == 0.  A release scan is counted where something is released (mcsfa_reltail, mcsfa_wreltail,
-// mcsfa_zreltail).
-// Hazards (table above): m0 is written two instructions before s_movrels reads it (one wait state
-// needed) and nothing writes it before s_movreld; s_set_gpr_idx_on / _idx overwrite m0, so both
-// relative moves come before the region, and m0 = the cursor is set after it as in every form; the
-// row compare writes vcc, which s_cbranch_vccz and SALU read (interlocked); the DPP chains keep s_nop 1.
+// is s80 == 0 (the count of the slots and the live lanes).  A release scan is counted where something is
+// released, from a row, from the batch lanes or from both (mcsfa_reltail, mcsfa_wreltail, mcsfa_zreltail).
+// Hazards (table above): s_set_gpr_idx_on overwrites m0, so m0 = the cursor is set after the decision's
+// region as in every form; the row and LIVE compares write vcc, which s_cbranch_vccz / vccnz and SALU read
+// (interlocked); the DPP chains keep s_nop 1; the surplus insert of the bulk move keeps the per-job
+// insert's distances (s_nop 0 between m0 and s_movrels, both relative moves before its region).
 //
 // The fit test is MCS_FA_FIT16 without the insert's free-row lanes: the pass's finish (s_add s55) is
 // the instruction between the last SDWA-preserve write and the v_perm (hazard table, row 2).
@@ -662,61 +680,180 @@
     "v_mov_b32 v36, -1\n\t"                                                                      \
     "v_mov_b32 v37, -1\n\t"                                                                      \
     "v_mov_b32 v38, -1\n\t"                                                                      \
-    "v_mov_b32 v39, -1\n\t"
-// MCS_FA_DECIDE16R's single register-index region; the slot is the lowest free lane of row
-// r = finish & 7 (s_ff1 of an empty FREE[r] is -1: the shift then gives a bit the AND drops, SCC of
-// the AND = a slot exists; none: the spill, out of line); L names the label the spill returns to: "ins"
-// in a copy's pass, "wins" in its waiting-head section
-#define MCS_FA_DECIDE16C(L, k)                                                                    \
-    "s_and_b32 s49, s55, 7\n\t"                                                                   \
-    "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
+    "v_mov_b32 v39, -1\n\t"                                                                      \
+    "v_mov_b32 v106, -1\n\t" /* LIVE: no job of the batch is running */
+// The decision is the pick and the commit alone (MCS_FA_DECIDE16R's chunk move in its register-index
+// region): a placed job takes no slot.  It stays in its batch lane, its finish in the LIVE column v106
+// (written beside the two result writes; -1 in every other lane), until it finishes there or the batch
+// ends and the live lanes go into their calendar rows together (MCS_FC_BMOVE).
+#define MCS_FA_DECIDE16C                                                                          \
     "v_readlane_b32 s51, v86, s50\n\t"                                                            \
     "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
-    "s_movrels_b64 s[60:61], s[86:87]\n\t" /* FREE[r] */                                         \
     "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
-    "s_ff1_i32_b64 s85, s[60:61]\n\t"                                                             \
     "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
-    "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
     "s_lshl2_add_u32 s54, s50, s53\n\t" /* kx = the node index, lane * 4 + chunk */             \
-    "s_andn2_b64 s[50:51], s[60:61], s[62:63]\n\t" /* (s50, s51 are done) */                    \
-    "s_and_b64 s[62:63], s[62:63], s[60:61]\n\t"                                                  \
-    "s_cbranch_scc0 mcsfa_sp_%=\n\t"                                                              \
-    "s_movreld_b64 s[86:87], s[50:51]\n" /* the slot is handed out */                            \
-    "mcsfa_" L #k "_%=:\n\t"                                                                      \
     "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
     "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
-    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
-    "s_lshl2_add_u32 s79, s54, s73\n\t"                                                           \
-    "s_set_gpr_idx_idx s49\n\t"                                                                   \
-    "v_mov_b32 v32, s55\n\t" /* the slot: finish, payload, node address (SGPR sources) */        \
-    "v_mov_b32 v40, s48\n\t"                                                                      \
-    "v_mov_b32 v48, s79\n\t"                                                                      \
     "s_set_gpr_idx_off\n\t"
-// the spill (out of line; returns to mcsfa_ins with s49 the row, s[62:63] the lane's mask): the first
-// row r+1 ... r+7 (mod 8) with a free lane, XMIN = min(XMIN, finish); none: the pool is full, the
-// insert runs under an empty exec (peak > 64*8 at the batch end, as W16R)
-#define MCS_FC_SPILL                                                                              \
-    "mcsfa_sp_%=:\n\t"                                                                            \
-    "s_and_b32 s76, s55, 7\n"                                                                     \
-    "mcsfa_spl_%=:\n\t"                                                                           \
+// a batch-lane release (out of line; vcc = the lanes of LIVE that finish by t, not empty): the LDS node
+// copy is refreshed, the requests (v96) go back to the nodes (base + 4 * v91) and the lanes leave LIVE;
+// then the calendar row of the second, with its body if it expires; s76 = the count of both, and into
+// the tail TAIL of the copy or of its waiting-head section.  P prefixes the labels.
+#define MCS_FC_BREL(P, k, F, PAY, A, FREE, TAIL)                                                  \
+    "mcsfa_" P #k "_%=:\n\t"                                                                      \
+    "ds_write_b128 v108, v[64:67]\n\t"                                                           \
+    "s_mov_b64 exec, vcc\n\t"                                                                     \
+    "s_bcnt1_i32_b64 s76, vcc\n\t"                                                               \
+    "v_lshl_add_u32 v121, v91, 2, v109\n\t"                                                      \
+    "ds_add_u32 v121, v96\n\t"                                                                    \
+    "v_mov_b32 v106, -1\n\t"                                                                      \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
+    "s_cbranch_vccz mcsfa_" TAIL #k "_%=\n\t"                                                     \
+    "s_mov_b64 exec, vcc\n\t"                                                                     \
+    "s_bcnt1_i32_b64 s49, vcc\n\t"                                                               \
+    "ds_add_u32 " A ", " PAY "\n\t"                                                             \
+    "v_mov_b32 " F ", -1\n\t"                                                                    \
+    "s_or_b64 " FREE ", " FREE ", vcc\n\t"                                                       \
+    "s_add_u32 s76, s76, s49\n\t"                                                                 \
+    "s_branch mcsfa_" TAIL #k "_%=\n"
+// The bulk move at the batch end (after the result stores, before the columns are recycled): the lanes
+// with LIVE != -1 go to row LIVE & 7, each row's candidates matched to its free lanes by rank.  The
+// candidates are numbered row after row (v_mbcnt on the row's candidate mask, on top of the rows before:
+// O[r] in s50-s55, s62, s63 is the count of rows 0 .. r) and write {finish, request, node address} to
+// the 16-byte entry of their number in the LDS scratch behind the node words (base + 1024); free lane
+// number j of row r reads entry O[r-1] + j while that is below O[r] (eight reads, one wait; a lane that
+// reads nothing keeps -1 in the word the finish lands in) and takes it into the row's registers.  A row
+// with more candidates than free lanes (out of line, mcsfa_bmo<r>) marks the ones beyond in s[46:47];
+// they go one at a time, as a per-job insert did, to the first row r+1 ... r+7 (mod 8) with a free lane,
+// XMIN = min(XMIN, finish).  The pool cannot be short: the batch end has left on peak > 64*8, and below
+// that the free slots are at least the live lanes (a row search that comes round is a pool overflow all
+// the same).  Temporaries: s[46:49] (set again by the batch take), s49, s75, s76, s79, s85, s[50:55],
+// s[60:63], v112-v115, v120-v123 and the read quads v[56:63], v[68:79], v[82:85], v[102:105], v[124:127].
+#define MCS_FC_BMA(r, OP, ON, FREE)                                                               \
+    "v_cmp_eq_u32_e64 s[60:61], " #r ", v122\n\t"                                                 \
+    "s_bcnt1_i32_b64 s76, s[60:61]\n\t"                                                           \
+    "v_mbcnt_lo_u32_b32 v120, s60, v121\n\t"                                                      \
+    "s_bcnt1_i32_b64 s75, " FREE "\n\t"                                                           \
+    "v_mbcnt_hi_u32_b32 v120, s61, v120\n\t"                                                      \
+    "s_add_u32 " ON ", " OP ", s76\n\t"                                                           \
+    "v_cndmask_b32_e64 v123, v123, v120, s[60:61]\n\t"                                            \
+    "s_cmp_gt_u32 s76, s75\n\t"                                                                   \
+    "s_cbranch_scc1 mcsfa_bmo" #r "_%=\n"                                                         \
+    "mcsfa_bmr" #r "_%=:\n\t"                                                                     \
+    "v_mov_b32 v121, " ON "\n\t"
+// (row r's candidates beyond its free lanes: number >= O[r-1] + the free lanes)
+#define MCS_FC_BMO(r, OP)                                                                         \
+    "mcsfa_bmo" #r "_%=:\n\t"                                                                     \
+    "s_add_u32 s75, s75, " OP "\n\t"                                                              \
+    "v_cmp_le_u32_e32 vcc, s75, v120\n\t"                                                         \
+    "s_and_b64 vcc, vcc, s[60:61]\n\t"                                                            \
+    "s_or_b64 s[46:47], s[46:47], vcc\n\t"                                                        \
+    "s_branch mcsfa_bmr" #r "_%=\n"
+#define MCS_FC_BMB(OP, ON, FREELO, FREEHI, FREE, Q)                                               \
+    "v_mov_b32 v121, " OP "\n\t"                                                                  \
+    "v_mbcnt_lo_u32_b32 v120, " FREELO ", v121\n\t"                                               \
+    "v_mbcnt_hi_u32_b32 v120, " FREEHI ", v120\n\t"                                               \
+    "v_cmp_gt_u32_e64 s[60:61], " ON ", v120\n\t"                                                 \
+    "v_lshl_add_u32 v120, v120, 4, v109\n\t"                                                      \
+    "s_and_b64 exec, s[60:61], " FREE "\n\t"                                                      \
+    "ds_read_b128 " Q ", v120 offset:1024\n\t"                                                    \
+    "s_andn2_b64 " FREE ", " FREE ", exec\n\t"                                                    \
+    "s_mov_b64 exec, -1\n\t"
+#define MCS_FC_BMC(Q0, Q1, Q2, F, P, A)                                                           \
+    "v_cmp_ne_u32_e32 vcc, -1, " Q0 "\n\t"                                                        \
+    "v_cndmask_b32_e32 " F ", " F ", " Q0 ", vcc\n\t"                                             \
+    "v_cndmask_b32_e32 " P ", " P ", " Q1 ", vcc\n\t"                                             \
+    "v_cndmask_b32_e32 " A ", " A ", " Q2 ", vcc\n\t"
+#define MCS_FC_BMOVE                                                                              \
+    "v_cmp_ne_u32_e32 vcc, -1, v106\n\t"                                                          \
+    "s_cbranch_vccz mcsfa_bmx_%=\n\t"                                                             \
+    "v_and_b32 v122, 7, v106\n\t"                                                                 \
+    "s_mov_b64 s[48:49], vcc\n\t" /* the live lanes */                                           \
+    "v_cndmask_b32_e32 v122, 8, v122, vcc\n\t" /* the lane's row; 8: none */                     \
+    "s_mov_b64 s[46:47], 0\n\t"                                                                   \
+    "v_mov_b32 v112, v106\n\t"                                                                    \
+    "v_mov_b32 v113, v96\n\t"                                                                     \
+    "v_lshl_add_u32 v114, v91, 2, v109\n\t"                                                       \
+    "v_mov_b32 v121, 0\n\t"                                                                       \
+    MCS_FC_BMA(0, "0", "s50", "s[86:87]") MCS_FC_BMA(1, "s50", "s51", "s[88:89]")                 \
+    MCS_FC_BMA(2, "s51", "s52", "s[90:91]") MCS_FC_BMA(3, "s52", "s53", "s[92:93]")               \
+    MCS_FC_BMA(4, "s53", "s54", "s[94:95]") MCS_FC_BMA(5, "s54", "s55", "s[96:97]")               \
+    MCS_FC_BMA(6, "s55", "s62", "s[98:99]") MCS_FC_BMA(7, "s62", "s63", "s[100:101]")             \
+    "s_mov_b64 exec, s[48:49]\n\t"                                                                \
+    "v_lshl_add_u32 v123, v123, 4, v109\n\t"                                                      \
+    "ds_write_b128 v123, v[112:115] offset:1024\n\t"                                              \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "v_mov_b32 v56, -1\n\t"                                                                       \
+    "v_mov_b32 v60, -1\n\t"                                                                       \
+    "v_mov_b32 v68, -1\n\t"                                                                       \
+    "v_mov_b32 v72, -1\n\t"                                                                       \
+    "v_mov_b32 v76, -1\n\t"                                                                       \
+    "v_mov_b32 v82, -1\n\t"                                                                       \
+    "v_mov_b32 v102, -1\n\t"                                                                      \
+    "v_mov_b32 v124, -1\n\t"                                                                      \
+    MCS_FC_BMB("0", "s50", "s86", "s87", "s[86:87]", "v[56:59]")                                  \
+    MCS_FC_BMB("s50", "s51", "s88", "s89", "s[88:89]", "v[60:63]")                                \
+    MCS_FC_BMB("s51", "s52", "s90", "s91", "s[90:91]", "v[68:71]")                                \
+    MCS_FC_BMB("s52", "s53", "s92", "s93", "s[92:93]", "v[72:75]")                                \
+    MCS_FC_BMB("s53", "s54", "s94", "s95", "s[94:95]", "v[76:79]")                                \
+    MCS_FC_BMB("s54", "s55", "s96", "s97", "s[96:97]", "v[82:85]")                                \
+    MCS_FC_BMB("s55", "s62", "s98", "s99", "s[98:99]", "v[102:105]")                              \
+    MCS_FC_BMB("s62", "s63", "s100", "s101", "s[100:101]", "v[124:127]")                          \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
+    MCS_FC_BMC("v56", "v57", "v58", "v32", "v40", "v48")                                          \
+    MCS_FC_BMC("v60", "v61", "v62", "v33", "v41", "v49")                                          \
+    MCS_FC_BMC("v68", "v69", "v70", "v34", "v42", "v50")                                          \
+    MCS_FC_BMC("v72", "v73", "v74", "v35", "v43", "v51")                                          \
+    MCS_FC_BMC("v76", "v77", "v78", "v36", "v44", "v52")                                          \
+    MCS_FC_BMC("v82", "v83", "v84", "v37", "v45", "v53")                                          \
+    MCS_FC_BMC("v102", "v103", "v104", "v38", "v46", "v54")                                       \
+    MCS_FC_BMC("v124", "v125", "v126", "v39", "v47", "v55")                                       \
+    "s_cmp_lg_u64 s[46:47], 0\n\t"                                                                \
+    "s_cbranch_scc1 mcsfa_bml_%=\n"                                                               \
+    "mcsfa_bmd_%=:\n\t"                                                                           \
+    "v_mov_b32 v106, -1\n"                                                                        \
+    "mcsfa_bmx_%=:\n\t"
+// the out-of-line parts of the bulk move (behind the batch end's closing branch): the rows' surplus
+// marks and the one-at-a-time insert of the jobs marked (s[46:47], not empty)
+#define MCS_FC_BMOVE_OOL                                                                          \
+    MCS_FC_BMO(0, "0") MCS_FC_BMO(1, "s50") MCS_FC_BMO(2, "s51") MCS_FC_BMO(3, "s52")             \
+    MCS_FC_BMO(4, "s53") MCS_FC_BMO(5, "s54") MCS_FC_BMO(6, "s55") MCS_FC_BMO(7, "s62")           \
+    "mcsfa_bml_%=:\n\t"                                                                           \
+    "s_ff1_i32_b64 s52, s[46:47]\n\t"                                                             \
+    "s_lshl_b64 s[60:61], 1, s52\n\t"                                                             \
+    "v_readlane_b32 s55, v106, s52\n\t" /* finish */                                             \
+    "v_readlane_b32 s48, v96, s52\n\t"  /* request */                                            \
+    "v_readlane_b32 s54, v91, s52\n\t"  /* node */                                               \
+    "s_andn2_b64 s[46:47], s[46:47], s[60:61]\n\t"                                                \
+    "s_and_b32 s76, s55, 7\n\t"                                                                   \
+    "s_mov_b32 s49, s76\n"                                                                        \
+    "mcsfa_bms_%=:\n\t"                                                                           \
     "s_add_u32 s49, s49, 1\n\t"                                                                   \
     "s_and_b32 s49, s49, 7\n\t"                                                                   \
     "s_cmp_eq_u32 s49, s76\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_spf_%=\n\t"                                                             \
+    "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_lshl_b32 m0, s49, 1\n\t"                                                                   \
     "s_nop 0\n\t"                                                                                 \
     "s_movrels_b64 s[60:61], s[86:87]\n\t"                                                        \
     "s_cmp_lg_u64 s[60:61], 0\n\t"                                                                \
-    "s_cbranch_scc0 mcsfa_spl_%=\n\t"                                                             \
+    "s_cbranch_scc0 mcsfa_bms_%=\n\t"                                                             \
     "s_ff1_i32_b64 s85, s[60:61]\n\t"                                                             \
     "s_lshl_b64 s[62:63], 1, s85\n\t"                                                             \
     "s_andn2_b64 s[50:51], s[60:61], s[62:63]\n\t"                                                \
     "s_movreld_b64 s[86:87], s[50:51]\n\t"                                                        \
     "s_min_u32 s77, s77, s55\n\t"                                                                 \
-    "s_branch mcsfa_ins_%=\n"                                                                     \
-    "mcsfa_spf_%=:\n\t"                                                                           \
-    "s_mov_b64 s[62:63], 0\n\t"                                                                   \
-    "s_branch mcsfa_ins_%=\n"
+    "s_lshl2_add_u32 s79, s54, s73\n\t"                                                           \
+    "s_mov_b64 exec, s[62:63]\n\t"                                                                \
+    "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
+    "v_mov_b32 v32, s55\n\t"                                                                      \
+    "v_mov_b32 v40, s48\n\t"                                                                      \
+    "v_mov_b32 v48, s79\n\t"                                                                      \
+    "s_set_gpr_idx_off\n\t"                                                                       \
+    "s_mov_b64 exec, -1\n\t"                                                                      \
+    "s_cmp_lg_u64 s[46:47], 0\n\t"                                                                \
+    "s_cbranch_scc1 mcsfa_bml_%=\n\t"                                                             \
+    "s_branch mcsfa_bmd_%=\n"
 // the wave's minimum of v120 into an SGPR (MCS_FA_SCANEND's chain)
 #define MCS_FC_WMIN(DST)                                                                          \
     "s_nop 1\n\t"                                                                                 \
@@ -759,6 +896,17 @@
     MCS_FC_FROW(2, "v34", "v42", "v50", "s[90:91]") MCS_FC_FROW(3, "v35", "v43", "v51", "s[92:93]") \
     MCS_FC_FROW(4, "v36", "v44", "v52", "s[94:95]") MCS_FC_FROW(5, "v37", "v45", "v53", "s[96:97]") \
     MCS_FC_FROW(6, "v38", "v46", "v54", "s[98:99]") MCS_FC_FROW(7, "v39", "v47", "v55", "s[100:101]") \
+    /* the ninth row: the batch lanes (LIVE), their requests back to the nodes base + 4 * v91 */  \
+    "v_cmp_ge_u32_e32 vcc, s40, v106\n\t"                                                        \
+    "s_cbranch_vccz mcsfa_fr8_%=\n\t"                                                            \
+    "s_mov_b64 exec, vcc\n\t"                                                                    \
+    "s_bcnt1_i32_b64 s76, vcc\n\t"                                                              \
+    "v_lshl_add_u32 v121, v91, 2, v109\n\t"                                                     \
+    "ds_add_u32 v121, v96\n\t"                                                                   \
+    "v_mov_b32 v106, -1\n\t"                                                                     \
+    "s_add_u32 s49, s49, s76\n\t"                                                                \
+    "s_mov_b64 exec, -1\n"                                                                       \
+    "mcsfa_fr8_%=:\n\t"                                                                          \
     "s_cmp_lt_u32 s40, s77\n\t" /* no misplaced slot was due: XMIN stands */                    \
     "s_cbranch_scc1 mcsfa_fx_%=\n\t"                                                              \
     "v_mov_b32 v120, -1\n\t"                                                                      \
@@ -770,12 +918,13 @@
     "s_cmp_eq_u32 s49, 0\n\t"                                                                     \
     "s_cbranch_scc1 mcsfa_norel_%=\n\t"                                                           \
     "s_branch mcsfa_reltail_%=\n"
-// every running slot's earliest finish into s76 (lane-minimum tree + DPP; free slots hold -1)
+// every running job's earliest finish into s76, the batch lanes' (LIVE) with the slots' (lane-minimum
+// tree + DPP; free slots and lanes hold -1)
 #define MCS_FC_EXACTMIN                                                                           \
     "v_min3_u32 v121, v32, v33, v34\n\t"                                                         \
     "v_min3_u32 v121, v121, v35, v36\n\t"                                                        \
     "v_min3_u32 v121, v121, v37, v38\n\t"                                                        \
-    "v_min3_u32 v120, v121, v39, v39\n\t" MCS_FC_WMIN("s76")
+    "v_min3_u32 v120, v121, v39, v106\n\t" MCS_FC_WMIN("s76")
 // the zero route (out of line, from mcsfa_arrive): the true arrival's test and the sleep to it, or the
 // fit test and mcsfa_zero.  A zero-duration job that fits nowhere waits out of line as well
 // (mcsfa_znofit, s43 = 2; 1 in 600 jobs has zero duration and few of those wait, so the copies' waiting-
@@ -814,7 +963,7 @@
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_cmp_eq_u32 s80, 0\n\t" /* nothing running */                                              \
     "s_cbranch_scc1 mcsfa_deadlock_%=\n\t" MCS_FC_EXACTMIN                                        \
-    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
+    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot or a live lane: flagged) */            \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_max_u32 s40, s40, s76\n\t"                                                                 \
     "s_branch mcsfa_full_%=\n"                                                                    \
@@ -834,9 +983,9 @@
 // t & 7, whose row block compares its row's registers, named in the text.  Whatever advances the clock by
 // one second goes on at the next copy's row block: the placed WaitQueue head's sleep falls through into it,
 // an arrival one second on branches there; only the XMIN test stays at the advance.  The paths that set the clock to any second, or that all copies share (the full scan, the
-// exact-minimum fallback, the batch end, the spill, the zero route), are single and come back through a
+// exact-minimum fallback, the batch end with its bulk move, the zero route), are single and come back through a
 // table of branches, eight per entry point (MCS_FC_RET: s74 + 32 * entry + 4 * (t & 7), the table on a
-// 512-byte line and 384 bytes long, so the sum never carries).  The padding in front of a copy's
+// 512-byte line and 320 bytes long, so the sum never carries).  The padding in front of a copy's
 // mcsfa_norel lies behind an unconditional branch and is never run; it puts the pass's head (mcsfa_fit)
 // 16 bytes into a 64-byte line, the position MCS_FA_HEAD16C kept for the single loop.
 //
@@ -853,7 +1002,7 @@
 // (the guard counts, the limit is formed again).  The head's placement is the pass's decision and
 // result writes, then without a test: it is counted as waited, s43 = 0, the next job's record, the
 // one-second sleep (:250), the XMIN test, and the next copy's ordinary row block.  The single paths a
-// waiting head can take (the full scan, the spill) return through MCS_FC_RETW, whose table entry is
+// waiting head can take (the full scan) return through MCS_FC_RETW, whose table entry is
 // e + s43: the waiting head's entry follows the ordinary one, a waiting zero-duration job's (s43 = 2,
 // MCS_FC_ZROUTE) that one.
 // The one-second advances carry no overflow branch: the host bounds last arrival + sum(dur + 1) below
@@ -861,7 +1010,7 @@
 // runs the compiled kernel), and no clock of the run exceeds that sum; a clock that did reach
 // 0xffffffff is still flagged after the loop (fifo_asm_kernel).
 // Table entries: 0 blk, 1 norel, 2 wnorel, 3 (zero job, no release: cannot be, flagged), 4 reltail,
-// 5 wreltail, 6 zreltail, 7 ins, 8 wins, 9 wblk, 10 inner, 11 placed.
+// 5 wreltail, 6 zreltail, 7 wblk, 8 inner, 9 placed.
 #define MCS_FC_RET(TMP, e)                                                                        \
     "s_and_b32 " TMP ", s40, 7\n\t"                                                               \
     "s_lshl2_add_u32 s58, " TMP ", s74\n\t"                                                       \
@@ -902,6 +1051,8 @@
     /* the row against t; an expiry refreshes the LDS node copy under the full wave, then hands */ \
     /* the payloads back under exec = the expiry mask (vcc) and falls into the tail */           \
     "mcsfa_blk" #k "_%=:\n\t"                                                                     \
+    "v_cmp_ge_u32_e32 vcc, s40, v106\n\t" /* the batch lanes (LIVE): a release out of line */   \
+    "s_cbranch_vccnz mcsfa_brel" #k "_%=\n\t"                                                     \
     "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
     "s_cbranch_vccz mcsfa_norel" #k "_%=\n\t"                                                     \
     "ds_write_b128 v108, v[64:67]\n\t"                                                           \
@@ -946,12 +1097,13 @@
     "mcsfa_fitted" #k "_%=:\n\t" /* (a release enters here, the fit test done in its tail) */    \
     "s_cbranch_vccz mcsfa_nofit" #k "_%=\n\t"                                                     \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
-    MCS_FA_DECIDE16C("ins", k)                                                                    \
+    MCS_FA_DECIDE16C                                                                              \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n"                                                              \
+    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
+    "v_writelane_b32 v106, s55, m0\n" /* LIVE: the job runs in its batch lane */                                                              \
     /* next ready job */                                                                          \
     /* (m0 = the lane of the job just placed; no next job in the batch and a zero-duration one */ \
     /* both read as the arrival 0xffffffff: one bottom test) */                                   \
@@ -973,6 +1125,8 @@
     "s_cmp_eq_u32 s45, -1\n\t" /* 0xffffffff: a zero-duration job, or no job: out of line */      \
     "s_cbranch_scc1 mcsfa_zarr_%=\n\t"                                                            \
     "s_branch mcsfa_arr2" #k "_%=\n"                                                              \
+    /* ---- the batch-lane releases of the row block and of the section's sleep (out of line) ---- */ \
+    MCS_FC_BREL("brel", k, F, P, A, FREE, "reltail") MCS_FC_BREL("wbrel", k, F, P, A, FREE, "wreltail") \
     /* ---- the copy's waiting-head section (after the copy's text; entered by branches only) ---- */ \
     /* no node fits: the head waits (s43 = 1) and sleeps to the next completion, a second at a */ \
     /* time up to the limit s79 = min(XMIN, t + 9), in the chain of sleep blocks (MCS_FC_WSL) */   \
@@ -1010,12 +1164,13 @@
     /* waited, the next job's record is read (m0 = the head's lane), and the head sleeps a */    \
     /* second (:250) into the next copy's ordinary row block */                                  \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
-    MCS_FA_DECIDE16C("wins", k)                                                                   \
+    MCS_FA_DECIDE16C                                                                              \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
     "v_writelane_b32 v92, s40, m0\n\t"                                                            \
+    "v_writelane_b32 v106, s55, m0\n\t"                                                            \
     "s_add_u32 s82, s82, 1\n\t"                                                                   \
     "s_mov_b32 s43, 0\n\t" MCS_FC_RECNEXT                                                        \
     "s_add_u32 s47, s47, 1\n\t"                                                                   \
@@ -1031,6 +1186,8 @@
     "s_cmp_ge_u32 s40, s79\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_wslow_%=\n"                                                             \
     "mcsfa_wblk" #k "_%=:\n\t"                                                                    \
+    "v_cmp_ge_u32_e32 vcc, s40, v106\n\t"                                                        \
+    "s_cbranch_vccnz mcsfa_wbrel" #k "_%=\n\t"                                                    \
     "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
     "s_cbranch_vccnz mcsfa_wrel" #k "_%=\n"
 // the passes of this form (mcs_fifo_asm.hip's MCS_FA_PASS, with its own clock advances): the entry goes
@@ -1057,20 +1214,20 @@
     "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
     "s_cbranch_scc1 mcsfa_full_%=\n"                                                              \
     "mcsfa_exact_%=:\n\t" MCS_FC_EXACTMIN                                                         \
-    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot: an insert was skipped) */             \
+    "s_cmp_eq_u32 s76, -1\n\t" /* (a count without a slot or a live lane: flagged) */            \
     "s_cbranch_scc1 mcsfa_poolovf_%=\n\t"                                                         \
     "s_max_u32 s40, s40, s76\n\t"                                                                 \
     "s_add_u32 s79, s40, 9\n\t"                                                                   \
     "s_min_u32 s79, s79, s77\n\t"                                                                 \
     "s_cmp_ge_u32 s40, s77\n\t"                                                                   \
-    "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 9)                                      \
+    "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 7)                                      \
     /* zero-duration job: committed and released before the next decision (D3); one that waited */ \
     /* (s43 = 2) goes on as a placed head (MCS_FC_ZROUTE) */                                      \
     "mcsfa_zero_%=:\n\t" MCS_FA_ZEROKX16C                                                        \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
     "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "s_cmp_lg_u32 s43, 0\n\t"                                                                     \
-    "s_cbranch_scc1 mcsfa_zhead_%=\n\t" MCS_FC_RET("s49", 11)                                    \
+    "s_cbranch_scc1 mcsfa_zhead_%=\n\t" MCS_FC_RET("s49", 9)                                    \
     /* the clock has moved to a second nothing but its own row's slots, or a misplaced one, can */ \
     /* have finished by (no head waits) */                                                        \
     "mcsfa_adv1_%=:\n\t"                                                                          \
@@ -1078,14 +1235,12 @@
     "s_cbranch_scc1 mcsfa_full_%=\n\t" MCS_FC_RET("s49", 0)                                      \
     "mcsfa_norel_%=:\n\t" MCS_FC_RETW("s49", 1)                                                  \
     "mcsfa_reltail_%=:\n\t" MCS_FC_RETW("s49", 4)                                                \
-    "mcsfa_inner_%=:\n\t" MCS_FC_RET("s49", 10)                                                  \
-    "mcsfa_ins_%=:\n\t" MCS_FC_RETW("s76", 7) /* (s49 is the spill's row) */                     \
-    MCS_FC_FULL MCS_FC_SPILL MCS_FC_ZROUTE(D)                                                     \
+    "mcsfa_inner_%=:\n\t" MCS_FC_RET("s49", 8)                                                  \
+    MCS_FC_FULL MCS_FC_ZROUTE(D)                                                     \
     ".p2align 9\n"                                                                                \
     "mcsfa_tbl_%=:\n\t" MCS_FC_TBL("blk") MCS_FC_TBL("norel") MCS_FC_TBL("wnorel")               \
     MCS_FC_TBL1("poolovf") MCS_FC_TBL("reltail") MCS_FC_TBL("wreltail") MCS_FC_TBL1("zreltail") \
-    MCS_FC_TBL("ins") MCS_FC_TBL("wins") MCS_FC_TBL("wblk") MCS_FC_TBL("inner")                  \
-    MCS_FC_TBL("placed") "\n"
+    MCS_FC_TBL("wblk") MCS_FC_TBL("inner") MCS_FC_TBL("placed") "\n"
 
 // ---- W16S: W16R for clusters of at most 64 nodes (one chunk, node = lane) and 2 slot rows --------
 // (cluster_small / cluster_big: C1-C3).  The fit bit is bit 15 of one SDWA AND; no chunk pick, and

@@ -27,10 +27,12 @@
 //     ANDed back with them); a full pool leaves exec empty and is caught by peak > 64*P at the
 //     batch end (the cluster is re-run with a bigger pool by the engine, as for the compiled
 //     kernel).  The counters (used, peak, waited, passes) are scalar.  The streamed W16R loop keeps
-//     calendar rows instead (W16C, mcs_fa_macros.h): a slot goes to row finish & 7, the lowest lane
-//     of that row's free-lane mask (eight 64-bit masks in SGPRs, read and written with
-//     s_movrels / s_movreld), or when that row is full to the next row with a free lane, with the
-//     same full-pool rule.
+//     calendar rows instead (W16C, mcs_fa_macros.h), and a placement there takes no slot at all: the
+//     job stays in its batch lane (its finish in a LIVE column, compared at every clock advance beside
+//     the calendar row) until it finishes there or the batch ends; then the live lanes go to row
+//     finish & 7 together, each row's candidates to the free lanes of its mask (eight 64-bit masks in
+//     SGPRs) by rank through a 1 KiB LDS scratch, and a row's surplus one at a time to the next row with
+//     a free lane; the pool is never short there, the batch end having left on peak > 64*P before.
 //   * The cursor's lane in the batch lives in m0 for the result batch writes (v_writelane) and
 //     in s47 for the record broadcasts (v_readlane).
 //   * Release at a clock advance: every slot row's expiry lane mask is computed before the first
@@ -242,8 +244,11 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_mov_b32 s47, 0\n\t" MCS_FA_REC##W MCS_FA_T1("s96")                                         \
     "s_branch mcsfa_inner_%=\n"
 // the streamed W16R loop (W16C): the same, with the batch's bound known before the records are taken
-// (MCS_FC_SHIFT marks the lanes without a job and builds the shifted record columns)
+// (MCS_FC_SHIFT marks the lanes without a job and builds the shifted record columns); before the columns
+// are recycled, the batch's live lanes go into their calendar rows (MCS_FC_BMOVE; its out-of-line parts
+// follow the closing branch).  The exit at the stream's end comes before it and moves nothing.
 #define MCS_FA_BENDTAIL_C(W)                                                                      \
+    MCS_FC_BMOVE                                                                                  \
     "s_sub_u32 s41, s42, s57\n\t"                                                                 \
     "s_min_u32 s41, s41, 64\n\t" MCS_FA_TAKE##W                                                   \
     "v_add_u32 v121, s57, v110\n\t"                                                               \
@@ -251,7 +256,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "v_add_u32 v121, 0x400, v121\n\t"                                                             \
     "global_load_dwordx4 v[98:101], v121, s[64:65]\n\t" MCS_FC_SHIFT                              \
     "s_mov_b32 s47, 0\n\t" MCS_FA_REC##W                                                          \
-    "s_branch mcsfa_inner_%=\n"
+    "s_branch mcsfa_inner_%=\n" MCS_FC_BMOVE_OOL
 // fused records: the statement ends with s59 = 1 and the kernel synthesises the next batch
 #define MCS_FA_BENDTAIL_F(W)                                                                      \
     "s_mov_b32 s47, 0\n\t"                                                                        \
@@ -289,12 +294,15 @@ __device__ unsigned long long g_fa_stamps[4];
 // the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes (eight copies,
 // one per clock residue, each with its waiting-head section; the sections' sleep chain and the single
 // paths behind them) and batch-end tail, the shared entry, ends and exit (a head still waiting at the exit
-// is s43 != 0); its clobbers add FREE's upper rows; the sections use no register of their own (s79 is the
-// sleep's limit between a failed fit and the head's placement).  It carries no MCS_STAMPS segment clocks
+// is s43 != 0); its clobbers add FREE's upper rows, the LIVE column and the bulk move's read quads; the
+// sections use no register of their own (s79 is the sleep's limit between a failed fit and the head's
+// placement).  It carries no MCS_STAMPS segment clocks
 // (its FREE rows occupy s92-s101, where the stamps live), so the probe build does not expand it and
 // runs this shape on W16; the forms with stamps are W32, W16, W16S and the fused W16R / W16S loops
 #define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, C) MCS_FA_EXIT_S(16C)
-#define MCS_FC_CLOBBERS MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101"
+#define MCS_FC_CLOBBERS                                                                                      \
+    MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101", "v56", "v57", "v58", \
+        "v59", "v60", "v61", "v62", "v63", "v102", "v103", "v104", "v105", "v106"
 
 // ---- the loop with the job stream synthesised in the kernel (mcs_gen_params.fused) ---------------
 // The statement runs one batch of records and ends at its batch end with s59 = 1 (or at the end of
@@ -408,8 +416,8 @@ __device__ __forceinline__ void fa_finish(const FifoArgs& a, uint32_t ci, uint32
 // (NPL nodes per lane, P slot rows: 4/8 for 129-256 node clusters, 1/2 for at most 64 nodes)
 // (DIAG: count the passes without a decision and the release scans into mcs_cluster_stats; the
 // production launches skip them, 1.6 % of the C4 loop)
-// (the streamed W16R loop, W16C: LDS holds the node words alone, [64] lanes x [4] chunks, one 16-byte
-// word per lane; its kx is the node index)
+// (the streamed W16R loop, W16C: LDS holds the node words, [64] lanes x [4] chunks, one 16-byte word per
+// lane, and behind them the bulk move's scratch, [64] entries of 16 bytes; its kx is the node index)
 template <int W, bool RS, int NPL, int P, bool DIAG>
 __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     static_assert(W == 16 || !RS, "register slots: 16-bit node format only");
@@ -419,7 +427,7 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     const uint32_t lane = threadIdx.x;
 
     constexpr bool CAL = W == 16 && RS && NPL == 4;  // W16C: calendar slot rows, 16-byte node words
-    __shared__ alignas(CAL ? 16 : 8) uint64_t lds[CAL ? NPL * kWave / 2 : NPL * kWave + 2 * P * kWave];
+    __shared__ alignas(CAL ? 16 : 8) uint64_t lds[CAL ? NPL * kWave / 2 + 2 * kWave : NPL * kWave + 2 * P * kWave];
 
     constexpr uint32_t kGuard = W == 32 ? 0x80000000u : 0x8000u;
     constexpr uint32_t kClamp = kGuard - 1u;  // request clamp and padding value

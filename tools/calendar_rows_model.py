@@ -13,6 +13,12 @@ completion, and by one second after a placed WaitQueue head), with the slot poli
   fit       without a release the clock jumps to the exact earliest finish.  The steps, the release that
             ends them and the head's placement run in the waiting-head section of the copy (DESIGN.md §4,
             "The waiting head"; WAIT below holds its counts beside those of the loop before it).
+Two insert policies are replayed side by side ("Running jobs stay in their batch lane"):
+  per-job   the slot is taken at the placement (the loop before);
+  deferred  a placed job stays in its batch lane (the LIVE column, compared at every clock advance beside the
+            calendar row) until it finishes there or its batch of 64 ends; then the live lanes go to their rows
+            together, each row's candidates to its free lanes, and a row's surplus spills as a per-job insert did.
+DEFER holds the instructions the deferred policy adds and removes, counted from the listing.
 Printed per job: release scans and what they compared, spills, failed fits and the seconds their sleeps
 cross, the compares that release nothing, the running slots; and the instructions a scan issues, counted
 from the listing of the loop as built (COST below; the pair scan of the loop before it from
@@ -72,17 +78,52 @@ WAIT = {
 }
 
 
-def replay(arr, dur, start, finish, st):
+# the deferred insert against the per-job one, from the two listings: (scalar, branch, vector, LDS) per event
+DEFER = {
+    # the pass's decision: the slot insert's 11 scalar instructions and its spill branch go (s_and s49, s_lshl m0,
+    # s_movrels, s_ff1 s85, s_lshl s[62:63], s_andn2, s_and, s_movreld, s_mov exec, s_lshl2_add s79,
+    # s_set_gpr_idx_idx; s_cbranch_scc0), and the three indexed v_mov; one v_writelane (LIVE) comes
+    "placement": ("inserts", (-11, -1, -2, 0)),
+    # every row compare is preceded by LIVE's: v_cmp and an untaken s_cbranch_vccnz
+    "row compare": ("row compares", (0, 1, 1, 0)),
+    # the out-of-line batch-lane release with nothing in the calendar row, against the row block's in-line body:
+    # the same exec / count / exec, one taken branch more, v_lshl_add and the second v_cmp
+    "batch-lane release, row empty": ("batch-lane scans, row empty", (0, 1, 2, 0)),
+    # ... with the row expiring as well: its body (4 scalar: exec, count, FREE, the sum), a branch back
+    "batch-lane release and row": ("batch-lane scans, row expires", (4, 2, 3, 1)),
+    # the bulk move of a batch with a live lane (MCS_FC_BMOVE): 2 + 8 x 4 + 2 + 8 x 3 + 1 scalar, 1 + 8 + 1 branch,
+    # 7 + 8 x 5 + 1 + 8 + 8 x 5 + 8 x 4 + 1 vector, the write and eight reads
+    "bulk move": ("bulk moves", (61, 10, 129, 9)),
+    # a batch end with no live lane: v_cmp and the branch
+    "bulk move, nothing live": ("bulk moves, nothing live", (0, 1, 1, 0)),
+    # a surplus job's insert at the batch end (mcsfa_bmo / mcsfa_bml: about one row searched), per spill of the
+    # deferred replay
+    "surplus insert": ("spills", (22, 5, 7, 0)),
+    # the per-job insert's spill, which goes, per spill of the per-job replay (MCS_FC_SPILL beside the insert that
+    # "placement" has taken off already, about one row searched: s_and s76; s_add, s_and, s_cmp, s_lshl m0, s_nop,
+    # s_movrels, s_cmp_lg and the loop's two branches; s_ff1, s_lshl, s_andn2, s_movreld, s_min and the branch back)
+    "per-job spill": ("spills", (-13, -3, 0, 0), "per-job insert"),
+}
+
+
+def replay(arr, dur, start, finish, st, deferred=False):
     free = np.ones((ROWS, LANES), bool)
-    heap = []  # (finish, row, lane, misplaced)
+    heap = []  # (finish, job)
+    slot = {}  # job -> (row, lane, misplaced), or None while it sits in its batch lane
     mis = []  # finishes of the misplaced slots alive (a heap)
     t = 0
 
     def release():
-        """-> rows released at t, misplaced among them"""
+        """-> rows released at t (-1: the batch lanes), misplaced among them"""
         rows, m = set(), 0
         while heap and heap[0][0] <= t:
-            f, row, lane, x = heapq.heappop(heap)
+            f, j = heapq.heappop(heap)
+            where = slot.pop(j)
+            if where is None:
+                rows.add(-1)
+                st["jobs that finish in their batch lane"] += 1
+                continue
+            row, lane, x = where
             free[row, lane] = True
             rows.add(row)
             if x:
@@ -90,6 +131,38 @@ def replay(arr, dur, start, finish, st):
                 mis.remove(f)
                 heapq.heapify(mis)
         return rows, m
+
+    def insert(j, f, bulk=False):
+        r, x = f & 7, 0
+        if not free[r].any():
+            st["spills"] += 1
+            x = 1
+            for i in range(1, ROWS):
+                if free[(f + i) & 7].any():
+                    r = (f + i) & 7
+                    break
+            else:
+                raise AssertionError("pool full")
+            heapq.heappush(mis, f)
+        lane = int(np.argmax(free[r]))
+        free[r, lane] = False
+        slot[j] = (r, lane, x)
+        return x
+
+    def bulk_move():
+        live = sorted(j for j, w in slot.items() if w is None)
+        st["bulk moves" if live else "bulk moves, nothing live"] += 1
+        # each row's candidates first (the rows' own free lanes), then the surplus one at a time
+        left = []
+        for j in live:
+            f = int(finish[j])
+            if free[f & 7].any():
+                insert(j, f)
+            else:
+                left.append(j)
+        for j in left:
+            insert(j, int(finish[j]))
+        st["batches with a surplus"] += bool(left)
 
     def full(why):
         rows, _ = release()
@@ -105,16 +178,21 @@ def replay(arr, dur, start, finish, st):
         if mis and t >= mis[0]:
             return full("a misplaced slot is due")
         due = heap and heap[0][0] <= t
+        st["row compares"] += 1
         if due:
             rows, m = release()
-            assert rows == {t & 7} and not m, (rows, t)
+            assert rows <= {t & 7, -1} and not m, (rows, t)
             st["release scans"] += 1
             st["scans of one row"] += 1
+            if -1 in rows:
+                st["batch-lane scans, row expires" if len(rows) == 2 else "batch-lane scans, row empty"] += 1
         else:
             st["empty compares: " + kind] += 1
         return bool(due)
 
     for k in range(len(arr)):
+        if deferred and k and k % LANES == 0:
+            bulk_move()
         if arr[k] > t:
             gap, t = int(arr[k]) - t, int(arr[k])
             st["arrival advances"] += 1
@@ -133,6 +211,7 @@ def replay(arr, dur, start, finish, st):
                 if steps == 8:
                     st["exact-minimum jumps"] += 1
                     t = heap[0][0]
+                    st["row compares"] -= 1  # (the jump lands in the row block; counted with the step)
                     assert adv1("failed fit")
                     break
                 t += 1
@@ -143,22 +222,13 @@ def replay(arr, dur, start, finish, st):
             st["longest sleep"] = max(st["longest sleep"], t - sleep0)
         if dur[k]:
             f = int(finish[k])
-            r, x = f & 7, 0
-            if not free[r].any():
-                st["spills"] += 1
-                x = 1
-                for i in range(1, ROWS):
-                    if free[(f + i) & 7].any():
-                        r = (f + i) & 7
-                        break
-                else:
-                    raise AssertionError("pool full")
-                heapq.heappush(mis, f)
-            lane = int(np.argmax(free[r]))
-            free[r, lane] = False
-            heapq.heappush(heap, (f, r, lane, x))
+            heapq.heappush(heap, (f, k))
+            if deferred:
+                slot[k] = None
+            else:
+                insert(k, f)
             st["inserts"] += 1
-        st["running"].append(len(heap))
+        st["running"].append(sum(w is not None for w in slot.values()) if deferred else len(heap))
         if w:  # a placed WaitQueue head sleeps one second
             st["waited"] += 1
             t += 1
@@ -168,15 +238,18 @@ def replay(arr, dur, start, finish, st):
 def main():
     gp = GenParams(seed=0x4D43535F53494D31, arrival_mode=1, lam=scaled_lambda(N, load=0.9))
     nc = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-    st = collections.Counter()
-    st["running"] = []
+    st, sd = collections.Counter(), collections.Counter()
+    st["running"], sd["running"] = [], []
     jobs = 0
     for ci in range(nc):
         a, d, c, m = gen_cluster_host(gp, ci, 32, 24000, J)
         node, start, finish = O.fifo_run(np.full(N, 32, np.uint32), np.full(N, 24000, np.uint32), a, d, c, m)[:3]
         assert (node >= 0).all()
         replay(a, d, start, finish, st)
+        replay(a, d, start, finish, sd, deferred=True)
         jobs += len(a)
+    drun = np.array(sd.pop("running"))
+    sd.pop("longest sleep")
     run = np.array(st.pop("running"))
     longest = st.pop("longest sleep")
     scans = st["release scans"]
@@ -196,6 +269,22 @@ def main():
     for i, f in enumerate(("scalar", "vector")):
         rows["change per job: " + f] = round(sum(st[n] * (a[i] - b[i]) for n, b, a in WAIT.values()) / jobs, 2)
     out["waiting_head_paths"] = rows
+    keys = ("row compares", "release scans", "jobs that finish in their batch lane", "batch-lane scans, row expires",
+            "batch-lane scans, row empty", "spills", "full scans: a misplaced slot is due", "bulk moves",
+            "bulk moves, nothing live", "batches with a surplus")
+    both = {k: {"per-job insert": round(st[k] / jobs, 4), "deferred": round(sd[k] / jobs, 4)} for k in keys}
+    both["slots in the table"] = {"per-job insert": {"mean": round(float(run.mean()), 1), "max": int(run.max())},
+                                  "deferred": {"mean": round(float(drun.mean()), 1), "max": int(drun.max())}}
+    batches = sd["bulk moves"] + sd["bulk moves, nothing live"]
+    both["share of batches with a surplus"] = round(sd["batches with a surplus"] / max(batches, 1), 4)
+    change = {}
+    for name, (n, cost, *of) in DEFER.items():
+        count = (st if of else sd)[n]  # the deferred replay's events, but for what the per-job insert alone did
+        change[name] = {"per_job": round(count / jobs, 4), "scalar, branch, vector, lds": list(cost)}
+        for i, f in enumerate(("scalar", "branch", "vector", "lds")):
+            change.setdefault("change per job", dict.fromkeys(("scalar", "branch", "vector", "lds"), 0.0))[f] += count * cost[i] / jobs
+    change["change per job"] = {f: round(x, 2) for f, x in change["change per job"].items()}
+    out["deferred_insert"] = {"replay": both, "instructions": change}
     print(json.dumps(out, indent=1))
 
 
