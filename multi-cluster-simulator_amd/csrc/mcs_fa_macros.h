@@ -72,14 +72,16 @@
 //                                                          move's masks (s[60:61] -> s_bcnt1,
 //                                                          s_and exec)
 //  VALU writes SGPR -> VALU reads it as a constant  0     the bulk move: v_cmp s[60:61] ->     (interlocked; not a lane select)
-//                                                          v_mbcnt / v_cndmask
+//                                                          v_mbcnt / v_cndmask; W16C's starts
+//                                                          (MCS_FA_STARTS16C: v_cmp vcc, one
+//                                                          v_sub, v_cndmask with vcc)
 //  LDS instruction issued -> its address / data      0     the bulk move: v120 is formed again  (not in the ISA's table of required
 //    VGPRs rewritten                                       right after each ds_read_b128        wait states, whose one row of this
 //                                                          (its address only: a read has no     kind is the VMEM store above; beyond
-//                                                          data VGPRs to be read later)         that it rests on the GPU parity runs
-//                                                                                              of tests/test_gpu_deferred_insert.py's
-//                                                                                              bulk-move cases, which differ per
-//                                                                                              entry in finish, request and node)
+//                                                          data VGPRs to be read later; the     that it rests on the GPU parity runs
+//                                                          reads land in the rows' own quads,   of tests/test_gpu_deferred_insert.py's
+//                                                          which nothing touches before the     bulk-move cases, which differ per
+//                                                          one s_waitcnt lgkmcnt(0) behind them) entry in finish, request and node)
 //  s_setpc_b64 to a computed address               -     W16C's MCS_FC_RET / MCS_FC_RETW      the table of branches starts on a
 //                                                                                              512-byte line and is 320 bytes, so
 //                                                                                              s74 + 32 * entry + 4 * (t & 7), with
@@ -142,8 +144,8 @@
 //   v118 frm - 1  v120 DPP min / scan temp  v121 address  v[122:123] payload  v124 lane minimum
 //   v125-v127 store temps
 // (W16C, the streamed W16R loop: s49, s[58:59], s74, s77-s79, s82 and s[86:101] have their own
-// meaning, v87 holds a column, v106 the LIVE column, v89 nothing, s75 and v56-v63, v102-v105 are the bulk
-// move's: see "W16C" below)
+// meaning, v87 holds a column, v106 the LIVE column, v89 nothing, its slot rows are the quads v[32:63], v92
+// holds no start for a live lane, s75 is the bulk move's: see "W16C" below)
 #define MCS_FA_CLOBBERS                                                                            \
     "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53",  \
         "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66",     \
@@ -510,6 +512,12 @@
 #define MCS_FA_XWAITED32 MCS_FA_XWAITED_
 #define MCS_FA_XWAITED16 MCS_FA_XWAITED_
 #define MCS_FA_XWAITED16S MCS_FA_XWAITED_
+// the result batch's start column (v92) before it is read, at the batch end's stores and at the exit:
+// complete in every form that writes a start at the placement; W16C forms its live lanes' here
+#define MCS_FA_STARTS32 ""
+#define MCS_FA_STARTS16 ""
+#define MCS_FA_STARTS16S ""
+#define MCS_FA_STARTS16R ""
 // slots of the pool (64 lanes x P rows)
 #define MCS_FA_POOLMAX32 "64*8"
 #define MCS_FA_POOLMAX16 "64*8"
@@ -525,14 +533,15 @@
 
 // ---- W16C: W16R with calendar slot rows (the streamed loop of the 129-256 node shape; DESIGN.md §4
 // "Calendar rows") ------------------------------------------------------------------------------------
-// A slot lives in row finish & 7, so a clock advance to second t compares ONE row, v(32 + (t & 7)),
+// A slot lives in row finish & 7, so a clock advance to second t compares ONE row, v(32 + 4 * (t & 7)),
 // and the wave's earliest finish is not kept at all (no lane-minimum tree, no DPP chain, no s_min per
 // insert).  Invariant, after the clock has been handled at second t: no slot has finish <= t; every
 // slot sits in row finish & 7 but the misplaced ones (their row was full: they took the next row with
 // a free lane); XMIN (s77) <= the earliest finish of any misplaced slot, 0xffffffff when there is none.
 // The free slots are scalar lane masks, one per row.  A placement takes no slot: the job stays in its
 // batch lane, its finish in the LIVE column v106 (-1 in every lane without a running job of the current
-// batch), its node in v91 and its request in v96 as the result batch and the records hold them anyway.
+// batch), its node in v91 and its request in v96 as the result batch and the records hold them anyway; its
+// start is not written at all while it is live (finish - v95, MCS_FA_STARTS16C).
 // Whatever compares a calendar row against t compares LIVE first (the copies' row blocks, the sleep chain,
 // the full scan as a ninth row, the exact minimum); a lane that expires hands its request back out of line
 // (MCS_FC_BREL).  At the batch end the live lanes go into their rows together (MCS_FC_BMOVE), so the
@@ -643,6 +652,16 @@
     "s_lshl2_add_u32 s54, s50, s53\n\t"
 #define MCS_FA_POOLMAX16C "64*8"
 #define MCS_FA_NODEIDX16C "v_mov_b32 v126, v91\n\t"
+// A running job of the current batch has no start in v92: LIVE holds its finish and v95 its duration, and
+// the start is formed where the lane leaves LIVE (MCS_FC_BREL, the full scan's ninth row) or, for the
+// lanes still live, where the result batch is read: before the batch end's stores and at the exit (no live
+// lane there when the run stopped at the first job of a new batch: the bulk move has left -1 in LIVE, and
+// v95 is the new batch's).  No wrap: finish = start + duration, which the host bounds below 2^32 - 1.
+// Zero-duration jobs never enter LIVE, their start is written at the placement (mcsfa_zero).
+#define MCS_FA_STARTS16C                                                                          \
+    "v_cmp_ne_u32_e32 vcc, -1, v106\n\t"                                                          \
+    "v_sub_u32 v120, v106, v95\n\t"                                                               \
+    "v_cndmask_b32_e32 v92, v92, v120, vcc\n\t"
 // The WaitQueue statistic of this form is counted where the WaitQueue head is placed (the waiting-head
 // section of MCS_FC_COPY, mcsfa_zhead: once per waited job, where the shared loop pays a subtract and an
 // add at every failed fit); a head still waiting when the loop leaves (deadlock, the runaway guard:
@@ -674,13 +693,13 @@
     "s_add_u32 s74, s58, mcsfa_tbl_%=-mcsfa_pc_%=\n\t"                                           \
     "s_addc_u32 s59, s59, 0\n\t"                                                                      \
     "v_mov_b32 v32, -1\n\t"                                                                      \
-    "v_mov_b32 v33, -1\n\t"                                                                      \
-    "v_mov_b32 v34, -1\n\t"                                                                      \
-    "v_mov_b32 v35, -1\n\t"                                                                      \
     "v_mov_b32 v36, -1\n\t"                                                                      \
-    "v_mov_b32 v37, -1\n\t"                                                                      \
-    "v_mov_b32 v38, -1\n\t"                                                                      \
-    "v_mov_b32 v39, -1\n\t"                                                                      \
+    "v_mov_b32 v40, -1\n\t"                                                                      \
+    "v_mov_b32 v44, -1\n\t"                                                                      \
+    "v_mov_b32 v48, -1\n\t"                                                                      \
+    "v_mov_b32 v52, -1\n\t"                                                                      \
+    "v_mov_b32 v56, -1\n\t"                                                                      \
+    "v_mov_b32 v60, -1\n\t"                                                                      \
     "v_mov_b32 v106, -1\n\t" /* LIVE: no job of the batch is running */
 // The decision is the pick and the commit alone (MCS_FA_DECIDE16R's chunk move in its register-index
 // region): a placed job takes no slot.  It stays in its batch lane, its finish in the LIVE column v106
@@ -706,6 +725,7 @@
     "s_bcnt1_i32_b64 s76, vcc\n\t"                                                               \
     "v_lshl_add_u32 v121, v91, 2, v109\n\t"                                                      \
     "ds_add_u32 v121, v96\n\t"                                                                    \
+    "v_sub_u32 v92, v106, v95\n\t" /* the start: finish - the lane's duration */                 \
     "v_mov_b32 v106, -1\n\t"                                                                      \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "v_cmp_ge_u32_e32 vcc, s40, " F "\n\t"                                                       \
@@ -722,14 +742,15 @@
 // candidates are numbered row after row (v_mbcnt on the row's candidate mask, on top of the rows before:
 // O[r] in s50-s55, s62, s63 is the count of rows 0 .. r) and write {finish, request, node address} to
 // the 16-byte entry of their number in the LDS scratch behind the node words (base + 1024); free lane
-// number j of row r reads entry O[r-1] + j while that is below O[r] (eight reads, one wait; a lane that
-// reads nothing keeps -1 in the word the finish lands in) and takes it into the row's registers.  A row
+// number j of row r reads entry O[r-1] + j while that is below O[r]: one masked ds_read_b128 per row, straight
+// into the row's quad v[32+4r : 35+4r] = {finish, payload, node address, a word nothing reads} under exec = the
+// lanes that take an entry, the other lanes keeping what they hold (eight reads, one wait).  A row
 // with more candidates than free lanes (out of line, mcsfa_bmo<r>) marks the ones beyond in s[46:47];
 // they go one at a time, as a per-job insert did, to the first row r+1 ... r+7 (mod 8) with a free lane,
 // XMIN = min(XMIN, finish).  The pool cannot be short: the batch end has left on peak > 64*8, and below
 // that the free slots are at least the live lanes (a row search that comes round is a pool overflow all
 // the same).  Temporaries: s[46:49] (set again by the batch take), s49, s75, s76, s79, s85, s[50:55],
-// s[60:63], v112-v115, v120-v123 and the read quads v[56:63], v[68:79], v[82:85], v[102:105], v[124:127].
+// s[60:63], v112-v115, v120-v123.
 #define MCS_FC_BMA(r, OP, ON, FREE)                                                               \
     "v_cmp_eq_u32_e64 s[60:61], " #r ", v122\n\t"                                                 \
     "s_bcnt1_i32_b64 s76, s[60:61]\n\t"                                                           \
@@ -760,11 +781,6 @@
     "ds_read_b128 " Q ", v120 offset:1024\n\t"                                                    \
     "s_andn2_b64 " FREE ", " FREE ", exec\n\t"                                                    \
     "s_mov_b64 exec, -1\n\t"
-#define MCS_FC_BMC(Q0, Q1, Q2, F, P, A)                                                           \
-    "v_cmp_ne_u32_e32 vcc, -1, " Q0 "\n\t"                                                        \
-    "v_cndmask_b32_e32 " F ", " F ", " Q0 ", vcc\n\t"                                             \
-    "v_cndmask_b32_e32 " P ", " P ", " Q1 ", vcc\n\t"                                             \
-    "v_cndmask_b32_e32 " A ", " A ", " Q2 ", vcc\n\t"
 #define MCS_FC_BMOVE                                                                              \
     "v_cmp_ne_u32_e32 vcc, -1, v106\n\t"                                                          \
     "s_cbranch_vccz mcsfa_bmx_%=\n\t"                                                             \
@@ -784,31 +800,15 @@
     "v_lshl_add_u32 v123, v123, 4, v109\n\t"                                                      \
     "ds_write_b128 v123, v[112:115] offset:1024\n\t"                                              \
     "s_mov_b64 exec, -1\n\t"                                                                      \
-    "v_mov_b32 v56, -1\n\t"                                                                       \
-    "v_mov_b32 v60, -1\n\t"                                                                       \
-    "v_mov_b32 v68, -1\n\t"                                                                       \
-    "v_mov_b32 v72, -1\n\t"                                                                       \
-    "v_mov_b32 v76, -1\n\t"                                                                       \
-    "v_mov_b32 v82, -1\n\t"                                                                       \
-    "v_mov_b32 v102, -1\n\t"                                                                      \
-    "v_mov_b32 v124, -1\n\t"                                                                      \
-    MCS_FC_BMB("0", "s50", "s86", "s87", "s[86:87]", "v[56:59]")                                  \
-    MCS_FC_BMB("s50", "s51", "s88", "s89", "s[88:89]", "v[60:63]")                                \
-    MCS_FC_BMB("s51", "s52", "s90", "s91", "s[90:91]", "v[68:71]")                                \
-    MCS_FC_BMB("s52", "s53", "s92", "s93", "s[92:93]", "v[72:75]")                                \
-    MCS_FC_BMB("s53", "s54", "s94", "s95", "s[94:95]", "v[76:79]")                                \
-    MCS_FC_BMB("s54", "s55", "s96", "s97", "s[96:97]", "v[82:85]")                                \
-    MCS_FC_BMB("s55", "s62", "s98", "s99", "s[98:99]", "v[102:105]")                              \
-    MCS_FC_BMB("s62", "s63", "s100", "s101", "s[100:101]", "v[124:127]")                          \
+    MCS_FC_BMB("0", "s50", "s86", "s87", "s[86:87]", "v[32:35]")                                  \
+    MCS_FC_BMB("s50", "s51", "s88", "s89", "s[88:89]", "v[36:39]")                                \
+    MCS_FC_BMB("s51", "s52", "s90", "s91", "s[90:91]", "v[40:43]")                                \
+    MCS_FC_BMB("s52", "s53", "s92", "s93", "s[92:93]", "v[44:47]")                                \
+    MCS_FC_BMB("s53", "s54", "s94", "s95", "s[94:95]", "v[48:51]")                                \
+    MCS_FC_BMB("s54", "s55", "s96", "s97", "s[96:97]", "v[52:55]")                                \
+    MCS_FC_BMB("s55", "s62", "s98", "s99", "s[98:99]", "v[56:59]")                                \
+    MCS_FC_BMB("s62", "s63", "s100", "s101", "s[100:101]", "v[60:63]")                            \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
-    MCS_FC_BMC("v56", "v57", "v58", "v32", "v40", "v48")                                          \
-    MCS_FC_BMC("v60", "v61", "v62", "v33", "v41", "v49")                                          \
-    MCS_FC_BMC("v68", "v69", "v70", "v34", "v42", "v50")                                          \
-    MCS_FC_BMC("v72", "v73", "v74", "v35", "v43", "v51")                                          \
-    MCS_FC_BMC("v76", "v77", "v78", "v36", "v44", "v52")                                          \
-    MCS_FC_BMC("v82", "v83", "v84", "v37", "v45", "v53")                                          \
-    MCS_FC_BMC("v102", "v103", "v104", "v38", "v46", "v54")                                       \
-    MCS_FC_BMC("v124", "v125", "v126", "v39", "v47", "v55")                                       \
     "s_cmp_lg_u64 s[46:47], 0\n\t"                                                                \
     "s_cbranch_scc1 mcsfa_bml_%=\n"                                                               \
     "mcsfa_bmd_%=:\n\t"                                                                           \
@@ -844,11 +844,12 @@
     "s_movreld_b64 s[86:87], s[50:51]\n\t"                                                        \
     "s_min_u32 s77, s77, s55\n\t"                                                                 \
     "s_lshl2_add_u32 s79, s54, s73\n\t"                                                           \
+    "s_lshl_b32 s75, s49, 2\n\t" /* the row's quad: v(32 + 4r) */                                \
     "s_mov_b64 exec, s[62:63]\n\t"                                                                \
-    "s_set_gpr_idx_on s49, gpr_idx(DST)\n\t"                                                      \
+    "s_set_gpr_idx_on s75, gpr_idx(DST)\n\t"                                                      \
     "v_mov_b32 v32, s55\n\t"                                                                      \
-    "v_mov_b32 v40, s48\n\t"                                                                      \
-    "v_mov_b32 v48, s79\n\t"                                                                      \
+    "v_mov_b32 v33, s48\n\t"                                                                      \
+    "v_mov_b32 v34, s79\n\t"                                                                      \
     "s_set_gpr_idx_off\n\t"                                                                       \
     "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_cmp_lg_u64 s[46:47], 0\n\t"                                                                \
@@ -892,10 +893,10 @@
     "mcsfa_full_%=:\n\t"                                                                          \
     "ds_write_b128 v108, v[64:67]\n\t"                                                           \
     "s_mov_b32 s49, 0\n\t"                                                                        \
-    MCS_FC_FROW(0, "v32", "v40", "v48", "s[86:87]") MCS_FC_FROW(1, "v33", "v41", "v49", "s[88:89]") \
-    MCS_FC_FROW(2, "v34", "v42", "v50", "s[90:91]") MCS_FC_FROW(3, "v35", "v43", "v51", "s[92:93]") \
-    MCS_FC_FROW(4, "v36", "v44", "v52", "s[94:95]") MCS_FC_FROW(5, "v37", "v45", "v53", "s[96:97]") \
-    MCS_FC_FROW(6, "v38", "v46", "v54", "s[98:99]") MCS_FC_FROW(7, "v39", "v47", "v55", "s[100:101]") \
+    MCS_FC_FROW(0, "v32", "v33", "v34", "s[86:87]") MCS_FC_FROW(1, "v36", "v37", "v38", "s[88:89]") \
+    MCS_FC_FROW(2, "v40", "v41", "v42", "s[90:91]") MCS_FC_FROW(3, "v44", "v45", "v46", "s[92:93]") \
+    MCS_FC_FROW(4, "v48", "v49", "v50", "s[94:95]") MCS_FC_FROW(5, "v52", "v53", "v54", "s[96:97]") \
+    MCS_FC_FROW(6, "v56", "v57", "v58", "s[98:99]") MCS_FC_FROW(7, "v60", "v61", "v62", "s[100:101]") \
     /* the ninth row: the batch lanes (LIVE), their requests back to the nodes base + 4 * v91 */  \
     "v_cmp_ge_u32_e32 vcc, s40, v106\n\t"                                                        \
     "s_cbranch_vccz mcsfa_fr8_%=\n\t"                                                            \
@@ -903,6 +904,7 @@
     "s_bcnt1_i32_b64 s76, vcc\n\t"                                                              \
     "v_lshl_add_u32 v121, v91, 2, v109\n\t"                                                     \
     "ds_add_u32 v121, v96\n\t"                                                                   \
+    "v_sub_u32 v92, v106, v95\n\t" /* the start */                                               \
     "v_mov_b32 v106, -1\n\t"                                                                     \
     "s_add_u32 s49, s49, s76\n\t"                                                                \
     "s_mov_b64 exec, -1\n"                                                                       \
@@ -910,8 +912,8 @@
     "s_cmp_lt_u32 s40, s77\n\t" /* no misplaced slot was due: XMIN stands */                    \
     "s_cbranch_scc1 mcsfa_fx_%=\n\t"                                                              \
     "v_mov_b32 v120, -1\n\t"                                                                      \
-    MCS_FC_XROW(0, "v32") MCS_FC_XROW(1, "v33") MCS_FC_XROW(2, "v34") MCS_FC_XROW(3, "v35")      \
-    MCS_FC_XROW(4, "v36") MCS_FC_XROW(5, "v37") MCS_FC_XROW(6, "v38") MCS_FC_XROW(7, "v39")      \
+    MCS_FC_XROW(0, "v32") MCS_FC_XROW(1, "v36") MCS_FC_XROW(2, "v40") MCS_FC_XROW(3, "v44")      \
+    MCS_FC_XROW(4, "v48") MCS_FC_XROW(5, "v52") MCS_FC_XROW(6, "v56") MCS_FC_XROW(7, "v60")      \
     MCS_FC_WMIN("s77") "\n"                                                                      \
     "mcsfa_fx_%=:\n\t"                                                                            \
     "s_mov_b32 s76, s49\n\t"                                                                      \
@@ -921,10 +923,10 @@
 // every running job's earliest finish into s76, the batch lanes' (LIVE) with the slots' (lane-minimum
 // tree + DPP; free slots and lanes hold -1)
 #define MCS_FC_EXACTMIN                                                                           \
-    "v_min3_u32 v121, v32, v33, v34\n\t"                                                         \
-    "v_min3_u32 v121, v121, v35, v36\n\t"                                                        \
-    "v_min3_u32 v121, v121, v37, v38\n\t"                                                        \
-    "v_min3_u32 v120, v121, v39, v106\n\t" MCS_FC_WMIN("s76")
+    "v_min3_u32 v121, v32, v36, v40\n\t"                                                         \
+    "v_min3_u32 v121, v121, v44, v48\n\t"                                                        \
+    "v_min3_u32 v121, v121, v52, v56\n\t"                                                        \
+    "v_min3_u32 v120, v121, v60, v106\n\t" MCS_FC_WMIN("s76")
 // the zero route (out of line, from mcsfa_arrive): the true arrival's test and the sleep to it, or the
 // fit test and mcsfa_zero.  A zero-duration job that fits nowhere waits out of line as well
 // (mcsfa_znofit, s43 = 2; 1 in 600 jobs has zero duration and few of those wait, so the copies' waiting-
@@ -1102,7 +1104,6 @@
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "v_writelane_b32 v106, s55, m0\n" /* LIVE: the job runs in its batch lane */                                                              \
     /* next ready job */                                                                          \
     /* (m0 = the lane of the job just placed; no next job in the batch and a zero-duration one */ \
@@ -1169,7 +1170,6 @@
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
-    "v_writelane_b32 v92, s40, m0\n\t"                                                            \
     "v_writelane_b32 v106, s55, m0\n\t"                                                            \
     "s_add_u32 s82, s82, 1\n\t"                                                                   \
     "s_mov_b32 s43, 0\n\t" MCS_FC_RECNEXT                                                        \
@@ -1195,17 +1195,17 @@
 #define MCS_FC_PASS(D)                                                                            \
     "s_branch mcsfa_inner_%=\n"                                                                   \
     ".p2align 6\n"                                                                                \
-    MCS_FC_COPY(D, 0, 1, "v32", "v40", "v48", "s[86:87]", "")                                     \
-    MCS_FC_COPY(D, 1, 2, "v33", "v41", "v49", "s[88:89]", "")                                     \
-    MCS_FC_COPY(D, 2, 3, "v34", "v42", "v50", "s[90:91]", "")                                     \
-    MCS_FC_COPY(D, 3, 4, "v35", "v43", "v51", "s[92:93]", "")                                     \
-    MCS_FC_COPY(D, 4, 5, "v36", "v44", "v52", "s[94:95]", "")                                     \
-    MCS_FC_COPY(D, 5, 6, "v37", "v45", "v53", "s[96:97]", "")                                     \
-    MCS_FC_COPY(D, 6, 7, "v38", "v46", "v54", "s[98:99]", "")                                     \
-    MCS_FC_COPY(D, 7, 0, "v39", "v47", "v55", "s[100:101]", "\ts_branch mcsfa_blk0_%=\n")         \
+    MCS_FC_COPY(D, 0, 1, "v32", "v33", "v34", "s[86:87]", "")                                     \
+    MCS_FC_COPY(D, 1, 2, "v36", "v37", "v38", "s[88:89]", "")                                     \
+    MCS_FC_COPY(D, 2, 3, "v40", "v41", "v42", "s[90:91]", "")                                     \
+    MCS_FC_COPY(D, 3, 4, "v44", "v45", "v46", "s[92:93]", "")                                     \
+    MCS_FC_COPY(D, 4, 5, "v48", "v49", "v50", "s[94:95]", "")                                     \
+    MCS_FC_COPY(D, 5, 6, "v52", "v53", "v54", "s[96:97]", "")                                     \
+    MCS_FC_COPY(D, 6, 7, "v56", "v57", "v58", "s[98:99]", "")                                     \
+    MCS_FC_COPY(D, 7, 0, "v60", "v61", "v62", "s[100:101]", "\ts_branch mcsfa_blk0_%=\n")         \
     /* ---- the sleep chain of the waiting-head sections ---- */                                 \
-    MCS_FC_WSL(0, "v32") MCS_FC_WSL(1, "v33") MCS_FC_WSL(2, "v34") MCS_FC_WSL(3, "v35")           \
-    MCS_FC_WSL(4, "v36") MCS_FC_WSL(5, "v37") MCS_FC_WSL(6, "v38") MCS_FC_WSL(7, "v39")           \
+    MCS_FC_WSL(0, "v32") MCS_FC_WSL(1, "v36") MCS_FC_WSL(2, "v40") MCS_FC_WSL(3, "v44")           \
+    MCS_FC_WSL(4, "v48") MCS_FC_WSL(5, "v52") MCS_FC_WSL(6, "v56") MCS_FC_WSL(7, "v60")           \
     "\ts_branch mcsfa_wsl0_%=\n"                                                                  \
     /* ---- the single paths ---- */                                                              \
     /* the sleep has reached its limit: a misplaced slot is due (every row is scanned), or eight */ \

@@ -33,6 +33,10 @@
 //     finish & 7 together, each row's candidates to the free lanes of its mask (eight 64-bit masks in
 //     SGPRs) by rank through a 1 KiB LDS scratch, and a row's surplus one at a time to the next row with
 //     a free lane; the pool is never short there, the batch end having left on peak > 64*P before.
+//     A slot row there is one register quad {finish, payload, node address, a spare word}, which the
+//     move's masked ds_read_b128 fills directly.  A live job's start is not written either: it is
+//     finish - duration, formed where the lane leaves LIVE, before the batch end's stores and at the
+//     exit (MCS_FA_STARTS16C).
 //   * The cursor's lane in the batch lives in m0 for the result batch writes (v_writelane) and
 //     in s47 for the record broadcasts (v_readlane).
 //   * Release at a clock advance: every slot row's expiry lane mask is computed before the first
@@ -223,7 +227,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_waitcnt vmcnt(0)\n\t"                                                                      \
     "v_add_u32 v125, s57, v110\n\t"                                                               \
     "v_lshlrev_b32 v125, 2, v125\n\t"                                                             \
-    MCS_FA_NODEIDX##W                                                                             \
+    MCS_FA_NODEIDX##W MCS_FA_STARTS##W                                                            \
     "global_store_dword v125, v126, s[66:67] nt\n\t"                                              \
     "global_store_dword v125, v92, s[68:69] nt\n\t"                                               \
     "v_add_u32 v93, v92, v95\n\t" /* finish = start + the batch's duration column */            \
@@ -275,7 +279,7 @@ __device__ unsigned long long g_fa_stamps[4];
     "s_max_u32 %[peak], s81, s80\n\t"                                                             \
     MCS_FA_XWAITED##W                                                                             \
     "s_mov_b32 %[nslow], s83\n\t"                                                                 \
-    "s_mov_b32 %[nrel], s84\n\t"                                                                  \
+    "s_mov_b32 %[nrel], s84\n\t" MCS_FA_STARTS##W                                                 \
     "v_mov_b32 %[on], v91\n\t"                                                                    \
     "v_mov_b32 %[os], v92\n\t"                                                                    \
     /* finish = start + duration of the batch the result registers hold: the current records', */ \
@@ -294,7 +298,7 @@ __device__ unsigned long long g_fa_stamps[4];
 // the streamed W16R loop with calendar slot rows (W16C, mcs_fa_macros.h): its own passes (eight copies,
 // one per clock residue, each with its waiting-head section; the sections' sleep chain and the single
 // paths behind them) and batch-end tail, the shared entry, ends and exit (a head still waiting at the exit
-// is s43 != 0); its clobbers add FREE's upper rows, the LIVE column and the bulk move's read quads; the
+// is s43 != 0); its clobbers add FREE's upper rows, the LIVE column and the rows' quads past v55; the
 // sections use no register of their own (s79 is the sleep's limit between a failed fit and the head's
 // placement).  It carries no MCS_STAMPS segment clocks
 // (its FREE rows occupy s92-s101, where the stamps live), so the probe build does not expand it and
@@ -302,7 +306,7 @@ __device__ unsigned long long g_fa_stamps[4];
 #define MCS_FC_LOOP(D) MCS_FA_ENTRY_S(16C) MCS_FC_PASS(D) MCS_FA_ENDS(16C, C) MCS_FA_EXIT_S(16C)
 #define MCS_FC_CLOBBERS                                                                                      \
     MCS_FA_CLOBBERS, "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101", "v56", "v57", "v58", \
-        "v59", "v60", "v61", "v62", "v63", "v102", "v103", "v104", "v105", "v106"
+        "v59", "v60", "v61", "v62", "v63", "v106"
 
 // ---- the loop with the job stream synthesised in the kernel (mcs_gen_params.fused) ---------------
 // The statement runs one batch of records and ends at its batch end with s59 = 1 (or at the end of

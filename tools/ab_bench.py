@@ -1,7 +1,7 @@
 """A/B timing of libmcs.so kernel variants on the C4 workload in ONE process per variant,
 alternating variants round-robin so box-to-box and thermal drift cancel.
 
-usage: python tools/ab_bench.py lib_a.so lib_b.so[@VAR=value] [...] [--rounds 3] [--steps 5]
+usage: python tools/ab_bench.py lib_a.so lib_b.so[@VAR=value] [...] [--rounds 3] [--steps 5] [--raw]
 (env AB_POLICY=FIFO|DELAY, AB_NODES, AB_LOAD, AB_CLUSTERS, AB_LAM, AB_MAXDUR select the workload;
 default C4 FIFO; AB_POLICY=DELAY AB_LAM=0.95 AB_MAXDUR=972 is the Level1-heavy DELAY stream)
 Each variant runs in its own subprocess (MCS_LIB=<path>) per round; prints median kernel ms."""
@@ -39,6 +39,9 @@ def main():
         i = args.index("--rounds"); rounds = int(args[i + 1]); del args[i:i + 2]
     if "--steps" in args:
         i = args.index("--steps"); steps = int(args[i + 1]); del args[i:i + 2]
+    raw = "--raw" in args  # every launch's ms after the summary, one JSON line per variant
+    if raw:
+        args.remove("--raw")
     res = {a: [] for a in args}
     for _ in range(rounds):
         for lib in args:
@@ -56,6 +59,9 @@ def main():
     for lib, ms in res.items():
         print(f"{os.path.basename(lib):28s} median {statistics.median(ms):8.3f} ms  min {min(ms):8.3f}  "
               f"max {max(ms):8.3f}  ({int(os.environ.get('AB_CLUSTERS', '4096')) * 16384 / statistics.median(ms) / 1e6:.3f}e9 placements/s)")
+    if raw:
+        for lib, ms in res.items():
+            print(json.dumps({os.path.basename(lib): [round(x, 3) for x in ms]}))
 
 
 if __name__ == "__main__":

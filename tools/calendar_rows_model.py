@@ -18,7 +18,8 @@ Two insert policies are replayed side by side ("Running jobs stay
   deferred  a placed job stays in its batch lane (the LIVE column, compared at every clock advance beside the
             calendar row) until it finishes there or its batch of 64 ends; then the live lanes go to their rows
             together, each row's candidates to its free lanes, and a row's surplus spills as a per-job insert did.
-DEFER holds the instructions the deferred policy adds and removes, counted from the listing.
+DEFER holds the instructions the deferred policy adds and removes, counted from the listing; LANE those of the
+three steps of "Lane results"  on top of it, per step, from the deferred replay's events.
 Printed per job: release scans and what they compared, spills, failed fits and the seconds their sleeps
 cross, the compares that release nothing, the running slots; and the instructions a scan issues, counted
 from the listing of the loop as built (COST below; the pair scan of the loop before it from
@@ -106,6 +107,36 @@ DEFER = {
 }
 
 
+# "Lane results" (DESIGN.md §4), per step and event: (scalar, branch, vector, LDS), from the listings
+LANE = {
+    # A: a live job's start is formed when its lane leaves LIVE.  The placement loses v_writelane v92; a
+    # batch-lane release (mcsfa_brel / mcsfa_wbrel, the full scan's ninth row) gains a v_sub; every stored batch
+    # and the exit gain v_cmp, v_sub, v_cndmask (MCS_FA_STARTS16C)
+    "A": {
+        "placement": ("inserts", (0, 0, -1, 0)),
+        "batch-lane release": ("batch-lane releases", (0, 0, 1, 0)),
+        "stored batch": ("batch ends", (0, 0, 3, 0)),
+        "exit": ("exits", (0, 0, 3, 0)),
+    },
+    # B (built and measured, not kept): node and finish written under exec = the job's lane.  The placement:
+    # s_mov exec, s_mov m0, s_add s80, two v_writelane, three v_readlane -> s_lshl exec, v_mov, v_add, s_mov exec,
+    # two v_readlane; the fit test's s_add s55 becomes s_add s80, taken back by an s_sub at a failed fit; the
+    # zero route reads the duration itself; MCS_FC_SHIFT loses v90's two instructions per batch
+    "B": {
+        "placement": ("inserts", (-1, 0, -1, 0)),
+        "failed fit": ("failed fits", (1, 0, 0, 0)),
+        "zero route": ("zero-duration jobs", (0, 0, 1, 0)),
+        "batch taken": ("batch ends", (0, 0, -2, 0)),
+    },
+    # C: a row is one register quad and the bulk move reads into it: eight v_mov -1 and eight times v_cmp and
+    # three v_cndmask go; a surplus insert gains the s_lshl of its register index
+    "C": {
+        "bulk move": ("bulk moves", (0, 0, -40, 0)),
+        "surplus insert": ("spills", (1, 0, 0, 0)),
+    },
+}
+
+
 def replay(arr, dur, start, finish, st, deferred=False):
     free = np.ones((ROWS, LANES), bool)
     heap = []  # (finish, job)
@@ -120,6 +151,8 @@ def replay(arr, dur, start, finish, st, deferred=False):
             f, j = heapq.heappop(heap)
             where = slot.pop(j)
             if where is None:
+                if -1 not in rows:
+                    st["batch-lane releases"] += 1
                 rows.add(-1)
                 st["jobs that finish in their batch lane"] += 1
                 continue
@@ -152,6 +185,7 @@ def replay(arr, dur, start, finish, st, deferred=False):
     def bulk_move():
         live = sorted(j for j, w in slot.items() if w is None)
         st["bulk moves" if live else "bulk moves, nothing live"] += 1
+        st["batch ends"] += 1
         # each row's candidates first (the rows' own free lanes), then the surplus one at a time
         left = []
         for j in live:
@@ -220,6 +254,7 @@ def replay(arr, dur, start, finish, st, deferred=False):
                 if adv1("failed fit"):
                     break
             st["longest sleep"] = max(st["longest sleep"], t - sleep0)
+        st["zero-duration jobs"] += not dur[k]
         if dur[k]:
             f = int(finish[k])
             heapq.heappush(heap, (f, k))
@@ -233,6 +268,7 @@ def replay(arr, dur, start, finish, st, deferred=False):
             st["waited"] += 1
             t += 1
             adv1("placed head")
+    st["exits"] += 1
 
 
 def main():
@@ -285,6 +321,16 @@ def main():
             change.setdefault("change per job", dict.fromkeys(("scalar", "branch", "vector", "lds"), 0.0))[f] += count * cost[i] / jobs
     change["change per job"] = {f: round(x, 2) for f, x in change["change per job"].items()}
     out["deferred_insert"] = {"replay": both, "instructions": change}
+    steps = {}
+    for step, events in LANE.items():
+        rows = {name: {"per_job": round(sd[n] / jobs, 4), "scalar, branch, vector, lds": list(cost)}
+                for name, (n, cost) in events.items()}
+        rows["change per job"] = {f: round(sum(sd[n] * cost[i] for n, cost in events.values()) / jobs, 2)
+                                  for i, f in enumerate(("scalar", "branch", "vector", "lds"))}
+        steps[step] = rows
+    steps["kept (A + C): change per job"] = {f: round(steps["A"]["change per job"][f] + steps["C"]["change per job"][f], 2)
+                                             for f in ("scalar", "branch", "vector", "lds")}
+    out["lane_results"] = steps
     print(json.dumps(out, indent=1))
 
 
