@@ -294,7 +294,24 @@ int mcs_resource_utilization(mcs_engine* eng, uint32_t cluster, float* core_util
  * (trader_server.go:24-47) would send at simulated second t_s, rebuilt from the last FIFO/DELAY
  * run's placements: the counters after second t_s (jobs with start <= t_s < finish hold their
  * node), GetResourceUtilization over them (cluster.go:46-63, float32 in node order) and the Run
- * totals (cluster.go:26-40).  average_wait_time (trader_server.go:39) is not in this record: under
+ * totals (cluster.go:26-40).
+ * After a FIFO trading run (MCS_POLICY_FIFO with borrow and/or trader; mcs_run or mcs_trade_begin ..
+ * mcs_trade_end) the record is defined by the own placements plus the lent runs (mcs_read_lent):
+ *   - a node is also held by every lent run whose lender is this cluster and whose
+ *     start_s <= t_s < finish_s, with the cores and memory of job `job` of cluster `borrower`
+ *     (scheduler.go:277-290); a zero-duration run holds nothing;
+ *   - running counts the own jobs and the lent runs holding at t_s;
+ *   - a job moved to the BorrowedQueue (MCS_NODE_BORROWED) is never running on its own cluster;
+ *   - a node index at or above the physical node count is a zero-capacity virtual node
+ *     (AddVirtualNode, cluster.go:65-85), which only a 0-core 0-memory job takes: the record counts
+ *     as running and adds to no node.  Utilization sums the physical nodes and divides by the Run
+ *     totals: a virtual node's term is float32(0) - float32(0) = +0 and the totals are not
+ *     recomputed (cluster.go:79), so virtual nodes change no bit;
+ *   - in the lock-step order of a tick (scheduler steps, borrow exchange, state samples, trader
+ *     rounds; mcs_trade.h) "the counters after second t_s" is the sample the Start stream sends at a
+ *     sample tick t_s.
+ * After a plain run an index >= the node count reads as unplaced, as it always did.
+ * average_wait_time (trader_server.go:39) is not in this record: under
  * DELAY it is mcs_wait_time_series at t_s (the value at the end of the run: mcs_read_delay_stats),
  * under FIFO it is 0, since only "/delay" feeds WaitTime. */
 typedef struct mcs_cluster_state {
@@ -306,8 +323,14 @@ typedef struct mcs_cluster_state {
     uint32_t t_s;
 } mcs_cluster_state;
 
-/* One gfx950 launch over every cluster (MCS_E_STATE after a trading run).  kernel_ms (may be
- * NULL) receives the launch's device time from HIP events on the engine stream. */
+/* One gfx950 launch over every cluster.  MCS_E_STATE, with the cause in mcs_last_error: before a run;
+ * after mcs_append_jobs; after a DELAY trading run (Foreign jobs, wrapped counters and virtual nodes
+ * with capacity are not in this record); after a FIFO trading run on a sharded engine (a lent record
+ * does not carry the job's cores and memory, and the borrower's job records live on another rank),
+ * one whose lent log overflowed (MCS_FLAG_LOG_OVERFLOW: records were dropped) or one cut short by a
+ * slot-pool or LentQueue overflow.  The first call after a FIFO trading run sorts the lent log by
+ * lender on the device (kept until the next run).  kernel_ms (may be NULL) receives the device time
+ * of the launches from HIP events on the engine stream. */
 int mcs_cluster_states(mcs_engine* eng, uint32_t t_s, mcs_cluster_state* out, uint32_t n_clusters,
                        double* kernel_ms);
 
@@ -324,9 +347,15 @@ int mcs_cluster_states(mcs_engine* eng, uint32_t t_s, mcs_cluster_state* out, ui
 typedef struct mcs_cluster_sample {   /* 16 B */
     float cores_utilization;          /* as mcs_cluster_state, at t_k                        */
     float memory_utilization;
-    uint32_t running;                 /* jobs with start <= t_k < finish                      */
+    uint32_t running;                 /* jobs with start <= t_k < finish (after a FIFO trading run:
+                                         own jobs and lent runs, see mcs_cluster_state)       */
     uint32_t queued;                  /* jobs with arrival <= t_k that have not started by t_k:
-                                         start > t_k, or never placed (MCS_NODE_UNPLACED)     */
+                                         start > t_k, or never placed (MCS_NODE_UNPLACED).  After a
+                                         FIFO trading run: own jobs that have not left the Ready and
+                                         Wait queues by t_k.  A borrowed job (MCS_NODE_BORROWED,
+                                         start = the borrow tick) is queued on [arrival, start); a
+                                         job undecided at t_max_s stays queued; LentQueue entries,
+                                         the lender's foreign work, are not counted             */
 } mcs_cluster_sample;
 
 /* Every sample t_k = t0_s + k * period_s, k < n_samples, of every cluster from one pass over the
@@ -334,8 +363,9 @@ typedef struct mcs_cluster_sample {   /* 16 B */
  * returns for cores_utilization, memory_utilization and running (float32 sums in node order).
  * out[c * n_samples + k] is cluster c at t_k.  first (may be NULL) receives the full record at t0_s:
  * the stream's first message, the only one that carries the totals (trader_server.go:28-34).
- * The preconditions are those of mcs_cluster_states (MCS_E_STATE before a run, after a trading run,
- * after mcs_append_jobs).  MCS_E_INVALID: period_s == 0, n_samples == 0, out == NULL, n_clusters
+ * The preconditions are those of mcs_cluster_states (MCS_E_STATE before a run, after
+ * mcs_append_jobs, after a DELAY trading run, and after a FIFO trading run that was sharded or
+ * overflowed); after a FIFO trading run the samples follow the trading semantics stated there.  MCS_E_INVALID: period_s == 0, n_samples == 0, out == NULL, n_clusters
  * above the engine's count, or a last sample past 0xFFFFFFFE.  kernel_ms (may be NULL) receives
  * the summed device time of the launches. */
 int mcs_cluster_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,

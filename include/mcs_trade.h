@@ -155,6 +155,12 @@ int mcs_trade_phase(mcs_engine* eng, uint32_t phase, const void* in, uint64_t in
 int mcs_trade_end(mcs_engine* eng, mcs_stats* stats);
 
 /* ---- results (after mcs_run or mcs_trade_end) ---------------------------------------------- */
+/* Besides the readers below, a FIFO trading run on one engine (rank 0 of world 1) leaves the
+ * ClusterState telemetry readable: mcs_cluster_states and mcs_cluster_state_series (mcs.h) rebuild
+ * the record from the own placements plus the lent runs, as the Start stream would sample it after
+ * the tick's scheduler steps and borrow exchange and before its trader rounds.  They return
+ * MCS_E_STATE on a sharded engine, after a lent-log overflow (MCS_FLAG_LOG_OVERFLOW) and after a
+ * DELAY trading run. */
 int mcs_read_trade_stats(mcs_engine* eng, mcs_trade_stats* out);
 /* Lent runs executed by this engine's clusters, sorted by (start_s, lender, borrower, job).
  * *n = total count (may exceed cap: then only cap records are written). */

@@ -822,15 +822,18 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
                        double* kernel_ms) {
     if (int st = check_engine(e)) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
-    if (e->trade_run || e->dtrade_run)
+    if (e->dtrade_run)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading");
+    mcs::StateArgs a{};
+    double prep_ms = 0.0;  // a FIFO trading run: its lent runs are the kernels' second stream
+    if (e->trade_run)
+        if (int st = mcs::trade_state_stream(e, &a, &prep_ms)) return st;
     if (e->segmented)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
     if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
     if (int st = mcs::ensure_job_records(e)) return st;
     mcs_cluster_state* d_out = nullptr;
     HIPCHK(e, hipMalloc(&d_out, (e->C ? e->C : 1) * sizeof(mcs_cluster_state)));
-    mcs::StateArgs a{};
     a.node_off = e->d_node_off;
     a.cap = e->d_cap;
     a.free0 = e->d_free0;
@@ -852,7 +855,7 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
         st = hipMemcpy(out, d_out, n_clusters * sizeof(mcs_cluster_state), hipMemcpyDeviceToHost);
     (void)hipFree(d_out);
     if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("cluster states: ") + hipGetErrorString(st));
-    if (kernel_ms) *kernel_ms = ms;
+    if (kernel_ms) *kernel_ms = ms + prep_ms;
     return MCS_OK;
 }
 
@@ -861,8 +864,12 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
                              double* kernel_ms) {
     if (int st = check_engine(e)) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
-    if (e->trade_run || e->dtrade_run)
+    if (e->dtrade_run)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading");
+    mcs::SeriesArgs a{};
+    double total_ms = 0.0;  // a FIFO trading run: its lent runs are the kernels' second stream
+    if (e->trade_run)
+        if (int st = mcs::trade_state_stream(e, &a.s, &total_ms)) return st;
     if (e->segmented)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
     if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
@@ -870,7 +877,6 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
         return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
     if (int st = mcs::ensure_job_records(e)) return st;
-    double total_ms = 0.0;
     if (first) {  // the stream's first message: the single record at t0_s
         double ms = 0.0;
         if (int st = mcs_cluster_states(e, t0_s, first, n_clusters, &ms)) return st;
@@ -890,7 +896,6 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     uint2* d_summ = nullptr;
     hipError_t st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_cluster_sample));
     if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(e->total_jobs, e->C) * sizeof(uint2));
-    mcs::SeriesArgs a{};
     a.s.node_off = e->d_node_off;
     a.s.cap = e->d_cap;
     a.s.free0 = e->d_free0;

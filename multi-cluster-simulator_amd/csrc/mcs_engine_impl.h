@@ -17,6 +17,11 @@ void trade_release_graphs(mcs_engine* e);  // the captured tick graphs only (bef
 void comm_free(mcs_engine* e);
 int trade_run(mcs_engine* e, mcs_stats* stats);
 int trade_cluster_stats(mcs_engine* e, mcs_cluster_stats* out, uint32_t n_clusters);
+// mcs_cluster_states / mcs_cluster_state_series after a FIFO trading run: MCS_E_STATE when the record
+// is not defined by this engine's results (sharded engine, overflowed run or lent log); else the
+// per-lender lent-run lists (built by the first call after a run, kept until the next run or
+// trade_free) go into a's second stream.  *prep_ms: device time of the pre-pass if this call ran it.
+int trade_state_stream(mcs_engine* e, StateArgs* a, double* prep_ms);
 struct DtradeDev;  // mcs_dtrade.cpp: lock-step trading with DELAY schedulers
 void dtrade_free(mcs_engine* e);
 void dtrade_release_graphs(mcs_engine* e);

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/mcs.h"
+#include "../../include/mcs_trade.h"
 
 namespace mcs {
 
@@ -120,6 +120,15 @@ constexpr uint32_t kDelayBail = 0x40000000u;
 bool delay_asm_eligible(int npl, int pool, uint32_t guard_ok, bool gen_on);
 hipError_t launch_delay_asm(const DelayArgs& a, hipStream_t s);
 
+// One lent run as the ClusterState kernels read it (mcs_state.hip, lent_scatter_kernel): the run
+// holds {cores, mem} of node `node` of its lender over [start, finish); node >= the lender's
+// physical node count is a zero-capacity virtual node (the run counts as running, no node row)
+struct LentRun {
+    uint32_t node, start, finish, cores;
+    uint32_t mem, pad0, pad1, pad2;
+};
+static_assert(sizeof(LentRun) == 32, "two 16 B loads");
+
 struct StateArgs {  // the ClusterState reduction over a run's placements (mcs_state.hip)
     const uint32_t* node_off;
     const uint2* cap;
@@ -132,8 +141,32 @@ struct StateArgs {  // the ClusterState reduction over a run's placements (mcs_s
     mcs_cluster_state* out;
     uint32_t t;
     uint32_t n_clusters;
+    // the second stream of a FIFO trading run (null after a plain run: the plain kernels never read
+    // these): per lender the lent runs [lent_off[c], lent_off[c + 1]) of `lent`, in no promised order
+    const uint32_t* lent_off;
+    const LentRun* lent;
+    const uint2* lent_summ;  // {earliest start from here on, finish_max} per kSeriesBatch lent runs
 };
 hipError_t launch_state(const StateArgs& a, uint32_t max_n, hipStream_t s);  // mcs_state.hip
+
+// The pre-pass over a FIFO trading run's lent log (mcs_state.hip): count per chunk and lender,
+// exclusive scans, scatter with the borrower's cores and memory, summaries.  One engine holds the whole system
+// (base 0): lender and borrower are local indices.
+struct LentPrepArgs {
+    const mcs_lent_rec* log;  // execution order
+    uint64_t n;               // records in the log (below 2^32)
+    const uint4* jobs;
+    const uint64_t* job_off;
+    uint32_t n_clusters;
+    uint32_t n_chunks;  // lent_chunks(n)
+    uint32_t* cnt;      // [n_chunks][n_clusters]: records per chunk and lender, then their offsets
+    uint32_t* off;      // [n_clusters + 1]
+    uint32_t* cursor;   // [n_clusters + 1]: the lists' lengths
+    LentRun* runs;      // [n]
+    uint2* summ;        // lent_summ_size() pairs
+};
+uint32_t lent_chunks(uint64_t n_lent);  // chunks of the log the pre-pass cuts it in
+hipError_t launch_lent_prep(const LentPrepArgs& a, hipStream_t s);
 
 // The ClusterState time series (mcs_state.hip, series_kernel): samples t0 + k * period, k < n_samples.
 struct SeriesArgs {
@@ -158,6 +191,10 @@ __host__ __device__ inline uint32_t series_tile(uint32_t n_nodes) {
 // cluster c's summaries start at job_off[c] / kSeriesBatch + c
 inline size_t series_summ_size(uint64_t total_jobs, uint32_t n_clusters) {
     return (size_t)(total_jobs / kSeriesBatch) + n_clusters + 1;
+}
+// lender c's lent-run summaries start at lent_off[c] / kSeriesBatch + c
+inline size_t lent_summ_size(uint64_t n_lent, uint32_t n_clusters) {
+    return (size_t)(n_lent / kSeriesBatch) + n_clusters + 1;
 }
 hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s);
 hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t s);

@@ -12,6 +12,24 @@
 // is scanned with coalesced 4 B loads; only the jobs running at t load their record's cores and
 // memory.  Per-node usage accumulates in LDS with u32 atomics; the float32 sum is serial in node
 // order (lane 0), as Go's loop is.  HBM-bound: 12 B per job scanned plus 8 B per running job.
+//
+// After a FIFO trading run (policy FIFO with borrow and/or trader) the kernels are
+// the TRADE instantiations and read a second stream, the lender's lent runs:
+//   - a node is also held by every lent run of this lender with start <= t < finish, with the cores
+//     and memory of the borrower's job (scheduler.go:277-290); the run counts in `running` and never
+//     in `queued` (the LentQueue is the lender's foreign work);
+//   - an own job moved to the BorrowedQueue (MCS_NODE_BORROWED, start = the borrow tick) is queued on
+//     [arrival, start) and never running here; a job undecided at t_max_s stays queued;
+//   - a node index at or above the physical node count is a zero-capacity virtual node
+//     (AddVirtualNode, cluster.go:65-85), which only a 0-core 0-memory job takes: the record counts
+//     as placed and running and touches no node row (every row index is guarded by k < N).  The
+//     utilization sums run over the physical nodes only: a virtual node's term is
+//     float32(0) - float32(0) = +0, and x + (+0) = x for every partial sum x these sums reach (they
+//     start at +0 and never reach -0), and the totals are not recomputed (cluster.go:79), so the
+//     virtual nodes change no bit.
+// The plain instantiations read an index >= N as "unplaced", as they always did, and never touch the
+// second stream.  lent_hist / lent_chunk_scan / lent_scan / lent_scatter / lent_summary_kernel build
+// the per-lender lists from the engine's lent log (execution order, 32 B records) once per run.
 #include "mcs_internal.h"
 #include "mcs_wave.h"
 
@@ -21,6 +39,7 @@ namespace {
 
 constexpr int kStateThreads = 256;
 
+template <bool TRADE>
 __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
     extern __shared__ uint32_t used[];  // [2 * max_n]: cores then memory per node
     const uint32_t c = blockIdx.x;
@@ -42,11 +61,34 @@ __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
         const int32_t k = __builtin_nontemporal_load(node + i);
         const uint32_t s = __builtin_nontemporal_load(start + i);
         const uint32_t f = __builtin_nontemporal_load(finish + i);
-        if (k >= 0 && (uint32_t)k < N && s <= t && t < f) {
+        if constexpr (TRADE) {
+            if (k >= 0 && s <= t && t < f) {
+                if ((uint32_t)k < N) {  // (a virtual node has no row)
+                    const uint2 cm = *reinterpret_cast<const uint2*>(&jobs[i].z);
+                    atomicAdd(&used[k], cm.x);
+                    atomicAdd(&used[N + k], cm.y);
+                }
+                ++nrun;
+            }
+        } else if (k >= 0 && (uint32_t)k < N && s <= t && t < f) {
             const uint2 cm = *reinterpret_cast<const uint2*>(&jobs[i].z);
             atomicAdd(&used[k], cm.x);
             atomicAdd(&used[N + k], cm.y);
             ++nrun;
+        }
+    }
+    if constexpr (TRADE) {  // the lender's lent runs, in any order
+        const uint32_t l0 = a.lent_off[c], nl = a.lent_off[c + 1] - l0;
+        const uint4* __restrict__ lr = reinterpret_cast<const uint4*>(a.lent + l0);
+        for (uint32_t i = tid; i < nl; i += kStateThreads) {
+            const uint4 r = lr[2u * i];  // {node, start, finish, cores}
+            if (r.y <= t && t < r.z) {
+                if (r.x < N) {
+                    atomicAdd(&used[r.x], r.w);
+                    atomicAdd(&used[N + r.x], lr[2u * i + 1u].x);
+                }
+                ++nrun;
+            }
         }
     }
     // running-job count: wave sums, then one LDS add per wave
@@ -101,6 +143,7 @@ __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kGroup = 8;  // hit batches whose records a thread loads before it uses the first
 
+template <bool TRADE>
 __global__ __launch_bounds__(kStateThreads) void series_summary_kernel(SeriesArgs a) {
     const uint32_t c = blockIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -109,9 +152,12 @@ __global__ __launch_bounds__(kStateThreads) void series_summary_kernel(SeriesArg
     const uint64_t J = a.s.job_off[c + 1] - j0;
     const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
     const int32_t* __restrict__ node = a.s.out_node + j0;
+    const uint32_t* __restrict__ start = a.s.out_start + j0;
     const uint32_t* __restrict__ finish = a.s.out_finish + j0;
     const uint4* __restrict__ jobs = a.s.jobs + j0;
     uint2* __restrict__ summ = a.summ + (j0 / kSeriesBatch + c);
+    (void)start;
+    (void)N;
     for (uint64_t b = wave; b < nb; b += kStateThreads / kWave) {
         uint32_t amin = kNone, emax = 0u;
 #pragma unroll
@@ -120,7 +166,11 @@ __global__ __launch_bounds__(kStateThreads) void series_summary_kernel(SeriesArg
             if (i < J) {
                 const uint32_t arr = jobs[i].x;
                 const int32_t k = node[i];
-                const uint32_t end = (k >= 0 && (uint32_t)k < N) ? finish[i] : kNone;  // unplaced: queued for good
+                uint32_t end;
+                if constexpr (TRADE)  // borrowed: out of the queue at its borrow tick; undecided: queued for good
+                    end = k >= 0 ? finish[i] : (k == MCS_NODE_BORROWED ? start[i] : kNone);
+                else
+                    end = (k >= 0 && (uint32_t)k < N) ? finish[i] : kNone;  // unplaced: queued for good
                 amin = arr < amin ? arr : amin;
                 emax = end > emax ? end : emax;
             }
@@ -142,6 +192,7 @@ __device__ __forceinline__ void range_add(uint32_t* row, uint32_t lo, uint32_t h
     }
 }
 
+template <bool TRADE>
 __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
     extern __shared__ uint32_t d[];   // [2 N + 2 kSeriesRep + 2][TS]
     __shared__ uint64_t masks[3][4];  // hit / dead / past ballots of a summary round, per wave
@@ -190,6 +241,16 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
     const float ftc = (float)tot[0], ftm = (float)tot[1];
 
     uint64_t b_lo = 0;  // every batch below ended at or before the current tile's first sample
+    // (TRADE) the lender's lent runs and their summaries, with a cursor of their own
+    uint32_t lb_lo = 0, lent_n = 0;
+    const uint4* __restrict__ lr = nullptr;
+    const uint2* __restrict__ lsumm = nullptr;
+    if constexpr (TRADE) {
+        const uint32_t l0 = a.s.lent_off[c];
+        lent_n = a.s.lent_off[c + 1] - l0;
+        lr = reinterpret_cast<const uint4*>(a.s.lent + l0);
+        lsumm = a.s.lent_summ + (l0 / kSeriesBatch + c);
+    }
     for (uint32_t k0 = 0; k0 < n; k0 += TS) {
         const uint32_t tsa = n - k0 < TS ? n - k0 : TS;
         // both fit: the last sample of the series is at most 0xFFFFFFFE
@@ -211,6 +272,22 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
             return q >= tsa ? tsa : q + 1u;
         };
         auto apply = [&](int32_t k, uint32_t s, uint32_t f, uint4 jr) {
+            if constexpr (TRADE) {
+                // placed on a physical or a virtual node; borrowed: queued up to the borrow tick s
+                const bool placed = k >= 0, gone = placed || k == MCS_NODE_BORROWED;
+                if (jr.x > t_last || (placed && f <= t_first) || (!placed && gone && s <= t_first)) return;
+                const uint32_t ka = kt(jr.x), ks = gone ? kt(s) : tsa;
+                range_add(my_que, ka, ks, tsa, 1u);
+                if (placed) {
+                    const uint32_t kf = kt(f);
+                    range_add(my_run, ks, kf, tsa, 1u);
+                    if ((uint32_t)k < N) {  // (a virtual node has no row)
+                        if (jr.z) range_add(d + (uint32_t)k * TS, ks, kf, tsa, jr.z);
+                        if (jr.w) range_add(d + (N + (uint32_t)k) * TS, ks, kf, tsa, jr.w);
+                    }
+                }
+                return;
+            }
             const bool placed = k >= 0 && (uint32_t)k < N;
             if (jr.x > t_last || (placed && f <= t_first)) return;
             const uint32_t ka = kt(jr.x), ks = placed ? kt(s) : tsa;
@@ -287,6 +364,74 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
             __syncthreads();  // masks and hits are rewritten by the next round
             if (any_past) break;
         }
+        if constexpr (TRADE) {
+            // the lender's lent runs, as the own jobs above: the summaries are tested from a cursor that
+            // skips the leading batches that ended before the tile (they stay ended: tiles only move
+            // on) up to the first batch whose x is past the tile.  x is the earliest start of the
+            // batch AND of every batch behind it (lent_summary_kernel), so that break is right in
+            // whatever order the lists are.  A hit batch is read by the whole workgroup; every run is
+            // tested on its own.  A run feeds the running row and its node's two rows, never the queue.
+            const uint32_t nl = lent_n;
+            const uint32_t nlb = (nl + kSeriesBatch - 1u) / kSeriesBatch;
+            bool lleading = true;
+            for (uint32_t base = lb_lo; base < nlb; base += kStateThreads) {
+                const uint32_t b = base + tid;
+                bool hit = false, dead = false, past = false;
+                if (b < nlb) {
+                    const uint2 s = lsumm[b];
+                    past = s.x > t_last;
+                    dead = s.y <= t_first;
+                    hit = !past && !dead;
+                }
+                const uint64_t hm = __ballot(hit), dm = __ballot(dead), pm = __ballot(past);
+                if (lane == 0) {
+                    masks[0][wave] = hm;
+                    masks[1][wave] = dm;
+                    masks[2][wave] = pm;
+                }
+                __syncthreads();
+                uint32_t lead = 0, n_hit = 0, before = 0;
+                bool counting = lleading, any_past = false;
+                for (uint32_t w = 0; w < 4; ++w) {
+                    any_past |= masks[2][w] != 0;
+                    if (w == wave) before = n_hit;
+                    n_hit += (uint32_t)__popcll(masks[0][w]);
+                    if (counting) {
+                        const uint64_t live = ~masks[1][w];
+                        if (live == 0) {
+                            lead += 64u;
+                        } else {
+                            lead += (uint32_t)__builtin_ctzll(live);
+                            counting = false;
+                        }
+                    }
+                }
+                if (hit) hits[before + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull))] = tid;
+                __syncthreads();
+                n_hit = sgpr(n_hit);
+                for (uint32_t h = 0; h < n_hit; ++h) {
+                    const uint32_t i = (base + hits[h]) * kSeriesBatch + tid;
+                    if (i < nl) {
+                        const uint4 r = lr[2u * i];  // {node, start, finish, cores}
+                        if (r.y <= t_last && r.z > t_first) {
+                            const uint32_t ks = kt(r.y), kf = kt(r.z);
+                            range_add(my_run, ks, kf, tsa, 1u);
+                            if (r.x < N) {  // (a virtual node has no row)
+                                const uint32_t m = lr[2u * i + 1u].x;
+                                if (r.w) range_add(d + r.x * TS, ks, kf, tsa, r.w);
+                                if (m) range_add(d + (N + r.x) * TS, ks, kf, tsa, m);
+                            }
+                        }
+                    }
+                }
+                if (lleading) {
+                    lb_lo += lead;
+                    lleading = lead == kStateThreads;
+                }
+                __syncthreads();  // masks and hits are rewritten by the next round
+                if (any_past) break;
+            }
+        }
         __syncthreads();
 
         // prefix sums along the samples, one thread per row; node rows leave their float32 term
@@ -339,11 +484,179 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
     }
 }
 
+// ---- the pre-pass over a FIFO trading run's lent log ---------------------------------------------
+//
+// The log is in execution order (starts ascend), every lender's records interleaved.  A counting
+// sort by lender that keeps that order chunk by chunk: the log is cut in chunks of kLentChunk records;
+// lent_hist_kernel counts each chunk's records per lender, lent_chunk_scan_kernel turns a lender's
+// counts into the chunk's offset within the lender's list (and the list's length), lent_scan_kernel
+// lays the lists out (exclusive scan over the lenders), lent_scatter_kernel moves the records, with
+// the cores and memory of the borrower's job record.  Lender c's runs end up contiguous at
+// [off[c], off[c + 1]), chunk after chunk, in no fixed order within a chunk: near enough to start
+// order for the batch summaries to be narrow, and no reader assumes more.  A
+// zero-duration run (finish == start) holds nothing; it is stored and joins no summary.
+constexpr uint32_t kPrepThreads = 256;
+constexpr uint32_t kLentChunk = 16u * kPrepThreads;
+constexpr uint32_t kPrepMaxClusters = 1024;  // LDS counters per chunk (the trading path's cluster limit)
+
+__global__ __launch_bounds__(kPrepThreads) void lent_hist_kernel(LentPrepArgs a) {
+    __shared__ uint32_t hist[kPrepMaxClusters];
+    const uint32_t tid = threadIdx.x, C = a.n_clusters;
+    for (uint32_t l = tid; l < C; l += kPrepThreads) hist[l] = 0u;
+    __syncthreads();
+    const uint64_t i0 = (uint64_t)blockIdx.x * kLentChunk;
+#pragma unroll 4
+    for (uint32_t u = 0; u < kLentChunk / kPrepThreads; ++u) {
+        const uint64_t i = i0 + u * kPrepThreads + tid;
+        if (i < a.n) {
+            const uint32_t l = a.log[i].lender;
+            if (l < C) atomicAdd(&hist[l], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t l = tid; l < C; l += kPrepThreads) a.cnt[(size_t)blockIdx.x * C + l] = hist[l];
+}
+
+// one workgroup per lender: cnt[chunk][lender] becomes the records of the lender in the chunks
+// before (exclusive scan along the chunks), cursor[lender] their total
+__global__ __launch_bounds__(kPrepThreads) void lent_chunk_scan_kernel(LentPrepArgs a) {
+    __shared__ uint32_t part[kPrepThreads];
+    const uint32_t tid = threadIdx.x, l = blockIdx.x, C = a.n_clusters, nc = a.n_chunks;
+    const uint32_t per = (nc + kPrepThreads - 1u) / kPrepThreads;
+    const uint32_t lo = tid * per < nc ? tid * per : nc, hi = lo + per < nc ? lo + per : nc;
+    uint32_t sum = 0;
+    for (uint32_t ch = lo; ch < hi; ++ch) sum += a.cnt[(size_t)ch * C + l];
+    part[tid] = sum;
+    __syncthreads();
+    uint32_t acc = 0;
+    for (uint32_t w = 0; w < tid; ++w) acc += part[w];
+    for (uint32_t ch = lo; ch < hi; ++ch) {
+        const uint32_t n = a.cnt[(size_t)ch * C + l];
+        a.cnt[(size_t)ch * C + l] = acc;
+        acc += n;
+    }
+    if (tid == kPrepThreads - 1u) a.cursor[l] = acc;  // (the spans behind the last chunk are empty)
+}
+
+// one workgroup: off = exclusive scan of the list lengths (at most 1024 clusters, 4 per thread)
+__global__ __launch_bounds__(kPrepThreads) void lent_scan_kernel(LentPrepArgs a) {
+    __shared__ uint32_t part[kPrepThreads];
+    const uint32_t tid = threadIdx.x, C = a.n_clusters;
+    const uint32_t per = (C + kPrepThreads - 1u) / kPrepThreads;
+    const uint32_t lo = tid * per < C ? tid * per : C, hi = lo + per < C ? lo + per : C;
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; ++i) sum += a.cursor[i];
+    part[tid] = sum;
+    __syncthreads();
+    uint32_t acc = 0;
+    for (uint32_t w = 0; w < tid; ++w) acc += part[w];
+    for (uint32_t i = lo; i < hi; ++i) {
+        a.off[i] = acc;
+        acc += a.cursor[i];
+    }
+    if (tid == kPrepThreads - 1u) a.off[C] = acc;
+}
+
+__global__ __launch_bounds__(kPrepThreads) void lent_scatter_kernel(LentPrepArgs a) {
+    __shared__ uint32_t cur[kPrepMaxClusters];
+    const uint32_t tid = threadIdx.x, C = a.n_clusters;
+    for (uint32_t l = tid; l < C; l += kPrepThreads) cur[l] = a.off[l] + a.cnt[(size_t)blockIdx.x * C + l];
+    __syncthreads();
+    const uint64_t i0 = (uint64_t)blockIdx.x * kLentChunk;
+#pragma unroll 4
+    for (uint32_t u = 0; u < kLentChunk / kPrepThreads; ++u) {
+        const uint64_t i = i0 + u * kPrepThreads + tid;
+        if (i >= a.n) continue;
+        const mcs_lent_rec r = a.log[i];
+        if (r.lender >= C) continue;  // (not counted either)
+        const uint32_t at = atomicAdd(&cur[r.lender], 1u);
+        if (at >= a.n) continue;
+        uint4 jr = make_uint4(0u, 0u, 0u, 0u);
+        bool ok = r.borrower < C;
+        if (ok) {
+            const uint64_t j0 = a.job_off[r.borrower];
+            ok = r.job < a.job_off[r.borrower + 1] - j0;
+            if (ok) jr = a.jobs[j0 + r.job];
+        }
+        // (a record that names no job of this engine holds nothing: an empty range)
+        uint4* out = reinterpret_cast<uint4*>(a.runs + at);
+        out[0] = make_uint4(r.node, r.start_s, ok ? r.finish_s : r.start_s, jr.z);
+        out[1] = make_uint4(jr.w, 0u, 0u, 0u);
+    }
+}
+
+// Per kSeriesBatch runs of a lender's list {x, finish_max}; an empty run joins neither.  x starts as
+// the batch's earliest start and becomes, in the second pass, the earliest start of the batch and of
+// every batch behind it (a suffix minimum): "x is past the tile" then holds for all later batches
+// too, in whatever order the list is.
+__global__ __launch_bounds__(kStateThreads) void lent_summary_kernel(LentPrepArgs a) {
+    __shared__ uint32_t part[kStateThreads];
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const uint32_t l0 = a.off[c], nl = a.off[c + 1] - l0;
+    const uint32_t nb = (nl + kSeriesBatch - 1u) / kSeriesBatch;
+    const uint4* __restrict__ lr = reinterpret_cast<const uint4*>(a.runs + l0);
+    uint2* summ = a.summ + (l0 / kSeriesBatch + c);
+    for (uint32_t b = wave; b < nb; b += kStateThreads / kWave) {
+        uint32_t smin = kNone, fmax = 0u;
+#pragma unroll
+        for (uint32_t u = 0; u < kSeriesBatch / kWave; ++u) {
+            const uint32_t i = b * kSeriesBatch + u * kWave + lane;
+            if (i < nl) {
+                const uint4 r = lr[2u * i];
+                if (r.y < r.z) {
+                    smin = r.y < smin ? r.y : smin;
+                    fmax = r.z > fmax ? r.z : fmax;
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t x = (uint32_t)__shfl_xor((int)smin, o), y = (uint32_t)__shfl_xor((int)fmax, o);
+            smin = x < smin ? x : smin;
+            fmax = y > fmax ? y : fmax;
+        }
+        if (lane == 0) summ[b] = make_uint2(smin, fmax);
+    }
+    __syncthreads();  // (the summaries above are this workgroup's own writes)
+    const uint32_t per = (nb + kStateThreads - 1u) / kStateThreads;
+    const uint32_t lo = tid * per < nb ? tid * per : nb, hi = lo + per < nb ? lo + per : nb;
+    uint32_t m = kNone;
+    for (uint32_t b = lo; b < hi; ++b) {
+        const uint32_t x = summ[b].x;
+        m = x < m ? x : m;
+    }
+    part[tid] = m;
+    __syncthreads();
+    uint32_t acc = kNone;
+    for (uint32_t w = tid + 1u; w < kStateThreads; ++w) acc = part[w] < acc ? part[w] : acc;
+    for (uint32_t b = hi; b-- > lo;) {
+        const uint32_t x = summ[b].x;
+        acc = x < acc ? x : acc;
+        summ[b].x = acc;
+    }
+}
+
 }  // namespace
+
+uint32_t lent_chunks(uint64_t n) { return (uint32_t)((n + kLentChunk - 1u) / kLentChunk); }
+
+hipError_t launch_lent_prep(const LentPrepArgs& a, hipStream_t s) {
+    if (a.n_clusters == 0) return hipSuccess;
+    if (a.n_clusters > kPrepMaxClusters || a.n_chunks != lent_chunks(a.n)) return hipErrorInvalidValue;
+    if (a.n_chunks) hipLaunchKernelGGL(lent_hist_kernel, dim3(a.n_chunks), dim3(kPrepThreads), 0, s, a);
+    hipLaunchKernelGGL(lent_chunk_scan_kernel, dim3(a.n_clusters), dim3(kPrepThreads), 0, s, a);
+    hipLaunchKernelGGL(lent_scan_kernel, dim3(1), dim3(kPrepThreads), 0, s, a);
+    if (a.n_chunks) hipLaunchKernelGGL(lent_scatter_kernel, dim3(a.n_chunks), dim3(kPrepThreads), 0, s, a);
+    hipLaunchKernelGGL(lent_summary_kernel, dim3(a.n_clusters), dim3(kStateThreads), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s) {
     if (a.s.n_clusters == 0) return hipSuccess;
-    hipLaunchKernelGGL(series_summary_kernel, dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
+    if (a.s.lent_off)
+        hipLaunchKernelGGL(series_summary_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(series_summary_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -353,16 +666,23 @@ hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t 
     if (max_n > 1024u) return hipErrorInvalidValue;  // the ABI's node limit: a tile of at least 9 samples
     uint32_t lds = 4u * series_rows(max_n) * kSeriesMaxTile;
     if (lds > kSeriesLds) lds = kSeriesLds;
-    hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void*>(series_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
+    const void* fn = a.s.lent_off ? reinterpret_cast<const void*>(series_kernel<true>)
+                                  : reinterpret_cast<const void*>(series_kernel<false>);
+    hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(series_kernel, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    if (a.s.lent_off)
+        hipLaunchKernelGGL(series_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    else
+        hipLaunchKernelGGL(series_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_state(const StateArgs& a, uint32_t max_n, hipStream_t s) {
     if (a.n_clusters == 0) return hipSuccess;
-    hipLaunchKernelGGL(state_kernel, dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);
+    if (a.lent_off)
+        hipLaunchKernelGGL(state_kernel<true>, dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);
+    else
+        hipLaunchKernelGGL(state_kernel<false>, dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);
     return hipGetLastError();
 }
 

@@ -55,7 +55,15 @@ struct TradeDev {
     uint32_t loop_form = kLoopGraph;
     bool begun = false;
     std::chrono::steady_clock::time_point w0;
+    float loop_ms = 0.0f;  // kernel_ms of the last run (mcs_trade_end; the engine's events are reused later)
+    // the ClusterState kernels' second stream (trade_state_stream): per-lender lent-run lists
+    bool lr_built = false;
+    uint32_t* lr_off = nullptr;
+    uint32_t* lr_cursor = nullptr;
+    LentRun* lr_runs = nullptr;
+    uint2* lr_summ = nullptr;
 };
+void lent_lists_free(TradeDev* td);
 
 namespace {
 
@@ -113,7 +121,9 @@ int trade_alloc(mcs_engine* e) {
     TradeDev* td = new (std::nothrow) TradeDev();
     if (!td) return fail(e, MCS_E_NOMEM, "trade state");
     e->td = td;
-    const uint64_t lent_cap = std::max<uint64_t>(1ull << 16, 16ull * e->total_jobs);
+    uint64_t lent_cap = std::max<uint64_t>(1ull << 16, 16ull * e->total_jobs);
+    if (const char* env = getenv("MCS_TRADE_LENT_LOG_CAP"))  // tests: a lent log that overflows
+        if (atoll(env) > 0) lent_cap = (uint64_t)atoll(env);
     const uint64_t trade_cap = 1ull << 22;
     HIPCHK(e, hipMalloc(&td->tn, std::max<uint64_t>(e->total_nodes, 1) * 8));
     HIPCHK(e, hipMalloc(&td->cl, Cl * sizeof(TrCluster)));
@@ -562,6 +572,7 @@ void trade_free(mcs_engine* e) {
     dfree(td->trades);
     dfree(td->lrp);
     dfree(td->tnr);
+    lent_lists_free(td);
     if (td->h_ctl) (void)hipHostFree(td->h_ctl);
     for (hipEvent_t& ev : td->pev)
         if (ev) (void)hipEventDestroy(ev);
@@ -570,6 +581,74 @@ void trade_free(mcs_engine* e) {
     delete td;
     e->td = nullptr;
     e->trade_run = false;
+}
+
+void lent_lists_free(TradeDev* td) {
+    dfree(td->lr_off);
+    dfree(td->lr_cursor);
+    dfree(td->lr_runs);
+    dfree(td->lr_summ);
+    td->lr_built = false;
+}
+
+int trade_state_stream(mcs_engine* e, StateArgs* a, double* prep_ms) {
+    TradeDev* td = e->td;
+    if (prep_ms) *prep_ms = 0.0;
+    if (!e->trade_run || !td) return fail(e, MCS_E_STATE, "no lock-step run");
+    if (e->world != 1)
+        return fail(e, MCS_E_STATE,
+                    "cluster states of a sharded trading run: a lent record does not carry the job's cores and "
+                    "memory, and the borrower's job records live on another rank (run the system on one engine)");
+    mcs_trade_stats ts{};
+    if (int s = fill_stats(e, &ts, nullptr)) return s;
+    if (ts.flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_LENT_OVERFLOW))
+        return fail(e, MCS_E_STATE, "cluster states of a trading run that overflowed its slot pool or a LentQueue: "
+                                    "the run stopped short of its results");
+    const uint64_t n = td->h_ctl->n_lent;
+    if (n > td->a.lent_cap)
+        return fail(e, MCS_E_STATE, "cluster states of a trading run whose lent log overflowed "
+                                    "(MCS_FLAG_LOG_OVERFLOW): lent runs were dropped");
+    if (n > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "more than 2^32 - 2 lent runs");
+    if (!td->lr_built) {
+        lent_lists_free(td);
+        HIPCHK(e, hipMalloc(&td->lr_off, (e->C + 1u) * sizeof(uint32_t)));
+        HIPCHK(e, hipMalloc(&td->lr_cursor, (e->C + 1u) * sizeof(uint32_t)));
+        HIPCHK(e, hipMalloc(&td->lr_runs, std::max<uint64_t>(n, 1) * sizeof(LentRun)));
+        HIPCHK(e, hipMalloc(&td->lr_summ, lent_summ_size(n, e->C) * sizeof(uint2)));
+        LentPrepArgs p{};
+        p.log = td->lent;
+        p.n = n;
+        p.jobs = e->d_jobs;
+        p.job_off = e->d_job_off;
+        p.n_clusters = e->C;
+        p.n_chunks = lent_chunks(n);
+        uint32_t* cnt = nullptr;  // (the pre-pass's scratch)
+        HIPCHK(e, hipMalloc(&cnt, std::max<size_t>((size_t)p.n_chunks * e->C, 1) * sizeof(uint32_t)));
+        p.cnt = cnt;
+        p.off = td->lr_off;
+        p.cursor = td->lr_cursor;
+        p.runs = td->lr_runs;
+        p.summ = td->lr_summ;
+        hipEvent_t p0 = nullptr, p1 = nullptr;
+        hipError_t st = hipEventCreate(&p0);
+        if (st == hipSuccess) st = hipEventCreate(&p1);
+        if (st == hipSuccess) st = hipEventRecord(p0, e->stream);
+        if (st == hipSuccess) st = launch_lent_prep(p, e->stream);
+        if (st == hipSuccess) st = hipEventRecord(p1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, p0, p1);
+        (void)hipFree(cnt);
+        if (p0) (void)hipEventDestroy(p0);
+        if (p1) (void)hipEventDestroy(p1);
+        if (st != hipSuccess) return hip_fail(e, "lent-run lists", st);
+        if (prep_ms) *prep_ms = ms;
+        td->lr_built = true;
+    }
+    a->lent_off = td->lr_off;
+    a->lent = td->lr_runs;
+    a->lent_summ = td->lr_summ;
+    return MCS_OK;
 }
 
 int trade_cluster_stats(mcs_engine* e, mcs_cluster_stats* out, uint32_t n) {
@@ -770,6 +849,7 @@ int mcs_trade_begin(mcs_engine* e) {
     td->rk_started = false;
     td->rk_tick = 0;
     td->end_ev = nullptr;
+    mcs::lent_lists_free(td);  // (the last run's lists)
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipEventRecord(e->ev0, e->stream));  // kernel_ms: the lock-step loop only
     td->begun = true;
@@ -917,6 +997,7 @@ int mcs_trade_end(mcs_engine* e, mcs_stats* stats) {
     if (int s = mcs::fill_stats(e, &ts, &st)) return s;
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, e->ev0, td->end_ev ? td->end_ev : e->ev1) != hipSuccess) ms = 0.0f;
+    td->loop_ms = ms;
     st.kernel_ms = ms;
     st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td->w0).count();
     if (stats) *stats = st;
@@ -934,9 +1015,7 @@ int mcs_read_trade_stats(mcs_engine* e, mcs_trade_stats* out) {
     if (!e->trade_run || !e->td) return fail(e, MCS_E_STATE, "no lock-step run");
     mcs_stats st{};
     if (int s = mcs::fill_stats(e, out, &st)) return s;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, e->ev0, e->td->end_ev ? e->td->end_ev : e->ev1) != hipSuccess) ms = 0.0f;
-    out->kernel_ms = ms;
+    out->kernel_ms = e->td->loop_ms;  // (mcs_cluster_states reuses the engine's events)
     out->wall_ms = 0.0;
     return MCS_OK;
 }

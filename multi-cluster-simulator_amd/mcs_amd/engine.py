@@ -429,7 +429,11 @@ class Engine:
 
     def cluster_states(self, t_s: int, with_time: bool = False):
         """ClusterState of every cluster at simulated second t_s, rebuilt on the GPU from the last
-        FIFO/DELAY run (mcs_cluster_states; CLUSTER_STATE_DTYPE).  with_time: also the kernel ms."""
+        FIFO/DELAY run (mcs_cluster_states; CLUSTER_STATE_DTYPE).  with_time: also the kernel ms.
+        After a FIFO trading run (borrow and/or trader, run() or trade_begin .. trade_end, one
+        engine) the lent runs hold their lender's nodes and count as running; a borrowed job is never
+        running on its own cluster.  MCSError (MCS_E_STATE) after a DELAY trading run, on a sharded
+        engine and after a run whose lent log overflowed."""
         n = self.num_clusters
         out = np.zeros(n, CLUSTER_STATE_DTYPE)
         ms = C.c_double(0.0)
@@ -441,7 +445,11 @@ class Engine:
         """The ClusterState time series of every cluster (mcs_cluster_state_series): samples
         t0_s + k * period_s, k < n_samples, as an array of shape (num_clusters, n_samples) of
         CLUSTER_SAMPLE_DTYPE, and the full records at t0_s (CLUSTER_STATE_DTYPE), the stream's first
-        messages.  Returns (samples, first); with_time: (samples, first, kernel ms)."""
+        messages.  Returns (samples, first); with_time: (samples, first, kernel ms).
+        After a FIFO trading run the samples follow cluster_states' trading semantics; queued counts
+        the own jobs still in the Ready and Wait queues: a borrowed job leaves at its borrow tick, a
+        job undecided at t_max_s stays, LentQueue entries are not counted.  A row feeds
+        wire.start_stream like a plain run's."""
         for v in (t0_s, period_s, n_samples):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
