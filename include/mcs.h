@@ -325,7 +325,8 @@ typedef struct mcs_cluster_state {
 
 /* One gfx950 launch over every cluster.  MCS_E_STATE, with the cause in mcs_last_error: before a run;
  * after mcs_append_jobs; after a DELAY trading run (Foreign jobs, wrapped counters and virtual nodes
- * with capacity are not in this record); after a FIFO trading run on a sharded engine (a lent record
+ * with capacity are not in this record: mcs_dtrade_state_series, mcs_trade.h, returns the record that
+ * has them); after a FIFO trading run on a sharded engine (a lent record
  * does not carry the job's cores and memory, and the borrower's job records live on another rank),
  * one whose lent log overflowed (MCS_FLAG_LOG_OVERFLOW: records were dropped) or one cut short by a
  * slot-pool or LentQueue overflow.  The first call after a FIFO trading run sorts the lent log by

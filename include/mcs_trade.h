@@ -182,6 +182,35 @@ int mcs_read_foreign(mcs_engine* eng, mcs_foreign_rec* out, uint64_t cap, uint64
 int mcs_read_virtual_node_caps(mcs_engine* eng, uint32_t cluster, uint32_t* cores, uint32_t* mem,
                                uint32_t cap, uint32_t* n);
 
+/* The ClusterState telemetry of a DELAY trading run on one engine (rank 0 of world 1), after
+ * mcs_run or mcs_trade_end: what the Start stream (trader_server.go:24-47) would have sent at the
+ * seconds t0_s + k * period_s, k < n_samples, sampled after the tick's Delay iteration and before its
+ * trader rounds.  out[c * n_samples + k] is cluster c's sample (mcs_cluster_sample, mcs.h), wait (may
+ * be NULL) the WaitTime statistics in the same shape (mcs_wait_sample), first (may be NULL) the full
+ * record at t0_s from a plain scan, n_clusters of them.  The three calls of mcs.h keep refusing such
+ * a run; this call refuses every other run.
+ *   - Rows: the cluster's physical nodes, then the virtual nodes it received, in order
+ *     (mcs_read_virtual_node_caps), each with capacity = initial free = its contract's {cores, mem}.
+ *     A virtual row is present from second 0: it holds nothing before its trade and its term is +0.
+ *   - An own job with node >= 0 holds its row (physical or virtual) on start <= t < finish; node -1
+ *     (undecided at t_max_s) is never running and stays queued.
+ *   - A Foreign job (mcs_foreign_rec, responder == c) holds {c, m} of row `node` on
+ *     start_s < t < finish_s: AllocateVirtualNodeResources runs after the sample of tick start_s.
+ *   - Counters are Go uint (uint64) and wrap: free = free0 - held (mod 2^64); a row's term is
+ *     float32(cap) - float32(free), summed in float32 in row order, divided by float32 of the totals
+ *     of the physical nodes (cluster.go:79: never recomputed).  Negative utilization is routine.
+ *   - running = own jobs plus Foreign jobs holding at t; queued = own jobs with arrival <= t that have
+ *     not started by t.  The wait statistics are those of mcs_wait_time_series over the run's
+ *     placements (they depend on no node); past the run's end the Go loop is continued.
+ * MCS_E_INVALID as mcs_cluster_state_series.  MCS_E_STATE, with the cause in mcs_last_error: before a
+ * run, after anything but a DELAY trading run, on a sharded engine, after a Foreign-log or
+ * contract-log overflow (MCS_FLAG_LOG_OVERFLOW), a virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW) or
+ * a run cut short by a capacity overflow, and after mcs_append_jobs.  MCS_DTRADE_FOREIGN_LOG_CAP in
+ * the environment lowers the Foreign log's capacity (tests).  *kernel_ms (may be NULL): device time. */
+int mcs_dtrade_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                            mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                            uint32_t n_clusters, double* kernel_ms);
+
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,
  * -1} (trader.go:47-52): a responder whose sample is {core_util, mem_util} and whose totals are

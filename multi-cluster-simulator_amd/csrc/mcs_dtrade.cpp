@@ -93,7 +93,10 @@ int dtrade_alloc(mcs_engine* e) {
     d->tag[2] = W;
     d->tag[3] = C;
     const size_t nj = e->total_jobs ? e->total_jobs : 1;
-    const uint64_t trade_cap = 1ull << 20, foreign_cap = 1ull << 22;
+    const uint64_t trade_cap = 1ull << 20;
+    uint64_t foreign_cap = 1ull << 22;
+    if (const char* env = getenv("MCS_DTRADE_FOREIGN_LOG_CAP"))  // tests: a Foreign log that overflows
+        if (atoll(env) > 0 && (uint64_t)atoll(env) < foreign_cap) foreign_cap = (uint64_t)atoll(env);
     HIPCHK(e, hipMalloc(&d->tn, std::max<uint64_t>(e->total_nodes, 1) * 8));
     HIPCHK(e, hipMalloc(&d->vn, (size_t)C * V * 8));
     HIPCHK(e, hipMalloc(&d->vcap, (size_t)C * V * sizeof(uint2)));
@@ -724,6 +727,126 @@ int mcs_read_virtual_node_caps(mcs_engine* e, uint32_t cluster, uint32_t* cores,
         }
     }
     *n = k.nv;
+    return MCS_OK;
+}
+
+// The ClusterState record and the wait statistics of a DELAY trading run: the third
+// form of the state kernels (mcs_state.hip, dt_*) over the placements, the virtual-node table and the
+// Foreign log, and the wait_*_kernels over the placements.
+int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                            mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                            uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (e->segmented)
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
+    if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
+    if (!e->dtrade_run || !e->dtd)
+        return fail(e, MCS_E_STATE, "mcs_dtrade_state_series reads a DELAY trading run (MCS_POLICY_DELAY with "
+                                    "cfg.trader); after any other run: mcs_cluster_state_series and "
+                                    "mcs_wait_time_series (mcs.h)");
+    if (e->world != 1)
+        return fail(e, MCS_E_STATE, "cluster states of a sharded DELAY trading run: the placements of the other "
+                                    "ranks' clusters live there (run the system on one engine)");
+    mcs::DtradeDev* d = e->dtd;
+    std::vector<mcs::DtCluster> cl;
+    if (int st = mcs::dt_clusters(e, cl)) return st;
+    const mcs::DtCtl ctl = *d->h_ctl;
+    uint32_t flags = ctl.flags;
+    for (uint32_t k = 0; k < e->C; ++k) flags |= cl[k].flags;
+    if (flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))
+        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run that a slot-pool overflow or a "
+                                    "virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW) cut short");
+    if ((flags & MCS_FLAG_LOG_OVERFLOW) || ctl.n_foreign > d->a.foreign_cap || ctl.n_trades > d->a.trade_cap)
+        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run whose Foreign or contract log "
+                                    "overflowed (MCS_FLAG_LOG_OVERFLOW): records were dropped");
+    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
+    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
+    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
+        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+    if (ctl.n_foreign > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "more than 2^32 - 2 Foreign jobs");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    if (n_clusters == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return MCS_OK;
+    }
+    double total_ms = 0.0;
+    if (wait) {  // (its own argument checks repeat the ones above and add the per-cluster job limit)
+        double ms = 0.0;
+        if (int st = mcs::wait_series(e, t0_s, period_s, n_samples, wait, n_clusters, &ms)) return st;
+        total_ms += ms;
+    }
+    const uint32_t V = d->a.V;
+    std::vector<uint32_t> nv(e->C);
+    uint32_t max_nn = 1;
+    for (uint32_t k = 0; k < e->C; ++k) {
+        nv[k] = std::min(cl[k].nv, V);
+        max_nn = std::max(max_nn, e->node_off[k + 1] - e->node_off[k] + nv[k]);
+    }
+    // samples per launch: the device buffer stays within 256 MiB (MCS_SERIES_CHUNK overrides the count)
+    uint64_t chunk = (256ull << 20) / (sizeof(mcs_cluster_sample) * (uint64_t)n_clusters);
+    if (const char* env = getenv("MCS_SERIES_CHUNK"))
+        if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_samples) chunk = n_samples;
+    uint32_t* d_nv = nullptr;
+    mcs_cluster_sample* d_out = nullptr;
+    mcs_cluster_state* d_first = nullptr;
+    uint2* d_summ = nullptr;
+    hipError_t st = hipMalloc(&d_nv, e->C * sizeof(uint32_t));
+    if (st == hipSuccess) st = hipMemcpy(d_nv, nv.data(), e->C * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (st == hipSuccess) st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_cluster_sample));
+    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(e->total_jobs, e->C) * sizeof(uint2));
+    if (st == hipSuccess && first) st = hipMalloc(&d_first, n_clusters * sizeof(mcs_cluster_state));
+    mcs::DtSeriesArgs a{};
+    a.d.s.node_off = e->d_node_off;
+    a.d.s.cap = e->d_cap;
+    a.d.s.free0 = e->d_free0;
+    a.d.s.jobs = e->d_jobs;
+    a.d.s.job_off = e->d_job_off;
+    a.d.s.out_node = e->d_out_node;
+    a.d.s.out_start = e->d_out_start;
+    a.d.s.out_finish = e->d_out_finish;
+    a.d.s.out = d_first;
+    a.d.s.t = t0_s;
+    a.d.s.n_clusters = n_clusters;
+    a.d.vcap = d->vcap;
+    a.d.nv = d_nv;
+    a.d.flog = d->foreign;
+    a.d.n_foreign = (uint32_t)ctl.n_foreign;
+    a.d.V = V;
+    a.summ = d_summ;
+    a.out = d_out;
+    a.period = period_s;
+    a.magic = period_s > 1 ? ~0ull / period_s + 1ull : 0ull;
+    for (uint64_t k0 = 0; st == hipSuccess && k0 < n_samples; k0 += chunk) {
+        const uint32_t nk = (uint32_t)(n_samples - k0 < chunk ? n_samples - k0 : chunk);
+        a.t0 = (uint32_t)(t0_s + k0 * period_s);
+        a.n_samples = nk;
+        st = hipEventRecord(e->ev0, e->stream);
+        if (st == hipSuccess && k0 == 0) {
+            // the stream's first message: a plain scan at t0_s, independent of the tile walk
+            if (first) st = mcs::launch_dt_state(a.d, max_nn, e->stream);
+            if (st == hipSuccess) st = mcs::launch_dt_series_summary(a, e->stream);
+        }
+        if (st == hipSuccess) st = mcs::launch_dt_state_series(a, max_nn, e->stream);
+        if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
+        total_ms += ms;
+        if (st == hipSuccess)  // the chunk's columns of every cluster's row
+            st = hipMemcpy2D(out + k0, (size_t)n_samples * sizeof(mcs_cluster_sample), d_out,
+                             (size_t)nk * sizeof(mcs_cluster_sample), (size_t)nk * sizeof(mcs_cluster_sample),
+                             n_clusters, hipMemcpyDeviceToHost);
+    }
+    if (st == hipSuccess && first)
+        st = hipMemcpy(first, d_first, n_clusters * sizeof(mcs_cluster_state), hipMemcpyDeviceToHost);
+    (void)hipFree(d_nv);
+    (void)hipFree(d_out);
+    (void)hipFree(d_summ);
+    if (d_first) (void)hipFree(d_first);
+    if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("DELAY trading state series: ") + hipGetErrorString(st));
+    if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
 }
 

@@ -823,7 +823,8 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
     if (int st = check_engine(e)) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
     if (e->dtrade_run)
-        return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading");
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading "
+                                    "(after a DELAY trading run: mcs_dtrade_state_series)");
     mcs::StateArgs a{};
     double prep_ms = 0.0;  // a FIFO trading run: its lent runs are the kernels' second stream
     if (e->trade_run)
@@ -865,7 +866,8 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     if (int st = check_engine(e)) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
     if (e->dtrade_run)
-        return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading");
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading "
+                                    "(after a DELAY trading run: mcs_dtrade_state_series)");
     mcs::SeriesArgs a{};
     double total_ms = 0.0;  // a FIFO trading run: its lent runs are the kernels' second stream
     if (e->trade_run)
@@ -938,9 +940,19 @@ int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32
     if (int st = check_engine(e)) return st;
     if (!e->has_run || !e->delay_run) return fail(e, MCS_E_STATE, "no DELAY run");
     if (e->trade_run || e->dtrade_run)
-        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from a DELAY run without trading");
+        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from a DELAY run without trading "
+                                    "(after a DELAY trading run: mcs_dtrade_state_series)");
     if (e->segmented)
         return fail(e, MCS_E_STATE, "the wait time series is rebuilt from batch runs (not after mcs_append_jobs)");
+    return mcs::wait_series(e, t0_s, period_s, n_samples, out, n_clusters, kernel_ms);
+}
+
+}  // extern "C"
+
+// WaitTime depends on arrivals, starts and max_wait_s alone (k >= 0 && start != none is the only
+// placement test of wait_prep_kernel), so the same kernels serve a DELAY trading run's placements
+int mcs::wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_wait_sample* out,
+                     uint32_t n_clusters, double* kernel_ms) {
     if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
     if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
     if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
@@ -1002,5 +1014,3 @@ int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32
     if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
 }
-
-}  // extern "C"

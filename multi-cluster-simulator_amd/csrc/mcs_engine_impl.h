@@ -41,6 +41,10 @@ int dtrade_phase(mcs_engine* e, uint32_t phase, const void* in, uint64_t in_byte
                  uint64_t out_bytes, uint32_t* done);
 int dtrade_end(mcs_engine* e, mcs_stats* stats);
 inline bool is_dtrade(const mcs_engine* e);
+// the body of mcs_wait_time_series behind its state checks (mcs_engine.cpp): the wait_*_kernels over
+// the engine's placements, whichever DELAY run wrote them (mcs_dtrade_state_series reuses it)
+int wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_wait_sample* out,
+                uint32_t n_clusters, double* kernel_ms);
 // online mode (mcs_online.cpp)
 void online_free(mcs_engine* e);
 int online_begin(mcs_engine* e);

@@ -199,6 +199,37 @@ inline size_t lent_summ_size(uint64_t n_lent, uint32_t n_clusters) {
 hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s);
 hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t s);
 
+// The record after a DELAY trading run (mcs_state.hip, dt_state_kernel / dt_series_kernel; world 1,
+// so global and local cluster indices coincide).  Cluster c has its N physical rows and then nv[c]
+// virtual rows with cap = free0 = vcap[c * V + i]; counters are Go uint64.  The Foreign log is read
+// as it is: launch order, every responder's records interleaved.
+struct DtStateArgs {
+    StateArgs s;                  // the run's placements (lent_* stay null)
+    const uint2* vcap;            // [s.n_clusters][V]
+    const uint32_t* nv;           // [s.n_clusters], each at most V
+    const mcs_foreign_rec* flog;  // n_foreign records
+    uint32_t n_foreign;
+    uint32_t V;
+};
+struct DtSeriesArgs {
+    DtStateArgs d;            // d.s.out and d.s.t are not used
+    uint2* summ;              // as SeriesArgs::summ (the TRADE summaries: end = finish of every placed job)
+    mcs_cluster_sample* out;  // [d.s.n_clusters][n_samples], cluster-major
+    uint32_t t0, period, n_samples;
+    unsigned long long magic;
+};
+// samples per tile of a cluster of nn = N + nv rows: 2 nn LDS rows of u64, then the u32 rows of
+// series_rows(0); odd, as series_tile.  nn <= 1280 leaves a tile of 3 samples.
+__host__ __device__ inline uint32_t dt_series_bytes(uint32_t nn) { return 16u * nn + 4u * series_rows(0); }
+__host__ __device__ inline uint32_t dt_series_tile(uint32_t nn) {
+    uint32_t ts = kSeriesLds / dt_series_bytes(nn);
+    if (ts > kSeriesMaxTile) ts = kSeriesMaxTile;
+    return (ts - 1u) | 1u;
+}
+hipError_t launch_dt_state(const DtStateArgs& a, uint32_t max_nn, hipStream_t s);
+hipError_t launch_dt_series_summary(const DtSeriesArgs& a, hipStream_t s);
+hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStream_t s);
+
 // The average wait time series of a DELAY run (mcs_wait.hip): WaitTime after the Delay iteration at
 // the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters.
 struct WaitArgs {

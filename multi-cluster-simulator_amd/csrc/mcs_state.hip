@@ -30,6 +30,9 @@
 // The plain instantiations read an index >= N as "unplaced", as they always did, and never touch the
 // second stream.  lent_hist / lent_chunk_scan / lent_scan / lent_scatter / lent_summary_kernel build
 // the per-lender lists from the engine's lent log (execution order, 32 B records) once per run.
+//
+// After a DELAY trading run (mcs_dtrade_state_series) dt_state_kernel and dt_series_kernel, further
+// down, rebuild the record with virtual-node rows, Foreign jobs and 64-bit wrapping counters.
 #include "mcs_internal.h"
 #include "mcs_wave.h"
 
@@ -484,6 +487,303 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
     }
 }
 
+// ---- the record after a DELAY trading run ----------------------------------------
+//
+// The third form of the three kernels, kernels of their own so that the plain and the TRADE
+// instantiations above stay the code they are.  What differs:
+//   - cluster c has NN = N + nv rows: its physical nodes, then the virtual nodes it received, whose
+//     capacity and initial free counters are the contract's {cores, mem} (AddVirtualNode,
+//     cluster.go:65-85).  A virtual row holds nothing before its trade, so its term is +0 until then.
+//     An own job's node index runs over NN; every row index is guarded by k < NN.
+//   - the counters are Go uint64: free = free0 - held (mod 2^64), the term is
+//     float32(cap) - float32(uint64 free), round to nearest even.  The rows accumulate in 64-bit LDS
+//     words with 64-bit atomics; differences and prefix sums wrap mod 2^64, which is exact.
+//   - a Foreign job (mcs_foreign_rec with responder == c) holds {c, m} of its row on
+//     start_s < t < finish_s: AllocateVirtualNodeResources runs in phase D of tick start_s, after that
+//     tick's sample.  It counts in `running`, never in `queued`.  The log is scanned as it is by every
+//     workgroup (C5-DELAY logs 232 records, 9 KB, §13); no order is assumed, the loop is bounded by
+//     the record count passed at launch.
+//   - the utilization sums run over the NN rows in order; the totals stay the physical sums.
+__device__ __forceinline__ void range_add64(unsigned long long* row, uint32_t lo, uint32_t hi, uint32_t tsa,
+                                            unsigned long long v) {
+    if (lo < hi) {
+        atomicAdd(&row[lo], v);
+        if (hi < tsa) atomicAdd(&row[hi], 0ull - v);
+    }
+}
+
+__global__ __launch_bounds__(kStateThreads) void dt_state_kernel(DtStateArgs a) {
+    extern __shared__ unsigned long long used64[];  // [2 * max_nn]: cores then memory per row
+    const uint32_t c = blockIdx.x;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n0 = a.s.node_off[c], N = a.s.node_off[c + 1] - n0;
+    const uint32_t nvc = a.nv[c] < a.V ? a.nv[c] : a.V, NN = N + nvc;
+    for (uint32_t i = tid; i < 2u * NN; i += kStateThreads) used64[i] = 0ull;
+    __syncthreads();
+
+    const uint64_t j0 = a.s.job_off[c];
+    const uint32_t J = (uint32_t)(a.s.job_off[c + 1] - j0);
+    const int32_t* __restrict__ node = a.s.out_node + j0;
+    const uint32_t* __restrict__ start = a.s.out_start + j0;
+    const uint32_t* __restrict__ finish = a.s.out_finish + j0;
+    const uint4* __restrict__ jobs = a.s.jobs + j0;
+    const uint32_t t = a.s.t;
+    uint32_t nrun = 0;
+#pragma unroll 4
+    for (uint32_t i = tid; i < J; i += kStateThreads) {
+        const int32_t k = __builtin_nontemporal_load(node + i);
+        const uint32_t s = __builtin_nontemporal_load(start + i);
+        const uint32_t f = __builtin_nontemporal_load(finish + i);
+        if (k >= 0 && s <= t && t < f) {
+            if ((uint32_t)k < NN) {
+                const uint2 cm = *reinterpret_cast<const uint2*>(&jobs[i].z);
+                atomicAdd(&used64[k], (unsigned long long)cm.x);
+                atomicAdd(&used64[NN + k], (unsigned long long)cm.y);
+            }
+            ++nrun;
+        }
+    }
+    for (uint32_t i = tid; i < a.n_foreign; i += kStateThreads) {
+        const mcs_foreign_rec r = a.flog[i];
+        if (r.responder == c && r.start_s < t && t < r.finish_s) {
+            if (r.node < NN) {
+                atomicAdd(&used64[r.node], (unsigned long long)r.c);
+                atomicAdd(&used64[NN + r.node], (unsigned long long)r.m);
+            }
+            ++nrun;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) nrun += (uint32_t)__shfl_xor((int)nrun, o);
+    __shared__ uint32_t run_total;
+    if (tid == 0) run_total = 0u;
+    __syncthreads();
+    if ((tid & 63u) == 0u) atomicAdd(&run_total, nrun);
+    __syncthreads();
+
+    if (tid == 0) {
+        float cu = 0.0f, mu = 0.0f;
+        uint32_t tc = 0, tm = 0;
+        for (uint32_t i = 0; i < NN; ++i) {
+            const uint2 cap = i < N ? a.s.cap[n0 + i] : a.vcap[(size_t)c * a.V + (i - N)];
+            const uint2 fr0 = i < N ? a.s.free0[n0 + i] : cap;
+            const unsigned long long fc = (unsigned long long)fr0.x - used64[i];
+            const unsigned long long fm = (unsigned long long)fr0.y - used64[NN + i];
+            cu = __fadd_rn(cu, __fsub_rn((float)cap.x, (float)fc));
+            mu = __fadd_rn(mu, __fsub_rn((float)cap.y, (float)fm));
+            if (i < N) {  // SetTotalResources ran before any trade (cluster.go:79)
+                tc += cap.x;
+                tm += cap.y;
+            }
+        }
+        mcs_cluster_state st;
+        st.cores_utilization = __fdiv_rn(cu, (float)tc);
+        st.memory_utilization = __fdiv_rn(mu, (float)tm);
+        st.total_cpu = tc;
+        st.total_memory = tm;
+        st.running = run_total;
+        st.t_s = t;
+        a.s.out[c] = st;
+    }
+}
+
+// series_kernel's tile walk with 64-bit node rows: LDS holds 2 NN rows of TS u64 (cores, memory),
+// then 2 kSeriesRep counter rows and two result rows of TS u32, TS = dt_series_tile(NN).
+__global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a) {
+    extern __shared__ unsigned long long d64[];  // [2 NN][TS] u64, then [2 kSeriesRep + 2][TS] u32
+    __shared__ uint64_t masks[3][4];
+    __shared__ uint32_t hits[kStateThreads];
+    __shared__ uint32_t tot[2];
+    const StateArgs& s_ = a.d.s;
+    const uint32_t c = blockIdx.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t n0 = s_.node_off[c], N = s_.node_off[c + 1] - n0;
+    const uint32_t nvc = a.d.nv[c] < a.d.V ? a.d.nv[c] : a.d.V, NN = N + nvc;
+    const uint64_t j0 = s_.job_off[c];
+    const uint64_t J = s_.job_off[c + 1] - j0;
+    const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
+    const int32_t* __restrict__ node = s_.out_node + j0;
+    const uint32_t* __restrict__ start = s_.out_start + j0;
+    const uint32_t* __restrict__ finish = s_.out_finish + j0;
+    const uint4* __restrict__ jobs = s_.jobs + j0;
+    const uint2* __restrict__ summ = a.summ + (j0 / kSeriesBatch + c);
+    const uint2* __restrict__ vcap = a.d.vcap + (size_t)c * a.d.V;
+    const uint32_t TS = dt_series_tile(NN);
+    const uint32_t n = a.n_samples, period = a.period;
+    uint32_t* const d32 = reinterpret_cast<uint32_t*>(d64 + (size_t)2u * NN * TS);
+    uint32_t* const run_rows = d32;
+    uint32_t* const que_rows = run_rows + kSeriesRep * TS;
+    uint32_t* const res_row = que_rows + kSeriesRep * TS;
+    uint32_t* const my_run = run_rows + (lane % kSeriesRep) * TS;
+    uint32_t* const my_que = que_rows + (lane % kSeriesRep) * TS;
+
+    if (tid < 2) tot[tid] = 0u;
+    __syncthreads();
+    uint32_t tc = 0, tm = 0;
+    for (uint32_t i = tid; i < N; i += kStateThreads) {
+        const uint2 cap = s_.cap[n0 + i];
+        tc += cap.x;
+        tm += cap.y;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        tc += (uint32_t)__shfl_xor((int)tc, o);
+        tm += (uint32_t)__shfl_xor((int)tm, o);
+    }
+    if (lane == 0) {
+        atomicAdd(&tot[0], tc);
+        atomicAdd(&tot[1], tm);
+    }
+    __syncthreads();
+    const float ftc = (float)tot[0], ftm = (float)tot[1];
+
+    uint64_t b_lo = 0;
+    for (uint32_t k0 = 0; k0 < n; k0 += TS) {
+        const uint32_t tsa = n - k0 < TS ? n - k0 : TS;
+        const uint32_t t_first = a.t0 + k0 * period, t_last = t_first + (tsa - 1u) * period;
+        {  // zero every row: 2 NN TS u64 words and (2 kSeriesRep + 2) TS u32 words
+            const uint32_t w64 = 2u * NN * TS, w32 = (2u * kSeriesRep + 2u) * TS;
+            for (uint32_t i = tid; i < w64; i += kStateThreads) d64[i] = 0ull;
+            for (uint32_t i = tid; i < w32; i += kStateThreads) d32[i] = 0u;
+        }
+        __syncthreads();
+
+        auto kt = [&](uint32_t x) -> uint32_t {
+            if (x <= t_first) return 0u;
+            const uint32_t y = x - t_first - 1u;
+            const uint32_t q = period == 1u ? y : (uint32_t)__umul64hi(a.magic, (uint64_t)y);
+            return q >= tsa ? tsa : q + 1u;
+        };
+        auto apply = [&](int32_t k, uint32_t s, uint32_t f, uint4 jr) {
+            const bool placed = k >= 0;  // on a physical or a virtual node; -1: undecided, queued for good
+            if (jr.x > t_last || (placed && f <= t_first)) return;
+            const uint32_t ka = kt(jr.x), ks = placed ? kt(s) : tsa;
+            range_add(my_que, ka, ks, tsa, 1u);
+            if (placed) {
+                const uint32_t kf = kt(f);
+                range_add(my_run, ks, kf, tsa, 1u);
+                if ((uint32_t)k < NN) {
+                    if (jr.z) range_add64(d64 + (size_t)(uint32_t)k * TS, ks, kf, tsa, jr.z);
+                    if (jr.w) range_add64(d64 + (size_t)(NN + (uint32_t)k) * TS, ks, kf, tsa, jr.w);
+                }
+            }
+        };
+
+        bool leading = true;
+        for (uint64_t base = b_lo; base < nb; base += kStateThreads) {
+            const uint64_t b = base + tid;
+            bool hit = false, dead = false, past = false;
+            if (b < nb) {
+                const uint2 s = summ[b];
+                past = s.x > t_last;
+                dead = s.y <= t_first;
+                hit = !past && !dead;
+            }
+            const uint64_t hm = __ballot(hit), dm = __ballot(dead), pm = __ballot(past);
+            if (lane == 0) {
+                masks[0][wave] = hm;
+                masks[1][wave] = dm;
+                masks[2][wave] = pm;
+            }
+            __syncthreads();
+            uint32_t lead = 0, n_hit = 0, before = 0;
+            bool counting = leading, any_past = false;
+            for (uint32_t w = 0; w < 4; ++w) {
+                any_past |= masks[2][w] != 0;
+                if (w == wave) before = n_hit;
+                n_hit += (uint32_t)__popcll(masks[0][w]);
+                if (counting) {
+                    const uint64_t live = ~masks[1][w];
+                    if (live == 0) {
+                        lead += 64u;
+                    } else {
+                        lead += (uint32_t)__builtin_ctzll(live);
+                        counting = false;
+                    }
+                }
+            }
+            if (hit) hits[before + (uint32_t)__popcll(hm & ((1ull << lane) - 1ull))] = tid;
+            __syncthreads();
+            n_hit = sgpr(n_hit);
+            for (uint32_t h = 0; h < n_hit; ++h) {
+                const uint64_t i = (base + hits[h]) * kSeriesBatch + tid;
+                if (i < J) apply(node[i], start[i], finish[i], jobs[i]);
+            }
+            if (leading) {
+                b_lo += lead;
+                leading = lead == kStateThreads;
+            }
+            __syncthreads();  // masks and hits are rewritten by the next round
+            if (any_past) break;
+        }
+        // the Foreign jobs of this responder: they hold on start_s < t < finish_s
+        for (uint32_t i = tid; i < a.d.n_foreign; i += kStateThreads) {
+            const mcs_foreign_rec* __restrict__ r = a.d.flog + i;
+            if (r->responder != c) continue;
+            const uint32_t fs = r->start_s, ff = r->finish_s;
+            if (fs >= t_last || ff <= t_first) continue;  // (fs < t_last <= 0xFFFFFFFE: fs + 1 fits)
+            const uint32_t ks = kt(fs + 1u), kf = kt(ff);
+            range_add(my_run, ks, kf, tsa, 1u);
+            const uint32_t k = r->node;
+            if (k < NN) {
+                const unsigned long long fc = r->c, fm = r->m;
+                if (fc) range_add64(d64 + (size_t)k * TS, ks, kf, tsa, fc);
+                if (fm) range_add64(d64 + (size_t)(NN + k) * TS, ks, kf, tsa, fm);
+            }
+        }
+        __syncthreads();
+
+        // prefix sums along the samples, one thread per row; node rows leave their float32 term
+        for (uint32_t r = tid; r < 2u * NN + 2u * kSeriesRep; r += kStateThreads) {
+            if (r < 2u * NN) {
+                unsigned long long* row = d64 + (size_t)r * TS;
+                const bool mem = r >= NN;
+                const uint32_t i = mem ? r - NN : r;
+                const uint2 cap = i < N ? s_.cap[n0 + i] : vcap[i - N];
+                const uint2 fr0 = i < N ? s_.free0[n0 + i] : cap;
+                const float fcap = (float)(mem ? cap.y : cap.x);
+                const unsigned long long fr = mem ? fr0.y : fr0.x;
+                unsigned long long acc = 0ull;
+#pragma unroll 8
+                for (uint32_t k = 0; k < tsa; ++k) {
+                    acc += row[k];
+                    row[k] = (unsigned long long)__float_as_uint(__fsub_rn(fcap, (float)(fr - acc)));
+                }
+            } else {
+                uint32_t* row = d32 + (r - 2u * NN) * TS;
+                uint32_t acc = 0;
+#pragma unroll 8
+                for (uint32_t k = 0; k < tsa; ++k) {
+                    acc += row[k];
+                    row[k] = acc;
+                }
+            }
+        }
+        __syncthreads();
+
+        // GetResourceUtilization: serial in row order, one lane per (sample, resource)
+        for (uint32_t x = tid; x < 2u * tsa; x += kStateThreads) {
+            const uint32_t mem = x >= tsa ? 1u : 0u, k = x - mem * tsa;
+            const unsigned long long* col = d64 + (size_t)mem * NN * TS + k;
+            float f = 0.0f;
+#pragma unroll 16
+            for (uint32_t i = 0; i < NN; ++i) f = __fadd_rn(f, __uint_as_float((uint32_t)col[(size_t)i * TS]));
+            res_row[mem * TS + k] = __float_as_uint(__fdiv_rn(f, mem ? ftm : ftc));
+        }
+        __syncthreads();
+
+        if (tid < tsa) {
+            uint32_t nrun = 0, nque = 0;
+#pragma unroll
+            for (uint32_t r = 0; r < kSeriesRep; ++r) {
+                nrun += run_rows[r * TS + tid];
+                nque += que_rows[r * TS + tid];
+            }
+            const uint4 v = make_uint4(res_row[tid], res_row[TS + tid], nrun, nque);
+            reinterpret_cast<uint4*>(a.out)[(size_t)c * n + k0 + tid] = v;
+        }
+        __syncthreads();  // the rows are zeroed for the next tile
+    }
+}
+
 // ---- the pre-pass over a FIFO trading run's lent log ---------------------------------------------
 //
 // The log is in execution order (starts ascend), every lender's records interleaved.  A counting
@@ -674,6 +974,38 @@ hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t 
         hipLaunchKernelGGL(series_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
     else
         hipLaunchKernelGGL(series_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_dt_state(const DtStateArgs& a, uint32_t max_nn, hipStream_t s) {
+    if (a.s.n_clusters == 0) return hipSuccess;
+    if (max_nn == 0 || max_nn > 1280u) return hipErrorInvalidValue;  // 1024 physical + 256 virtual rows: 20 KB
+    hipLaunchKernelGGL(dt_state_kernel, dim3(a.s.n_clusters), dim3(kStateThreads),
+                       2 * max_nn * sizeof(unsigned long long), s, a);
+    return hipGetLastError();
+}
+
+// the TRADE summaries: end = finish of every placed job, physical or virtual node (a DELAY run has no
+// borrowed job); an undecided job keeps its batch alive for good
+hipError_t launch_dt_series_summary(const DtSeriesArgs& a, hipStream_t s) {
+    if (a.d.s.n_clusters == 0) return hipSuccess;
+    SeriesArgs p{};
+    p.s = a.d.s;
+    p.summ = a.summ;
+    hipLaunchKernelGGL(series_summary_kernel<true>, dim3(a.d.s.n_clusters), dim3(kStateThreads), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStream_t s) {
+    if (a.d.s.n_clusters == 0) return hipSuccess;
+    // dt_series_tile(NN) samples of dt_series_bytes(NN) bytes, NN <= max_nn, within kSeriesLds
+    if (max_nn == 0 || max_nn > 1280u) return hipErrorInvalidValue;  // a tile of at least 3 samples
+    uint32_t lds = dt_series_bytes(max_nn) * kSeriesMaxTile;
+    if (lds > kSeriesLds) lds = kSeriesLds;
+    hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void*>(dt_series_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
+    if (st != hipSuccess) return st;
+    hipLaunchKernelGGL(dt_series_kernel, dim3(a.d.s.n_clusters), dim3(kStateThreads), lds, s, a);
     return hipGetLastError();
 }
 

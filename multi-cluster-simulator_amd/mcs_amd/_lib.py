@@ -263,6 +263,9 @@ SIGNATURES = [
     ("mcs_wait_time_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_wait_sample),
                                        C.c_uint32, C.POINTER(C.c_double)]),
     # include/mcs_trade.h
+    ("mcs_dtrade_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
+                                          C.POINTER(mcs_wait_sample), C.POINTER(mcs_cluster_state), C.c_uint32,
+                                          C.POINTER(C.c_double)]),
     ("mcs_set_shard", C.c_int, [vp, C.c_uint32, C.c_uint32]),
     ("mcs_comm_unique_id", C.c_int, [C.POINTER(mcs_comm_id)]),
     ("mcs_comm_init", C.c_int, [vp, C.POINTER(mcs_comm_id)]),

@@ -478,6 +478,32 @@ class Engine:
                                              C.byref(ms)))
         return (samples, ms.value) if with_time else samples
 
+    def dtrade_state_series(self, t0_s: int, period_s: int, n_samples: int, with_wait: bool = True,
+                            with_time: bool = False):
+        """The ClusterState time series and the wait statistics of the last DELAY trading run
+        (mcs_dtrade_state_series; policy DELAY with trader, run() or trade_begin .. trade_end on one
+        engine): samples t0_s + k * period_s, k < n_samples, taken after the tick's Delay iteration
+        and before its trader rounds.  The rows are the physical nodes and then the virtual nodes
+        the cluster received; own jobs hold on start <= t < finish, Foreign jobs on
+        start < t < finish; the counters are uint64 and wrap, so utilization can be negative.
+        Returns (samples, wait, first): (num_clusters, n_samples) of CLUSTER_SAMPLE_DTYPE, the same
+        shape of WAIT_SAMPLE_DTYPE (None without with_wait) and the full records at t0_s
+        (CLUSTER_STATE_DTYPE); with_time adds the kernel ms.  MCSError (MCS_E_STATE) after any other
+        run, on a sharded engine and after a run whose logs or capacities overflowed."""
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), CLUSTER_SAMPLE_DTYPE)
+        wait = np.zeros((n, max(int(n_samples), 0)), WAIT_SAMPLE_DTYPE) if with_wait else None
+        first = np.zeros(n, CLUSTER_STATE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(L.lib().mcs_dtrade_state_series(
+            self._h, int(t0_s), int(period_s), int(n_samples), samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None,
+            first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
+        return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
+
     def approve_trade(self, total_cores, total_memory, core_util, mem_util, cores, memory, time_s) -> np.ndarray:
         """mcs_approve_trade: Trader.ApproveTrade (trader.go:141-167) on the GPU for arrays of
         (responder totals + sample, contract) queries; returns 0/1 per query."""
