@@ -18,11 +18,12 @@
 //                                                          wave_shl:1 of v94, v95, v96)        written earlier still
 //  SDWA / op_sel write preserving the other word     1     MCS_FA_FIT16: v80/v81 (WORD_1,      v_cmp_lt s[60:61] + v_ffbl v117
 //    -> VALU reads that VGPR (DstSelForwarding)            UNUSED_PRESERVE) -> v_perm          between (found by measurement,
-//                                                                                              tools/asm_debug.py); MCS_FA_FIT16C:
-//                                                                                              s_add s55 (one wait state, after
-//                                                                                              the v81 write the v_perm reads);
-//                                                                                              W16C's release tail (the same
-//                                                                                              pair): s_cmp_le_u32 between
+//                                                                                              tools/asm_debug.py)
+//                                                          MCS_FA_FITBITS16C: v86 (WORD_0,     the second v_perm (v81) between the
+//                                                          then WORD_1 UNUSED_PRESERVE, which  two writes; the caller's scalar
+//                                                          reads the first write) -> v_cmp     instruction (the pass: s_add s55,
+//                                                                                              the release tail: s_cmp_le_u32)
+//                                                                                              between the second and the v_cmp
 //  VALU writes SGPR -> v_readlane / v_writelane      4     none: every lane select is SALU-    (s50/s85/s82 from s_ff1, s47/m0
 //    uses it as the lane select                            written                             from s_add/s_mov)
 //  SALU writes M0 -> v_writelane with an M0 lane     1*    result writes at a Level0 decision  >= 1 other instruction between
@@ -41,7 +42,7 @@
 //                                                          W16C's v89 / v90 / v107 (written    s_mov s47 + three v_readlane after
 //                                                          per batch only, MCS_FC_SHIFT)       the batch's
 //                                                          W16C's sections: v72-v75, v80, v81,  the pass's own distances (the same
-//                                                          v86 of MCS_FA_FIT16C in the tail     macros: FIT16C, DECIDE16C)
+//                                                          v86 of MCS_FA_FITBITS16C in the tail macros: FITBITS16C, DECIDE16C)
 //                                                          DELAY G pass (r04): v_cndmask v113  >= 6 (GTEST's scalar prologue)
 //                                                          -> GTEST's v_readlane v113; v123
 //                                                          (indexed move) -> v_readlane s74     >= 3 (s_set_gpr_idx_off, s_add,
@@ -51,15 +52,20 @@
 //                                                          then s_cbranch_vccz / vccnz: copies, right after the v_cmp)
 //                                                          scan, sleep chain, bulk move)
 //  VALU writes EXEC -> DPP (5) / v_readlane (4)      5/4   none: exec is written by SALU only   (no v_cmpx in any loop; W16C's row
-//                                                                                              blocks: s_mov_b64 exec)
+//                                                                                              blocks: s_mov_b64 exec; its
+//                                                                                              commit leaves exec alone)
+//  SALU writes an SGPR pair -> VALU reads it as a    0     DECIDE16C: s_lshl_b64 s[60:61] ->    (interlocked; four scalar
+//    lane mask (v_cndmask)                                 the indexed v_cndmask               instructions lie between anyway)
 //  VMEM store of > 64 bits -> its data VGPRs         1     none: every store is one dword       -
 //    rewritten
 //  VALU writes SGPR -> VMEM reads it (address/      5     none: the store/load bases s[64:71]   -
 //    soffset)                                              are SALU-written
 //  s_set_gpr_idx_on -> indexed VALU, _off -> plain   0     DECIDE16R / DECIDE16C / COMMIT16 /   (the indexed moves sit between
 //                                                          INSERT16R (none is open in a        on and off; no non-indexed VALU
-//                                                          release scan or its tail); W16C's   read inside a region)
-//                                                          surplus insert (MCS_FC_BMOVE_OOL)
+//                                                          release scan or its tail); W16C's   read inside a region; DECIDE16C's
+//                                                          surplus insert (MCS_FC_BMOVE_OOL)   v_cndmask is VOP3: the index goes
+//                                                                                              to its VGPR operands, SRC0, SRC1
+//                                                                                              and DST, its mask is an SGPR pair)
 //  SALU writes M0 -> s_movrels / s_movreld         1     W16C's surplus insert at a batch end   s_nop 0 between; s_movreld follows
 //    reads it                                              (FREE[r], m0 = 2r)                  with m0 untouched
 //  s_set_gpr_idx_on overwrites M0                  -     DECIDE16C; W16C's surplus insert     m0 = the cursor is set after the
@@ -552,8 +558,8 @@
 //   s77 XMIN   s74, s59 the address of the copies' table of branches (MCS_FC_RET; on a 512-byte line),
 //   low and high word   s[58:59] a computed jump's target   s49 a computed jump's t & 7 / the full scan's
 //   released count / a batch-lane release's row count   s79 the limit of a waiting head's sleep,
-//   min(XMIN, t + 9)   s[50:55], s[60:63], s75, s85: the decision's pick (s50-s54) and the bulk move's
-//   temporaries   s43 1 while a head waits in
+//   min(XMIN, t + 9)   s[50:55], s[60:63], s75, s85: the decision's pick (s50-s54), its lane mask (s[60:61])
+//   and the bulk move's temporaries   s43 1 while a head waits in
 //   a copy's section, 2 while a zero-duration job waits out of line, else 0   s41 min(64, J - cb), read where a
 //   batch is taken only   v89, v90, v107 the record columns shifted by one lane (MCS_FC_SHIFT)   m0 after a
 //   placement: the lane of the job placed, the record read's lane select
@@ -580,19 +586,25 @@
 // (interlocked); the DPP chains keep s_nop 1; the surplus insert of the bulk move keeps the per-job
 // insert's distances (s_nop 0 between m0 and s_movrels, both relative moves before its region).
 //
-// The fit test is MCS_FA_FIT16 without the insert's free-row lanes: the pass's finish (s_add s55) is
-// the instruction between the last SDWA-preserve write and the v_perm (hazard table, row 2).
-#define MCS_FA_FIT16C                                                                             \
+// The fit test ("Fit and commit"): the four differences as in MCS_FA_FIT16; then one v_perm per
+// pair of chunks sign-replicates byte 1 and byte 3 of both differences, the guard bits (s72 = 0x0b090a08:
+// {c0, c1 | m0, m1}, the cores guards in the low half, the memory guards in the high half, every byte 0x00 or
+// 0xff), and one SDWA AND of high half & low half per pair writes half of v86: byte c is 0xff exactly when
+// chunk c fits, as MCS_FA_FIT16's v_perm leaves it, in nine vector instructions for ten.  Hazard table, row 2:
+// the second v_perm lies between the two SDWA writes of v86 (the second preserves, so reads, the half the
+// first wrote), and GAP, a scalar instruction of the caller's (the pass's finish, s_add s55; the release
+// tail's arrival test, s_cmp_le), between the preserving write and the v_cmp that reads v86.
+#define MCS_FA_FITBITS16C(GAP)                                                                    \
     "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
     "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
     "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
     "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
-    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "s_add_u32 s55, s40, s46\n\t" /* finish; the wait state the v_perm's read of v81 needs */    \
-    "v_perm_b32 v86, v81, v80, s72\n\t"
+    "v_perm_b32 v80, v73, v72, s72\n\t" /* {c0, c1 | m0, m1} */                                   \
+    "v_and_b32_sdwa v86, v80, v80 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    "v_perm_b32 v81, v75, v74, s72\n\t" /* {c2, c3 | m2, m3} */                                   \
+    "v_and_b32_sdwa v86, v81, v81 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
+    GAP
+#define MCS_FA_FIT16C MCS_FA_FITBITS16C("s_add_u32 s55, s40, s46\n\t") /* finish */
 // (the record broadcasts stay: one s_load_dwordx4 per job into an SGPR quad, a pass ahead, measured
 // faster at 512 clusters and slower at 4096, where the scalar port pays 7 instructions for the three
 // v_readlane: DESIGN.md §4 "pass trim", profiles/pass_trim/steps_flagged.patch)
@@ -673,10 +685,11 @@
 // number 4J + 257 trips it, as the shared loop's s78 > s79); s79 has another use in this form.
 #define MCS_FA_GUARD016C "s_lshl2_add_u32 s78, s42, 0x100\n\t"
 // The entry needs no padding: it reaches the copy of its clock through the table of branches, and each
-// copy places its own head 16 bytes into a 64-byte instruction line (MCS_FC_COPY), the position that
+// copy places its own head 24 bytes into a 64-byte instruction line (MCS_FC_COPY; 16 bytes before the fit
+// test lost 8), the position that
 // measured best of the eight 4-byte positions for the single loop at 4096 and at 512 clusters (where the
-// loop lies decided up to 1.8 % and 3.4 % of its time, profiles/pass_trim/ab_place_*.txt and
-// profiles/calendar_rows/ab_place_*.txt).
+// loop lies decided up to 1.8 % and 3.4 % of its time, profiles/pass_trim/ab_place_*.txt,
+// profiles/calendar_rows/ab_place_*.txt and profiles/fit_commit/ab_place_*.txt).
 #define MCS_FA_HEAD16C ""
 #define MCS_FA_INIT16C MCS_FA_ZMASK16C("v94") /* (batch 0) */                                     \
     "s_min_u32 s41, s42, 64\n\t" MCS_FC_SHIFT                                                     \
@@ -701,18 +714,21 @@
     "v_mov_b32 v56, -1\n\t"                                                                      \
     "v_mov_b32 v60, -1\n\t"                                                                      \
     "v_mov_b32 v106, -1\n\t" /* LIVE: no job of the batch is running */
-// The decision is the pick and the commit alone (MCS_FA_DECIDE16R's chunk move in its register-index
-// region): a placed job takes no slot.  It stays in its batch lane, its finish in the LIVE column v106
+// The decision is the pick and the commit alone: a placed job takes no slot.  The commit is
+// MCS_FA_DECIDE16R's chunk move in its register-index region, as a v_cndmask under the fitting lane's mask
+// in s[60:61] (a temporary of the bulk move and the releases, free in a pass): the lane's chunk takes the
+// difference, every other lane keeps its own, and exec stays the full wave from the fit test to the record
+// read ("Fit and commit"; the zero route commits nothing, MCS_FA_ZEROKX16C).  It stays in its batch lane, its finish in the LIVE column v106
 // (written beside the two result writes; -1 in every other lane), until it finishes there or the batch
 // ends and the live lanes go into their calendar rows together (MCS_FC_BMOVE).
 #define MCS_FA_DECIDE16C                                                                          \
     "v_readlane_b32 s51, v86, s50\n\t"                                                            \
-    "s_lshl_b64 exec, 1, s50\n\t"                                                                 \
+    "s_lshl_b64 s[60:61], 1, s50\n\t" /* the fitting lane's mask (s[60:61]: free in a pass) */  \
     "s_ff1_i32_b32 s52, s51\n\t"                                                                  \
     "s_lshr_b32 s53, s52, 3\n\t"                                                                  \
     "s_lshl2_add_u32 s54, s50, s53\n\t" /* kx = the node index, lane * 4 + chunk */             \
-    "s_set_gpr_idx_on s53, gpr_idx(SRC0,DST)\n\t"                                                 \
-    "v_mov_b32 v64, v72\n\t" /* the commit (cluster.go:146-147) */                                \
+    "s_set_gpr_idx_on s53, gpr_idx(SRC0,SRC1,DST)\n\t"                                            \
+    "v_cndmask_b32_e64 v64, v64, v72, s[60:61]\n\t" /* the commit (cluster.go:146-147) */         \
     "s_set_gpr_idx_off\n\t"
 // a batch-lane release (out of line; vcc = the lanes of LIVE that finish by t, not empty): the LDS node
 // copy is refreshed, the requests (v96) go back to the nodes (base + 4 * v91) and the lanes leave LIVE;
@@ -989,7 +1005,9 @@
 // table of branches, eight per entry point (MCS_FC_RET: s74 + 32 * entry + 4 * (t & 7), the table on a
 // 512-byte line and 320 bytes long, so the sum never carries).  The padding in front of a copy's
 // mcsfa_norel lies behind an unconditional branch and is never run; it puts the pass's head (mcsfa_fit)
-// 16 bytes into a 64-byte line, the position MCS_FA_HEAD16C kept for the single loop.
+// 24 bytes into a 64-byte line: 16, the position MCS_FA_HEAD16C kept for the single loop, while the fit test
+// was 8 bytes longer, so what lies behind the test is where it was; again the best of the eight 4-byte
+// positions at 4096 and at 512 clusters (profiles/fit_commit/ab_place_*.txt).
 //
 // A waiting WaitQueue head has a section of its own in each copy ("The waiting head"),
 // entered at the failed fit (mcsfa_nofit<k>) and left when the head is placed; nothing else runs while
@@ -1075,20 +1093,13 @@
     "s_sub_u32 s80, s80, s76\n\t" MCS_FA_RELOAD16C                                               \
     "s_add_u32 s55, s40, s46\n\t" /* finish */                                                   \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                    \
-    "v_pk_sub_u16 v72, v64, s48\n\t"                                                              \
-    "v_pk_sub_u16 v73, v65, s48\n\t"                                                              \
-    "v_pk_sub_u16 v74, v66, s48\n\t"                                                              \
-    "v_pk_sub_u16 v75, v67, s48\n\t"                                                              \
-    "v_and_b32_sdwa v80, v72, v72 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v74, v74 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v80, v73, v73 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "v_and_b32_sdwa v81, v75, v75 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0\n\t" \
-    "s_cmp_le_u32 s45, s40\n\t" /* (the wait state the v_perm's read of v81 needs) */            \
-    "v_perm_b32 v86, v81, v80, s72\n\t" MCS_FA_ANYFIT                                            \
+    MCS_FA_FITBITS16C("s_cmp_le_u32 s45, s40\n\t") MCS_FA_ANYFIT                                 \
     "s_cbranch_scc1 mcsfa_fitted" #k "_%=\n\t"                                                    \
     "s_branch mcsfa_arrive" #k "_%=\n"                                                            \
     ".p2align 6\n\t"                                                                              \
-    "s_nop 0\n\t" /* (never run: mcsfa_fit 16 bytes into the line) */                            \
+    "s_nop 0\n\t" /* (never run: mcsfa_fit 24 bytes into the line) */                            \
+    "s_nop 0\n\t"                                                                                 \
+    "s_nop 0\n\t"                                                                                 \
     "s_nop 0\n"                                                                                   \
     /* nothing released: the advance ends (a sleeping head never comes here) */                  \
     "mcsfa_norel" #k "_%=:\n"                                                                     \
@@ -1100,7 +1111,6 @@
     "s_cbranch_vccz mcsfa_nofit" #k "_%=\n\t"                                                     \
     "s_ff1_i32_b64 s50, vcc\n\t" /* lowest lane with a fit */                                     \
     MCS_FA_DECIDE16C                                                                              \
-    "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \
@@ -1166,7 +1176,6 @@
     /* second (:250) into the next copy's ordinary row block */                                  \
     "s_ff1_i32_b64 s50, vcc\n\t"                                                                  \
     MCS_FA_DECIDE16C                                                                              \
-    "s_mov_b64 exec, -1\n\t"                                                                      \
     "s_mov_b32 m0, s47\n\t"                                                                       \
     "s_add_u32 s80, s80, 1\n\t"                                                                   \
     "v_writelane_b32 v91, s54, m0\n\t"                                                            \

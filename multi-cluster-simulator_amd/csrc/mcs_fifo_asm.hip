@@ -474,8 +474,9 @@ __global__ __launch_bounds__(64) void fifo_asm_kernel(FifoArgs a) {
     const uint32_t v_pay = CAL ? 0u : base + 2048u + lane * 8u;  // (W16C: no LDS slot rows)
     const uint32_t v_nb = base + lane * (CAL ? 16u : W / 4u);
     const uint32_t v_nbase = base;
-    // perm selectors: W32 gathers chunk pairs 0/1 and 2/3, W16 all four chunks at once
-    const uint32_t sel0 = W == 32 ? 0x0c0c0b09u : NPL == 1 ? 0x7fffu : 0x0b0a0908u;
+    // perm selectors: W32 gathers chunk pairs 0/1 and 2/3, W16 all four chunks at once; the streamed W16R
+    // loop sign-replicates the guard bits of a chunk pair before it ANDs them (MCS_FA_FITBITS16C)
+    const uint32_t sel0 = W == 32 ? 0x0c0c0b09u : NPL == 1 ? 0x7fffu : CAL ? 0x0b090a08u : 0x0b0a0908u;
     const uint32_t sel1 = W == 32 ? 0x0b090c0cu : base;  // (W16R: the node array's LDS base)
 
     uint32_t t = 0, r = 0, flags = 0, have_w = 0;

@@ -19,7 +19,8 @@ Two insert policies are replayed side by side ("Running jobs stay
             calendar row) until it finishes there or its batch of 64 ends; then the live lanes go to their rows
             together, each row's candidates to its free lanes, and a row's surplus spills as a per-job insert did.
 DEFER holds the instructions the deferred policy adds and removes, counted from the listing; LANE those of the
-three steps of "Lane results"  on top of it, per step, from the deferred replay's events.
+three steps of "Lane results"  on top of it, FITC those of "Fit and commit" on top of those, per step, from
+the deferred replay's events.
 Printed per job: release scans and what they compared, spills, failed fits and the seconds their sleeps
 cross, the compares that release nothing, the running slots; and the instructions a scan issues, counted
 from the listing of the loop as built (COST below; the pair scan of the loop before it from
@@ -133,6 +134,33 @@ LANE = {
     "C": {
         "bulk move": ("bulk moves", (0, 0, -40, 0)),
         "surplus insert": ("spills", (1, 0, 0, 0)),
+    },
+}
+
+
+# "Fit and commit" (DESIGN.md §4), per step and event: (scalar, branch, vector, LDS), from the listings
+FITC = {
+    # F: the fit test in nine vector instructions (two v_perm that sign-replicate the guard bits, two SDWA ANDs)
+    # for ten (four SDWA ANDs, one v_perm).  A job's own fit test runs once where it is placed (the pass, a
+    # release's tail, the zero route), once more per failed fit, and a release behind a placed head runs one
+    # for nothing when no job is ready
+    "F": {
+        "placement": ("inserts", (0, 0, -1, 0)),
+        "zero-duration job": ("zero-duration jobs", (0, 0, -1, 0)),
+        "failed fit": ("failed fits", (0, 0, -1, 0)),
+        "tail's fit test dropped": ("placed-head releases, no ready job behind", (0, 0, -1, 0)),
+    },
+    # C: the commit is a v_cndmask under a scalar lane mask: s_lshl_b64 exec + v_mov + s_mov_b64 exec ->
+    # s_lshl_b64 s[60:61] + v_cndmask (the pass's decision and the waiting head's placement)
+    "C": {
+        "placement": ("inserts", (-1, 0, 0, 0)),
+    },
+    # U (counted, not built): the running count from the cursor.  The placement loses s_add s80; a release scan
+    # gains one instruction, a batch end one
+    "U": {
+        "placement": ("inserts", (-1, 0, 0, 0)),
+        "release scan": ("release scans", (1, 0, 0, 0)),
+        "batch end": ("batch ends", (1, 0, 0, 0)),
     },
 }
 
@@ -267,7 +295,8 @@ def replay(arr, dur, start, finish, st, deferred=False):
         if w:  # a placed WaitQueue head sleeps one second
             st["waited"] += 1
             t += 1
-            adv1("placed head")
+            if adv1("placed head") and not (k + 1 < len(arr) and arr[k + 1] <= t):
+                st["placed-head releases, no ready job behind"] += 1  # (the tail's fit test is dropped)
     st["exits"] += 1
 
 
@@ -331,6 +360,16 @@ def main():
     steps["kept (A + C): change per job"] = {f: round(steps["A"]["change per job"][f] + steps["C"]["change per job"][f], 2)
                                              for f in ("scalar", "branch", "vector", "lds")}
     out["lane_results"] = steps
+    steps = {}
+    for step, events in FITC.items():
+        rows = {name: {"per_job": round(sd[n] / jobs, 4), "scalar, branch, vector, lds": list(cost)}
+                for name, (n, cost) in events.items()}
+        rows["change per job"] = {f: round(sum(sd[n] * cost[i] for n, cost in events.values()) / jobs, 2)
+                                  for i, f in enumerate(("scalar", "branch", "vector", "lds"))}
+        steps[step] = rows
+    steps["kept (F + C): change per job"] = {f: round(steps["F"]["change per job"][f] + steps["C"]["change per job"][f], 2)
+                                             for f in ("scalar", "branch", "vector", "lds")}
+    out["fit_commit"] = steps
     print(json.dumps(out, indent=1))
 
 
