@@ -31,7 +31,13 @@
 // failed fits than 8J + 256: a loop fault, re-run at the same pool and counted in handed_over;
 // MCS_FLAG_OVERFLOW stays the real slot exhaustion, which escalates the pool).  A Level1 deadlock (nothing runs or arrives and Level1 fits no node) ends the
 // cluster here, as delay_kernel does: its Level1 jobs are written unplaced.
-// Same results bit for bit as delay_kernel and the oracle (tests/test_gpu_delay.py, every form).
+// Same results bit for bit as delay_kernel and the oracle (tests/test_gpu_delay.py, every form;
+// tests/test_gpu_delay_edges.py on the loop's constructed edges: Level1's capacity and row boundaries,
+// |G| of 0, 1, 64 and 65, the mode changes, mcsfd_last, the s[100:101] borrow, mcsfd_poolovf), with
+// handed_over equal to the number of clusters whose Level1 needs a 641st entry: a guard that trips on
+// a legitimate stream fails there.  The mcsfd_clkovf paths have no test: the checked horizon bound
+// (mcs_submit_jobs) keeps every clock of the run inside uint32, and an engine with unchecked_horizon
+// runs the online kernels, never this loop.
 #include "mcs_internal.h"
 #include "mcs_lds.h"
 #include "mcs_wave.h"

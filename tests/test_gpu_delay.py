@@ -32,8 +32,12 @@ def run(eng, arrays, streams):
     return node, start, fin, st, eng.cluster_stats(), eng.delay_stats()
 
 
-def assert_delay_parity(arrays, streams, node, start, fin, cs, ds):
-    on, os_, of, od = O.delay_run_batch(arrays, streams, n_threads=8)
+L1_CAP = 640  # kL1Cap: the hand-scheduled loop's Level1 entries in LDS (csrc/mcs_delay_asm.hip)
+
+
+def assert_delay_parity(arrays, streams, node, start, fin, cs, ds, max_wait_s=10):
+    """Bit-exact against the oracle; returns the oracle's per-cluster statistics."""
+    on, os_, of, od = O.delay_run_batch(arrays, streams, n_threads=8, max_wait_s=max_wait_s)
     bad = np.nonzero((node != on) | (start != os_) | (fin != of))[0]
     assert bad.size == 0, f"{bad.size} mismatches, first at {bad[:5]}: gpu {node[bad[:5]]},{start[bad[:5]]} " \
                           f"oracle {on[bad[:5]]},{os_[bad[:5]]}"
@@ -44,6 +48,13 @@ def assert_delay_parity(arrays, streams, node, start, fin, cs, ds):
     np.testing.assert_array_equal(cs["flags"], od["flags"], err_msg="flags")
     for key in ("total_wait_ms", "jobs_count", "moved_l1", "placed_l1", "peak_l1", "l1_left"):
         np.testing.assert_array_equal(ds[key], od[key], err_msg=key)
+    return od
+
+
+def handed_expected(od):
+    """The hand-scheduled loop hands over exactly the clusters whose Level1 needs a 641st entry: any
+    other hand-over is a runaway guard or an early bail-out, which the re-run would hide."""
+    return int((od["peak_l1"] > L1_CAP).sum())
 
 
 @pytest.mark.parametrize("k", DKATS, ids=[k["name"] for k in DKATS])
@@ -80,8 +91,9 @@ def test_gpu_delay_kats_one_launch(delay_engine):
 def test_gpu_delay_seeded_parity(delay_engine, kind, n_clusters, jobs):
     arrays, streams, _ = seeded_workload(kind, n_clusters, jobs)
     node, start, fin, st, cs, ds = run(delay_engine, arrays, streams)
-    assert_delay_parity(arrays, streams, node, start, fin, cs, ds)
+    od = assert_delay_parity(arrays, streams, node, start, fin, cs, ds)
     assert st.placed + st.unplaced == streams.n_jobs
+    assert st.handed_over == (handed_expected(od) if kind.startswith("n256") else 0)
 
 
 def test_gpu_delay_mixed_cluster_sizes(delay_engine):
@@ -139,7 +151,8 @@ def test_gpu_delay_fuzz(delay_engine, shape, seed):
     moves and passes, the D6 skip, WaitTime sums and never-fitting Level1 jobs, bit-exact."""
     arrays, s = fuzz_workload(shape, seed, n_clusters=96, J=1500)
     node, start, fin, st, cs, ds = run(delay_engine, arrays, s)
-    assert_delay_parity(arrays, s, node, start, fin, cs, ds)
+    od = assert_delay_parity(arrays, s, node, start, fin, cs, ds)
+    assert st.handed_over == (handed_expected(od) if shape == "w16r" else 0)
 
 
 @pytest.mark.parametrize("kind", [
@@ -164,7 +177,8 @@ def test_gpu_delay_hand_scheduled_loop(kind, diag, monkeypatch):
         handed = got[3].handed_over
         assert eng.last_kernel == ("mcs::delay_asm_kernel" if handed == 0 else
                                    f"mcs::delay_asm_kernel + mcs::delay_kernel ({handed} of 64 clusters handed over)")
-    assert_delay_parity(arrays, streams, *got[:3], got[4], got[5])
+    od = assert_delay_parity(arrays, streams, *got[:3], got[4], got[5])
+    assert handed == handed_expected(od)
     if kind.startswith("n256"):
         assert handed == 0  # Level1 stays in the hand-scheduled loop
     monkeypatch.setenv("MCS_DELAY_ASM", "0")
@@ -284,5 +298,6 @@ def test_gpu_delay_level1_deadlock_and_capacity(blocked, handed):
     with Engine(0, policy="DELAY") as eng:
         node, start, fin, st, cs, ds = run(eng, arrays, streams)
         assert (st.handed_over == 8) == handed and (st.handed_over == 0) == (not handed)
-    assert_delay_parity(arrays, streams, node, start, fin, cs, ds)
+    od = assert_delay_parity(arrays, streams, node, start, fin, cs, ds)
+    assert st.handed_over == handed_expected(od)
     assert (cs["flags"] & L.MCS_FLAG_DEADLOCK).all() and (ds["l1_left"] >= blocked).all()
