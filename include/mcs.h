@@ -261,6 +261,13 @@ int mcs_rewind(mcs_engine* eng);
  * [off[c], off[c+1]) of mcs_read_placements / mcs_read_jobs. */
 int mcs_read_job_offsets(mcs_engine* eng, uint64_t* off);
 
+/* Where the streams sit on the device (n_clusters + 1 entries): cluster c's segment starts at row
+ * off[c] and has room for off[c + 1] - off[c] jobs, of which mcs_read_job_offsets counts those it
+ * holds.  Without an append the segments are the dense streams; an append that does not fit moves
+ * every segment, which this call makes visible.  Diagnostic: no other call takes
+ * these offsets. */
+int mcs_read_segment_offsets(mcs_engine* eng, uint64_t* off);
+
 /* Per-job results of the last mcs_run, indexed like the submitted jobs. */
 int mcs_read_placements(mcs_engine* eng, int32_t* node, uint32_t* start_s, uint32_t* finish_s);
 int mcs_read_cluster_stats(mcs_engine* eng, mcs_cluster_stats* out, uint32_t n_clusters);
@@ -324,9 +331,10 @@ typedef struct mcs_cluster_state {
 } mcs_cluster_state;
 
 /* One gfx950 launch over every cluster.  MCS_E_STATE, with the cause in mcs_last_error: before a run;
- * after mcs_append_jobs; after a DELAY trading run (Foreign jobs, wrapped counters and virtual nodes
- * with capacity are not in this record: mcs_dtrade_state_series, mcs_trade.h, returns the record that
- * has them); after a FIFO trading run on a sharded engine (a lent record
+ * after mcs_append_jobs (an online session is served by mcs_online_state_series, below); after a
+ * DELAY trading run (Foreign jobs, wrapped counters and virtual nodes with capacity are not in this
+ * record: mcs_dtrade_state_series, mcs_trade.h, returns the record that has them); after a FIFO
+ * trading run on a sharded engine (a lent record
  * does not carry the job's cores and memory, and the borrower's job records live on another rank),
  * one whose lent log overflowed (MCS_FLAG_LOG_OVERFLOW: records were dropped) or one cut short by a
  * slot-pool or LentQueue overflow.  The first call after a FIFO trading run sorts the lent log by
@@ -397,6 +405,41 @@ typedef struct mcs_wait_sample {      /* 24 B */
  * a last sample past 0xFFFFFFFE.  kernel_ms (may be NULL) receives the summed device time. */
 int mcs_wait_time_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                          mcs_wait_sample* out, uint32_t n_clusters, double* kernel_ms);
+
+/* ---- the Start stream of an online session ---------------------------------------------------- */
+/* The two series above and the record at t0_s, read from the current online session (mcs_run with a
+ * horizon, mcs_append_jobs; FIFO or DELAY without trading) as its last mcs_run left it:
+ * after a finite horizon, after a run that followed mcs_append_jobs, on a stream mcs_generate_jobs
+ * fused (its records are materialised, as the batch calls do).  The four batch calls
+ * (mcs_cluster_states, mcs_cluster_state_series, mcs_wait_time_series, mcs_dtrade_state_series) keep
+ * returning MCS_E_STATE after mcs_append_jobs and name this call.
+ *   out[c * n_samples + k]   cluster c at t_k = t0_s + k * period_s, as mcs_cluster_state_series
+ *   wait (may be NULL)       the same shape, as mcs_wait_time_series; a DELAY session only
+ *                            (MCS_E_INVALID under FIFO: only "/delay" feeds WaitTime)
+ *   first (may be NULL)      the full record at t0_s, as mcs_cluster_states
+ * The decided frontier.  Let h be the horizon of the last mcs_run.  After a finite horizon every t_k
+ * must lie below h (MCS_E_INVALID otherwise; mcs_last_error names h).  After a drain
+ * (MCS_TIME_NONE) every t_k up to 0xFFFFFFFE is accepted, and the samples describe the streams so
+ * far as a batch run over them would, the continued Go loop of the wait statistics included.
+ * The guarantee.  A sample below a finite horizon is final: no later append or horizon changes a bit
+ * of it, and it equals, bit for bit, the sample the batch calls return after a batch run over all the
+ * jobs the session ever receives.  Every start below h is decided by mcs_run(h), and appended jobs
+ * arrive at or after h, so an undecided job is exactly one with start >= h > t_k: queued if its
+ * arrival <= t_k, never running.  The wait statistics at t_k < h depend on the arrivals and the
+ * starts below h alone (DESIGN.md §14 has the derivation).  A session that starts over (mcs_rewind,
+ * or a horizon or an append after a batch run) first marks every row undecided, so no result of the
+ * earlier pass is read, whatever jobs the restarted session then receives.
+ * MCS_E_STATE: without an online session (before any run, after a batch or a trading run); after
+ * mcs_rewind until the next run; after a run that failed (MCS_E_RANGE, MCS_E_CAPACITY); after jobs
+ * were appended behind a drain, until the next run.  MCS_E_INVALID: as mcs_cluster_state_series, a
+ * non-NULL wait under FIFO, a sample at or past a finite horizon.  Each call rebuilds its scratch
+ * (batch summaries, wait records) from the session: its cost grows with the history, and nothing is
+ * kept that a later run, append, rewind or segment relayout could leave stale.  kernel_ms (may be
+ * NULL) receives the summed device time of the launches. */
+int mcs_online_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                            mcs_cluster_sample* out, mcs_wait_sample* wait /* may be NULL */,
+                            mcs_cluster_state* first /* may be NULL */, uint32_t n_clusters,
+                            double* kernel_ms);
 
 #ifdef __cplusplus
 }

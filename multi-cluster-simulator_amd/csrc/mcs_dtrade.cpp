@@ -738,7 +738,8 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
                             uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
     if (e->segmented)
-        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs; "
+                                    "in an online session: mcs_online_state_series)");
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
     if (!e->dtrade_run || !e->dtd)
         return fail(e, MCS_E_STATE, "mcs_dtrade_state_series reads a DELAY trading run (MCS_POLICY_DELAY with "

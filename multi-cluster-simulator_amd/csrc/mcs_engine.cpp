@@ -830,9 +830,21 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
     if (e->trade_run)
         if (int st = mcs::trade_state_stream(e, &a, &prep_ms)) return st;
     if (e->segmented)
-        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs; "
+                                    "in an online session: mcs_online_state_series)");
     if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
     if (int st = mcs::ensure_job_records(e)) return st;
+    if (int st = mcs::state_record(e, a, t_s, out, n_clusters, kernel_ms)) return st;
+    if (kernel_ms) *kernel_ms += prep_ms;
+    return MCS_OK;
+}
+
+}  // extern "C"
+
+// the launch of mcs_cluster_states behind its state checks: a holds the second stream after a FIFO
+// trading run, or job_cnt in an online session (mcs_online_state_series), or neither
+int mcs::state_record(mcs_engine* e, mcs::StateArgs a, uint32_t t_s, mcs_cluster_state* out, uint32_t n_clusters,
+                      double* kernel_ms) {
     mcs_cluster_state* d_out = nullptr;
     HIPCHK(e, hipMalloc(&d_out, (e->C ? e->C : 1) * sizeof(mcs_cluster_state)));
     a.node_off = e->d_node_off;
@@ -856,9 +868,11 @@ int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint
         st = hipMemcpy(out, d_out, n_clusters * sizeof(mcs_cluster_state), hipMemcpyDeviceToHost);
     (void)hipFree(d_out);
     if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("cluster states: ") + hipGetErrorString(st));
-    if (kernel_ms) *kernel_ms = ms + prep_ms;
+    if (kernel_ms) *kernel_ms = ms;
     return MCS_OK;
 }
+
+extern "C" {
 
 int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                              mcs_cluster_sample* out, mcs_cluster_state* first, uint32_t n_clusters,
@@ -873,17 +887,38 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     if (e->trade_run)
         if (int st = mcs::trade_state_stream(e, &a.s, &total_ms)) return st;
     if (e->segmented)
-        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs)");
-    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
-    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
-    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
-        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+        return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs; "
+                                    "in an online session: mcs_online_state_series)");
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
     if (int st = mcs::ensure_job_records(e)) return st;
     if (first) {  // the stream's first message: the single record at t0_s
         double ms = 0.0;
         if (int st = mcs_cluster_states(e, t0_s, first, n_clusters, &ms)) return st;
         total_ms += ms;
     }
+    double ms = 0.0;
+    if (int st = mcs::state_series(e, a, t0_s, period_s, n_samples, out, n_clusters, &ms)) return st;
+    if (kernel_ms) *kernel_ms = total_ms + ms;
+    return MCS_OK;
+}
+
+}  // extern "C"
+
+int mcs::series_args_check(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, const void* out,
+                           uint32_t n_clusters) {
+    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
+    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
+    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
+        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+    return MCS_OK;
+}
+
+// the chunked launches of mcs_cluster_state_series behind its checks; a.s as for state_record.  The
+// summaries are computed by every call and freed with it: nothing is kept that a later run, append,
+// rewind or relayout could leave stale.
+int mcs::state_series(mcs_engine* e, mcs::SeriesArgs a, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                      mcs_cluster_sample* out, uint32_t n_clusters, double* kernel_ms) {
+    double total_ms = 0.0;
     if (n_clusters == 0) {
         if (kernel_ms) *kernel_ms = total_ms;
         return MCS_OK;
@@ -897,7 +932,9 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     mcs_cluster_sample* d_out = nullptr;
     uint2* d_summ = nullptr;
     hipError_t st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_cluster_sample));
-    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(e->total_jobs, e->C) * sizeof(uint2));
+    // (over segments with slack the summaries are indexed by capacity: series_summ_size)
+    const uint64_t rows = a.s.job_cnt ? e->job_off[e->C] : e->total_jobs;
+    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(rows, e->C) * sizeof(uint2));
     a.s.node_off = e->d_node_off;
     a.s.cap = e->d_cap;
     a.s.free0 = e->d_free0;
@@ -935,6 +972,8 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
     return MCS_OK;
 }
 
+extern "C" {
+
 int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                          mcs_wait_sample* out, uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
@@ -943,7 +982,8 @@ int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32
         return fail(e, MCS_E_STATE, "the wait time series is rebuilt from a DELAY run without trading "
                                     "(after a DELAY trading run: mcs_dtrade_state_series)");
     if (e->segmented)
-        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from batch runs (not after mcs_append_jobs)");
+        return fail(e, MCS_E_STATE, "the wait time series is rebuilt from batch runs (not after mcs_append_jobs; "
+                                    "in an online session: mcs_online_state_series)");
     return mcs::wait_series(e, t0_s, period_s, n_samples, out, n_clusters, kernel_ms);
 }
 
@@ -952,11 +992,8 @@ int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32
 // WaitTime depends on arrivals, starts and max_wait_s alone (k >= 0 && start != none is the only
 // placement test of wait_prep_kernel), so the same kernels serve a DELAY trading run's placements
 int mcs::wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_wait_sample* out,
-                     uint32_t n_clusters, double* kernel_ms) {
-    if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
-    if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
-    if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
-        return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
+                     uint32_t n_clusters, double* kernel_ms, bool seg) {
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
     for (uint32_t c = 0; c < n_clusters; ++c)  // job indices within a cluster are 32-bit on the device
         if (e->job_off[c + 1] - e->job_off[c] > 0xFFFFFFFEull)
             return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
@@ -981,6 +1018,7 @@ int mcs::wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n
     mcs::WaitArgs a{};
     a.jobs = e->d_jobs;
     a.job_off = e->d_job_off;
+    a.job_cnt = seg ? e->d_job_cnt : nullptr;  // (rec and ev follow job_off: the segments' capacity)
     a.out_node = e->d_out_node;
     a.out_start = e->d_out_start;
     a.rec = d_rec;

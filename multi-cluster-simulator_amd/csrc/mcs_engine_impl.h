@@ -43,8 +43,17 @@ int dtrade_end(mcs_engine* e, mcs_stats* stats);
 inline bool is_dtrade(const mcs_engine* e);
 // the body of mcs_wait_time_series behind its state checks (mcs_engine.cpp): the wait_*_kernels over
 // the engine's placements, whichever DELAY run wrote them (mcs_dtrade_state_series reuses it)
+// seg: an online session's segments (job_off, d_job_cnt), for mcs_online_state_series
 int wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_wait_sample* out,
-                uint32_t n_clusters, double* kernel_ms);
+                uint32_t n_clusters, double* kernel_ms, bool seg = false);
+// the bodies of mcs_cluster_states and mcs_cluster_state_series behind their state checks
+// (mcs_engine.cpp); a.job_cnt / a.s.job_cnt set: the rows are an online session's segments
+int series_args_check(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, const void* out,
+                      uint32_t n_clusters);
+int state_record(mcs_engine* e, StateArgs a, uint32_t t_s, mcs_cluster_state* out, uint32_t n_clusters,
+                 double* kernel_ms);
+int state_series(mcs_engine* e, SeriesArgs a, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                 mcs_cluster_sample* out, uint32_t n_clusters, double* kernel_ms);
 // online mode (mcs_online.cpp)
 void online_free(mcs_engine* e);
 int online_begin(mcs_engine* e);
@@ -175,6 +184,10 @@ struct mcs_engine {
     std::vector<uint32_t> job_cnt;     // jobs per cluster (online; job_off = segment starts)
     std::vector<uint32_t> last_arr;    // last arrival per cluster (append checks)
     std::vector<uint64_t> sum_dur;     // sum of (dur + 1 [+ max_wait]) per cluster (clock bound)
+    // mcs_online_state_series: the session's rows are as the last mcs_run left them (false from
+    // online_begin, a failed run and an append after a drain, until the next run succeeds)
+    bool on_series_ok = false;
+    uint32_t on_series_hor = 0;        // that run's horizon (MCS_TIME_NONE: a drain)
     bool bounds_known = false;         // last_arr / sum_dur filled
 };
 

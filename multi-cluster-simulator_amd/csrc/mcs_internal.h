@@ -146,6 +146,10 @@ struct StateArgs {  // the ClusterState reduction over a run's placements (mcs_s
     const uint32_t* lent_off;
     const LentRun* lent;
     const uint2* lent_summ;  // {earliest start from here on, finish_max} per kSeriesBatch lent runs
+    // an online session (mcs_online_state_series; the SEG instantiations, which read nothing of the
+    // second stream): cluster c's rows are the first job_cnt[c] of the segment that starts at
+    // job_off[c].  Null for a batch run: the rows are then [job_off[c], job_off[c + 1]).
+    const uint32_t* job_cnt;
 };
 hipError_t launch_state(const StateArgs& a, uint32_t max_n, hipStream_t s);  // mcs_state.hip
 
@@ -188,7 +192,10 @@ __host__ __device__ inline uint32_t series_tile(uint32_t n_nodes) {
     if (ts > kSeriesMaxTile) ts = kSeriesMaxTile;
     return (ts - 1u) | 1u;
 }
-// cluster c's summaries start at job_off[c] / kSeriesBatch + c
+// cluster c's summaries start at job_off[c] / kSeriesBatch + c.  Over segments with slack the same
+// index serves, with total_jobs the summed capacity job_off[n_clusters]: a segment holds at most its
+// capacity, so its ceil(job_cnt[c] / kSeriesBatch) pairs end at or before
+// floor(job_off[c + 1] / kSeriesBatch) + c + 1, where the next cluster's begin.
 inline size_t series_summ_size(uint64_t total_jobs, uint32_t n_clusters) {
     return (size_t)(total_jobs / kSeriesBatch) + n_clusters + 1;
 }
@@ -235,6 +242,7 @@ hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStr
 struct WaitArgs {
     const uint4* jobs;
     const uint64_t* job_off;
+    const uint32_t* job_cnt;  // an online session: the rows of each segment (StateArgs::job_cnt); else null
     const int32_t* out_node;
     const uint32_t* out_start;
     uint4* rec;            // per job {h, m, s, arrival}: wait_prep_kernel

@@ -1,6 +1,6 @@
 // mcs_online.cpp — online mode of libmcs.so: mcs_run with a finite horizon,
-// mcs_append_jobs, mcs_rewind, mcs_read_job_offsets.  Host code plus the small data-movement
-// kernels it needs; compiled by hipcc.
+// mcs_append_jobs, mcs_rewind, mcs_read_job_offsets, mcs_online_state_series.  Host code plus the
+// small data-movement kernels it needs; compiled by hipcc.
 //
 // The reference's scheduler is an infinite loop fed by HTTP POSTs (pkg/scheduler/server.go:23-78,
 // scheduler.go:216-369).  A Go caller replacing it through cgo advances the simulated clock in
@@ -179,12 +179,23 @@ int online_begin(mcs_engine* e) {
     if (int st = ensure_l1(e)) return st;
     e->on_cur = 0;
     HIPCHK(e, hipMemset(e->d_ost[0], 0, (e->C ? e->C : 1) * sizeof(OnlineState)));  // valid = 0: the spec
+    // every row is undecided again.  The rows may hold an earlier pass's results (a batch run, or the
+    // session before mcs_rewind), and the HOR kernels write a row only when they decide it: jobs
+    // appended to the restarted session can change later decisions, so a stale start below the next
+    // horizon would be read as decided (mcs_online_state_series, mcs_read_placements).
+    if (e->d_out_node) {
+        const size_t rows = (size_t)(e->job_off[e->C] ? e->job_off[e->C] : 1) + kJobPad;  // as allocated
+        HIPCHK(e, hipMemsetAsync(e->d_out_node, 0xFF, rows * sizeof(int32_t), e->stream));
+        HIPCHK(e, hipMemsetAsync(e->d_out_start, 0xFF, rows * sizeof(uint32_t), e->stream));
+        HIPCHK(e, hipMemsetAsync(e->d_out_finish, 0xFF, rows * sizeof(uint32_t), e->stream));
+    }
     e->on_pool = e->cfg.slot_pool ? (int)e->cfg.slot_pool : auto_pool(e->max_n);
     e->on_t_done = 0;
     e->on_t_hor = 0;
     e->on_floor.assign(e->C, 0u);
     e->online = true;
     e->has_run = false;
+    e->on_series_ok = false;
     return MCS_OK;
 }
 
@@ -238,6 +249,7 @@ int online_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     const bool delay = e->cfg.policy == MCS_POLICY_DELAY;
     const int npl = npl_for(e->max_n ? e->max_n : 1);
     if (npl < 0) return fail(e, MCS_E_INVALID, "cluster too large");
+    e->on_series_ok = false;  // until this run has ended well
     int pool = e->on_pool;
     const int in = e->on_cur, out = 1 - e->on_cur;
 
@@ -366,6 +378,8 @@ int online_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     if (tot.clock_overflowed)
         return fail(e, MCS_E_RANGE, std::to_string(tot.clock_overflowed) +
                                         " cluster(s) stopped: the simulated clock left the uint32 seconds range");
+    e->on_series_ok = true;
+    e->on_series_hor = t_hor;
     return MCS_OK;
 }
 
@@ -558,6 +572,49 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
     e->total_jobs += na;
     if (int st = mcs::upload_counts(e)) return st;
     e->has_jobs = true;
+    // after a drain the series describe the streams as a batch run over them would: no longer, with
+    // jobs that no run has seen (below a finite horizon the samples stay final)
+    if (na && e->on_series_hor == MCS_TIME_NONE) e->on_series_ok = false;
+    return MCS_OK;
+}
+
+// The Start stream of an online session: the SEG instantiations of the state and wait
+// kernels over the session's segments (job_off = segment starts, d_job_cnt = lengths; without an
+// append the segments are the dense streams).  Nothing is kept between calls: the batch summaries and
+// the wait records are rebuilt by each call, so no run, append, rewind or relayout leaves them stale.
+int mcs_online_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                            mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                            uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (!e->online)
+        return fail(e, MCS_E_STATE, "mcs_online_state_series reads an online session (mcs_run with a horizon, "
+                                    "mcs_append_jobs); after a batch run: mcs_cluster_state_series and "
+                                    "mcs_wait_time_series");
+    if (!e->has_run || !e->on_series_ok || !e->d_job_cnt)
+        return fail(e, MCS_E_STATE, "mcs_online_state_series reads the session as its last mcs_run left it: run "
+                                    "first (after mcs_rewind, after a run that failed, after jobs appended "
+                                    "behind a drain)");
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
+    if (wait && e->cfg.policy != MCS_POLICY_DELAY)
+        return fail(e, MCS_E_INVALID, "the wait statistics need a DELAY session: only \"/delay\" feeds WaitTime");
+    const uint32_t h = e->on_series_hor;
+    if (h != MCS_TIME_NONE && (uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s >= h)
+        return fail(e, MCS_E_INVALID, "the last sample lies at or past the last horizon " + std::to_string(h) +
+                                          ": only samples below it are decided");
+    double total_ms = 0.0, ms = 0.0;
+    mcs::SeriesArgs a{};
+    a.s.job_cnt = e->d_job_cnt;
+    if (first) {  // the stream's first message: the single record at t0_s
+        if (int st = mcs::state_record(e, a.s, t0_s, first, n_clusters, &ms)) return st;
+        total_ms += ms;
+    }
+    if (int st = mcs::state_series(e, a, t0_s, period_s, n_samples, out, n_clusters, &ms)) return st;
+    total_ms += ms;
+    if (wait) {
+        if (int st = mcs::wait_series(e, t0_s, period_s, n_samples, wait, n_clusters, &ms, true)) return st;
+        total_ms += ms;
+    }
+    if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
 }
 
@@ -576,6 +633,14 @@ int mcs_read_job_offsets(mcs_engine* e, uint64_t* off) {
     off[0] = 0;
     for (uint32_t c = 0; c < e->C; ++c)
         off[c + 1] = off[c] + (e->online ? e->job_cnt[c] : e->job_off[c + 1] - e->job_off[c]);
+    return MCS_OK;
+}
+
+int mcs_read_segment_offsets(mcs_engine* e, uint64_t* off) {
+    if (int st = check_engine(e)) return st;
+    if (!e->has_jobs) return fail(e, MCS_E_STATE, "no jobs");
+    if (!off) return fail(e, MCS_E_INVALID, "null output");
+    std::copy(e->job_off.begin(), e->job_off.begin() + e->C + 1, off);
     return MCS_OK;
 }
 

@@ -33,6 +33,10 @@
 //
 // After a DELAY trading run (mcs_dtrade_state_series) dt_state_kernel and dt_series_kernel, further
 // down, rebuild the record with virtual-node rows, Foreign jobs and 64-bit wrapping counters.
+//
+// In an online session (mcs_online_state_series) the kernels are the SEG instantiations
+// of the plain code: a cluster's rows are the first job_cnt[c] of the segment at job_off[c], and its
+// batch summaries are indexed over segment capacity (series_summ_size).  Nothing else differs.
 #include "mcs_internal.h"
 #include "mcs_wave.h"
 
@@ -42,8 +46,21 @@ namespace {
 
 constexpr int kStateThreads = 256;
 
-template <bool TRADE>
+// The rows of cluster c.  SEG: the first job_cnt[c] rows of the segment at job_off[c] (an online
+// session: segments with slack after an append); else the dense CSR of a batch run.
+// A job that no horizon has decided yet reads MCS_NODE_UNPLACED / MCS_TIME_NONE, which the plain
+// code below already takes as "queued from its arrival on, never running".
+template <bool SEG>
+__device__ __forceinline__ uint64_t rows_of(const StateArgs& a, uint32_t c) {
+    if constexpr (SEG)
+        return a.job_cnt[c];
+    else
+        return a.job_off[c + 1] - a.job_off[c];
+}
+
+template <bool TRADE, bool SEG = false>
 __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
+    static_assert(!(TRADE && SEG), "an online session has no trading");
     extern __shared__ uint32_t used[];  // [2 * max_n]: cores then memory per node
     const uint32_t c = blockIdx.x;
     const uint32_t tid = threadIdx.x;
@@ -52,7 +69,7 @@ __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
     __syncthreads();
 
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = (uint32_t)rows_of<SEG>(a, c);
     const int32_t* __restrict__ node = a.out_node + j0;
     const uint32_t* __restrict__ start = a.out_start + j0;
     const uint32_t* __restrict__ finish = a.out_finish + j0;
@@ -146,13 +163,13 @@ __global__ __launch_bounds__(kStateThreads) void state_kernel(StateArgs a) {
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kGroup = 8;  // hit batches whose records a thread loads before it uses the first
 
-template <bool TRADE>
+template <bool TRADE, bool SEG = false>
 __global__ __launch_bounds__(kStateThreads) void series_summary_kernel(SeriesArgs a) {
     const uint32_t c = blockIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t N = a.s.node_off[c + 1] - a.s.node_off[c];
     const uint64_t j0 = a.s.job_off[c];
-    const uint64_t J = a.s.job_off[c + 1] - j0;
+    const uint64_t J = rows_of<SEG>(a.s, c);
     const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
     const int32_t* __restrict__ node = a.s.out_node + j0;
     const uint32_t* __restrict__ start = a.s.out_start + j0;
@@ -195,8 +212,9 @@ __device__ __forceinline__ void range_add(uint32_t* row, uint32_t lo, uint32_t h
     }
 }
 
-template <bool TRADE>
+template <bool TRADE, bool SEG = false>
 __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
+    static_assert(!(TRADE && SEG), "an online session has no trading");
     extern __shared__ uint32_t d[];   // [2 N + 2 kSeriesRep + 2][TS]
     __shared__ uint64_t masks[3][4];  // hit / dead / past ballots of a summary round, per wave
     __shared__ uint32_t hits[kStateThreads];  // the round's hit batches, in stream order
@@ -205,7 +223,7 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t n0 = a.s.node_off[c], N = a.s.node_off[c + 1] - n0;
     const uint64_t j0 = a.s.job_off[c];
-    const uint64_t J = a.s.job_off[c + 1] - j0;
+    const uint64_t J = rows_of<SEG>(a.s, c);
     const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
     const int32_t* __restrict__ node = a.s.out_node + j0;
     const uint32_t* __restrict__ start = a.s.out_start + j0;
@@ -953,7 +971,9 @@ hipError_t launch_lent_prep(const LentPrepArgs& a, hipStream_t s) {
 
 hipError_t launch_series_summary(const SeriesArgs& a, hipStream_t s) {
     if (a.s.n_clusters == 0) return hipSuccess;
-    if (a.s.lent_off)
+    if (a.s.job_cnt)
+        hipLaunchKernelGGL((series_summary_kernel<false, true>), dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
+    else if (a.s.lent_off)
         hipLaunchKernelGGL(series_summary_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
     else
         hipLaunchKernelGGL(series_summary_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads), 0, s, a);
@@ -966,11 +986,15 @@ hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t 
     if (max_n > 1024u) return hipErrorInvalidValue;  // the ABI's node limit: a tile of at least 9 samples
     uint32_t lds = 4u * series_rows(max_n) * kSeriesMaxTile;
     if (lds > kSeriesLds) lds = kSeriesLds;
-    const void* fn = a.s.lent_off ? reinterpret_cast<const void*>(series_kernel<true>)
-                                  : reinterpret_cast<const void*>(series_kernel<false>);
+    if (a.s.job_cnt && a.s.lent_off) return hipErrorInvalidValue;  // no trading in an online session
+    const void* fn = a.s.job_cnt    ? reinterpret_cast<const void*>(series_kernel<false, true>)
+                     : a.s.lent_off ? reinterpret_cast<const void*>(series_kernel<true>)
+                                    : reinterpret_cast<const void*>(series_kernel<false>);
     hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
     if (st != hipSuccess) return st;
-    if (a.s.lent_off)
+    if (a.s.job_cnt)
+        hipLaunchKernelGGL((series_kernel<false, true>), dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    else if (a.s.lent_off)
         hipLaunchKernelGGL(series_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
     else
         hipLaunchKernelGGL(series_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads), lds, s, a);
@@ -1011,7 +1035,10 @@ hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStr
 
 hipError_t launch_state(const StateArgs& a, uint32_t max_n, hipStream_t s) {
     if (a.n_clusters == 0) return hipSuccess;
-    if (a.lent_off)
+    if (a.job_cnt && a.lent_off) return hipErrorInvalidValue;  // no trading in an online session
+    if (a.job_cnt)
+        hipLaunchKernelGGL((state_kernel<false, true>), dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);
+    else if (a.lent_off)
         hipLaunchKernelGGL(state_kernel<true>, dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);
     else
         hipLaunchKernelGGL(state_kernel<false>, dim3(a.n_clusters), dim3(kStateThreads), 2 * max_n * sizeof(uint32_t), s, a);

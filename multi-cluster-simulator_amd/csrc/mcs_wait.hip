@@ -32,6 +32,8 @@
 //   wait_finish_kernel  prefix sums of A and B along the samples in rounds of 256 with a carried
 //                       base, JobsCount by bisection of the sorted arrivals, and the three fields.
 // Every loop is bounded by J or the sample count; no workgroup waits for another.
+// Each kernel has a SEG instantiation for an online session (mcs_online_state_series): J is then the
+// segment's job_cnt[c], not the distance to the next segment.
 #include "mcs_internal.h"
 #include "mcs_wave.h"
 
@@ -64,15 +66,28 @@ __device__ __forceinline__ Clamp clamp_then(const Clamp& first, const Clamp& sec
     return r;
 }
 
+// The rows of cluster c.  SEG: the first job_cnt[c] rows of the segment at job_off[c] (an online
+// session, mcs_online_state_series); rec and ev are addressed by the same segment starts.  A job no
+// horizon has decided yet reads MCS_NODE_UNPLACED / MCS_TIME_NONE, so its s is kInf below: d is then
+// exact wherever it lies below the horizon and at or above it otherwise.
+template <bool SEG>
+__device__ __forceinline__ uint32_t wait_rows(const WaitArgs& a, uint32_t c) {
+    if constexpr (SEG)
+        return a.job_cnt[c];
+    else
+        return (uint32_t)(a.job_off[c + 1] - a.job_off[c]);
+}
+
 __device__ __forceinline__ uint32_t sat32(long long x) { return x >= (long long)kNone ? kNone : (uint32_t)x; }
 
+template <bool SEG>
 __global__ __launch_bounds__(kWaitThreads) void wait_prep_kernel(WaitArgs a) {
     __shared__ Clamp wave_tot[kWaitThreads / kWave];
     __shared__ long long carry_s;
     const uint32_t c = blockIdx.x;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ jobs = a.jobs + j0;
     const int32_t* __restrict__ node = a.out_node + j0;
     const uint32_t* __restrict__ start = a.out_start + j0;
@@ -120,10 +135,11 @@ __global__ __launch_bounds__(kWaitThreads) void wait_prep_kernel(WaitArgs a) {
     }
 }
 
+template <bool SEG>
 __global__ __launch_bounds__(kWaitThreads) void wait_skip_kernel(WaitArgs a) {
     const uint32_t c = blockIdx.x;
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ rec = a.rec + j0;
     uint2* __restrict__ ev = a.ev + j0;
     for (uint64_t base = 0; base < J; base += kWaitThreads) {
@@ -177,10 +193,11 @@ __device__ __forceinline__ unsigned long long* acc_of(mcs_wait_sample* s) {
     return reinterpret_cast<unsigned long long*>(s);
 }
 
+template <bool SEG>
 __global__ __launch_bounds__(kWaitThreads) void wait_accum_kernel(WaitArgs a) {
     const uint32_t c = blockIdx.x;
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ rec = a.rec + j0;
     const uint2* __restrict__ ev = a.ev + j0;
     const uint32_t n = a.n_samples, period = a.period, t_first = a.t0;
@@ -232,12 +249,13 @@ __global__ __launch_bounds__(kWaitThreads) void wait_accum_kernel(WaitArgs a) {
     }
 }
 
+template <bool SEG>
 __global__ __launch_bounds__(kWaitThreads) void wait_finish_kernel(WaitArgs a) {
     __shared__ unsigned long long wave_tot[2][kWaitThreads / kWave];
     const uint32_t c = blockIdx.x;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ rec = a.rec + j0;
     const uint32_t n = a.n_samples;
     mcs_wait_sample* const row = a.out + (size_t)c * n;
@@ -300,10 +318,16 @@ __global__ __launch_bounds__(kWaitThreads) void wait_finish_kernel(WaitArgs a) {
 
 hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s) {
     if (a.n_clusters == 0) return hipSuccess;
-    hipLaunchKernelGGL(wait_prep_kernel, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    if (a.job_cnt)
+        hipLaunchKernelGGL(wait_prep_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(wait_prep_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     hipError_t st = hipGetLastError();
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(wait_skip_kernel, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    if (a.job_cnt)
+        hipLaunchKernelGGL(wait_skip_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(wait_skip_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -311,10 +335,16 @@ hipError_t launch_wait_series(const WaitArgs& a, hipStream_t s) {
     if (a.n_clusters == 0 || a.n_samples == 0) return hipSuccess;
     hipError_t st = hipMemsetAsync(a.out, 0, (size_t)a.n_clusters * a.n_samples * sizeof(mcs_wait_sample), s);
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(wait_accum_kernel, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    if (a.job_cnt)
+        hipLaunchKernelGGL(wait_accum_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(wait_accum_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     st = hipGetLastError();
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(wait_finish_kernel, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    if (a.job_cnt)
+        hipLaunchKernelGGL(wait_finish_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(wait_finish_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     return hipGetLastError();
 }
 

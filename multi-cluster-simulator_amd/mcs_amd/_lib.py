@@ -246,6 +246,7 @@ SIGNATURES = [
     ("mcs_append_jobs", C.c_int, [vp, u32p, u32p, u32p, u32p, u64p]),
     ("mcs_rewind", C.c_int, [vp]),
     ("mcs_read_job_offsets", C.c_int, [vp, u64p]),
+    ("mcs_read_segment_offsets", C.c_int, [vp, u64p]),
     ("mcs_read_placements", C.c_int, [vp, i32p, u32p, u32p]),
     ("mcs_read_cluster_stats", C.c_int, [vp, C.POINTER(mcs_cluster_stats), C.c_uint32]),
     ("mcs_read_delay_stats", C.c_int, [vp, C.POINTER(mcs_delay_cluster_stats), C.c_uint32]),
@@ -262,6 +263,9 @@ SIGNATURES = [
                                            C.POINTER(mcs_cluster_state), C.c_uint32, C.POINTER(C.c_double)]),
     ("mcs_wait_time_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_wait_sample),
                                        C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_online_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
+                                          C.POINTER(mcs_wait_sample), C.POINTER(mcs_cluster_state), C.c_uint32,
+                                          C.POINTER(C.c_double)]),
     # include/mcs_trade.h
     ("mcs_dtrade_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
                                           C.POINTER(mcs_wait_sample), C.POINTER(mcs_cluster_state), C.c_uint32,

@@ -404,6 +404,12 @@ class Engine:
         self._c(L.lib().mcs_read_job_offsets(self._h, L.ptr(off, C.c_uint64)))
         return off
 
+    def segment_offsets(self) -> np.ndarray:
+        """mcs_read_segment_offsets: where each cluster's segment starts on the device, and its room."""
+        off = np.zeros(self.num_clusters + 1, np.uint64)
+        self._c(L.lib().mcs_read_segment_offsets(self._h, L.ptr(off, C.c_uint64)))
+        return off
+
     def placements(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         n = self.num_jobs
         node = np.empty(n, np.int32)
@@ -499,6 +505,35 @@ class Engine:
         first = np.zeros(n, CLUSTER_STATE_DTYPE)
         ms = C.c_double(0.0)
         self._c(L.lib().mcs_dtrade_state_series(
+            self._h, int(t0_s), int(period_s), int(n_samples), samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None,
+            first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
+        return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
+
+    def online_state_series(self, t0_s: int, period_s: int, n_samples: int, with_wait: Optional[bool] = None,
+                            with_time: bool = False):
+        """The ClusterState time series, the wait statistics and the records at t0_s of the current
+        online session (mcs_online_state_series; run(h), append_jobs, FIFO or DELAY without trading)
+        as its last run() left it: samples t0_s + k * period_s, k < n_samples.  After a finite
+        horizon h every sample must lie below h, and is then final: equal, bit for bit, to what
+        cluster_state_series and wait_time_series return after a batch run over every job the
+        session ever receives.  After a drain any second is accepted.
+        Returns (samples, wait, first) as dtrade_state_series does; with_wait None: the wait
+        statistics under DELAY, none under FIFO (asking for them there is MCS_E_INVALID); with_time
+        adds the kernel ms.  A row feeds wire.start_stream like a batch run's.  MCSError
+        (MCS_E_STATE) without an online session, after rewind() until the next run, after a run that
+        failed and after jobs appended behind a drain."""
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        if with_wait is None:
+            with_wait = self.policy == "DELAY"
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), CLUSTER_SAMPLE_DTYPE)
+        wait = np.zeros((n, max(int(n_samples), 0)), WAIT_SAMPLE_DTYPE) if with_wait else None
+        first = np.zeros(n, CLUSTER_STATE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(L.lib().mcs_online_state_series(
             self._h, int(t0_s), int(period_s), int(n_samples), samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
             wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None,
             first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
