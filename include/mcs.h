@@ -441,6 +441,68 @@ int mcs_online_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, u
                             mcs_cluster_state* first /* may be NULL */, uint32_t n_clusters,
                             double* kernel_ms);
 
+/* ---- the Level1 list over time: what ProvideJobs hands the trader ---------------------------- */
+/* The other half of the ResourceChannel service (pkg/scheduler/trader_server.go): ProvideJobs (:69-94,
+ * over GetLevel1, scheduler.go:204-214) sends sched.Level1 in batches of 20, the last one padded with
+ * zero jobs (D9), and the trader sizes every contract from that list: calculateFastNodeSize and
+ * calculateSmallNodeSize (pkg/trader/scheduler_client.go:126-289).  One sample holds the list's length,
+ * its first row and the finished ContractRequest of both sizings after the Delay iteration at t_k
+ * (SDELAY) — the convention of mcs_wait_time_series, and the point at which a trader
+ * round of tick t_k reads Level1 in the lock-step order (scheduler steps, state samples, trader
+ * rounds; mcs_trade.h).
+ * ContractRequest.Price is not returned: it is always 0.  Both sizings multiply by
+ * Trader.MaximimumCoreCost and Trader.MemoryCost, which nothing ever sets (trader.go:34-35), and
+ * Budget is -1 (trader.go:53), so no price is positive and the budget never ends a sizing loop. */
+typedef struct mcs_level1_sample {   /* 24 B */
+    uint32_t len;          /* len(sched.Level1) after the Delay iteration at t_k                     */
+    uint32_t cores;        /* ContractRequest.Cores of both sizings: sum of CoresNeeded mod 2^32     */
+    uint32_t mem;          /* ... Memory, likewise (both sizings add in uint32 / int32 and wrap; they
+                              agree while every single request is at most 2^31: the small-node sizing
+                              drops a larger one, :238-250, and this field then is the fast one)     */
+    uint32_t fast_time_s;  /* calculateFastNodeSize: max Duration over the list, seconds; 0 if empty */
+    uint32_t small_time_s; /* calculateSmallNodeSize over the list padded to a multiple of 20 (D9):
+                              each job sets the time to its Duration if the time so far is below it,
+                              else to 0 (:263-265), so a padded last batch leaves 0                  */
+    uint32_t head;         /* row of Level1[0] in the cluster's stream; MCS_TIME_NONE when empty     */
+} mcs_level1_sample;
+
+/* Every sample t_k = t0_s + k * period_s, k < n_samples, of every cluster, rebuilt on the GPU from the
+ * last DELAY run's arrivals and starts and the engine's max_wait_s:
+ * Level1(t) = { j : m_j <= t < s_j } in stream order, m_j the iteration at which job j, still failing
+ * as the Level0 head, moves to Level1 and s_j its start.  out[c * n_samples + k] is cluster c at t_k.
+ * The Go loop is continued past the run's end, as mcs_wait_time_series does: a drained cluster reads
+ * as empty, a deadlocked one keeps the jobs it has left up to second 0xFFFFFFFE, and a job undecided
+ * when a trading run stopped at t_max_s counts as never placed.
+ * Accepted after a DELAY run without trading and after a DELAY trading run on one engine (every logged
+ * contract of mcs_read_contracts then equals the sample at its (t_s, requester): cores, mem and
+ * fast_time_s under policy 0, small_time_s under policy 1).  MCS_E_STATE, with the cause in
+ * mcs_last_error: before a run, after a FIFO or FIFO trading run, on a sharded engine
+ * (mcs_set_shard with world > 1), after mcs_append_jobs (an online session is served by
+ * mcs_online_level1_series).  MCS_E_INVALID as mcs_cluster_state_series: period_s == 0,
+ * n_samples == 0, out == NULL, n_clusters above the engine's count, or a last sample past 0xFFFFFFFE.
+ * kernel_ms (may be NULL) receives the summed device time of the launches. */
+int mcs_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                      mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms);
+
+/* The same samples of the current online session (a DELAY session; MCS_E_INVALID under FIFO, which has
+ * no Level1), under the rules of mcs_online_state_series: read as the last mcs_run left the session;
+ * after a finite horizon h every t_k must lie below h (MCS_E_INVALID otherwise) and a sample below it
+ * is final, equal bit for bit to mcs_level1_series after a batch run over all the jobs the session
+ * ever receives (a job undecided at h has m_j exact wherever it lies below h and s_j >= h > t_k);
+ * after a drain every t_k up to 0xFFFFFFFE is accepted.  MCS_E_STATE as mcs_online_state_series:
+ * without an online session, after mcs_rewind until the next run, after a run that failed, after jobs
+ * appended behind a drain.  Nothing is kept between calls. */
+int mcs_online_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                             mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms);
+
+/* ProvideJobs at one second: the rows of Level1(t_s) of one cluster in list order, as indices into
+ * the cluster's stream (row r is job job_offsets[cluster] + r of mcs_read_jobs, which has its
+ * CoresNeeded, MemoryNeeded and Duration).  *n receives len(Level1); it may exceed cap, and then the
+ * first cap rows are written (rows may be NULL when cap is 0).  The preconditions of
+ * mcs_level1_series; MCS_E_INVALID also for a cluster out of range, t_s past 0xFFFFFFFE and n == NULL. */
+int mcs_read_level1(mcs_engine* eng, uint32_t cluster, uint32_t t_s, uint32_t* rows, uint32_t cap,
+                    uint32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1052,3 +1052,155 @@ int mcs::wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n
     if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
 }
+
+// mcs_level1_series and mcs_read_level1 read the placements of a DELAY run, with or without trading,
+// that this engine holds whole
+static int level1_state_check(mcs_engine* e) {
+    if (!e->has_run || !e->delay_run) return fail(e, MCS_E_STATE, "no DELAY run");
+    if (e->world != 1)
+        return fail(e, MCS_E_STATE, "the Level1 series is rebuilt on one engine that holds the whole system "
+                                    "(not on a shard of mcs_set_shard)");
+    if (e->segmented)
+        return fail(e, MCS_E_STATE, "the Level1 series is rebuilt from batch runs (not after mcs_append_jobs; "
+                                    "in an online session: mcs_online_level1_series)");
+    return MCS_OK;
+}
+
+extern "C" {
+
+int mcs_level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                      mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (int st = level1_state_check(e)) return st;
+    return mcs::level1_series(e, t0_s, period_s, n_samples, out, n_clusters, kernel_ms);
+}
+
+int mcs_read_level1(mcs_engine* e, uint32_t cluster, uint32_t t_s, uint32_t* rows, uint32_t cap, uint32_t* n) {
+    if (int st = check_engine(e)) return st;
+    if (int st = level1_state_check(e)) return st;
+    if (cluster >= e->C) return fail(e, MCS_E_INVALID, "cluster out of range");
+    if (!n || (cap && !rows)) return fail(e, MCS_E_INVALID, "bad output");
+    if (t_s > 0xFFFFFFFEu) return fail(e, MCS_E_INVALID, "t_s lies past second 0xFFFFFFFE");
+    const uint64_t J = e->job_off[cluster + 1] - e->job_off[cluster];
+    if (J > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    if (J == 0) {
+        *n = 0;
+        return MCS_OK;
+    }
+    const uint32_t room = cap < J ? cap : (uint32_t)J;  // the list holds at most J rows
+    uint4* d_rec = nullptr;
+    uint32_t* d_rows = nullptr;  // [room] rows, then the length
+    hipError_t st = hipMalloc(&d_rec, J * sizeof(uint4));
+    if (st == hipSuccess) st = hipMalloc(&d_rows, ((size_t)room + 1) * sizeof(uint32_t));
+    mcs::WaitArgs w{};  // the one cluster as cluster 0 of a launch of its own
+    w.jobs = e->d_jobs;
+    w.job_off = e->d_job_off + cluster;
+    w.out_node = e->d_out_node;
+    w.out_start = e->d_out_start;
+    w.rec = d_rec;
+    w.rec_off = e->job_off[cluster];
+    w.max_wait = e->cfg.max_wait_s;
+    w.n_clusters = 1;
+    mcs::Level1Args a{};
+    a.jobs = w.jobs;
+    a.job_off = w.job_off;
+    a.rec = d_rec;
+    a.rec_off = w.rec_off;
+    a.t0 = t_s;
+    a.n_clusters = 1;
+    a.cap = room;
+    a.rows = d_rows;
+    a.n_out = d_rows + room;
+    if (st == hipSuccess) st = mcs::launch_wait_rec(w, e->stream);
+    if (st == hipSuccess) st = mcs::launch_level1_list(a, e->stream);
+    if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+    uint32_t len = 0;
+    if (st == hipSuccess) st = hipMemcpy(&len, d_rows + room, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (st == hipSuccess && len && room)
+        st = hipMemcpy(rows, d_rows, (size_t)(len < room ? len : room) * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d_rec);
+    (void)hipFree(d_rows);
+    if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("read level1: ") + hipGetErrorString(st));
+    *n = len;
+    return MCS_OK;
+}
+
+}  // extern "C"
+
+// Level1 depends on arrivals, starts and max_wait_s alone, like WaitTime (wait_series above): the same
+// records serve a plain DELAY run, a DELAY trading run and an online session's segments.  The records
+// and the batch summaries are rebuilt by every call and freed with it.
+int mcs::level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_level1_sample* out,
+                       uint32_t n_clusters, double* kernel_ms, bool seg) {
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
+    for (uint32_t c = 0; c < n_clusters; ++c)  // job indices within a cluster are 32-bit on the device
+        if (e->job_off[c + 1] - e->job_off[c] > 0xFFFFFFFEull)
+            return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    if (n_clusters == 0) {
+        if (kernel_ms) *kernel_ms = 0.0;
+        return MCS_OK;
+    }
+    // samples per launch: the device buffer stays within 256 MiB (MCS_SERIES_CHUNK overrides the count)
+    uint64_t chunk = (256ull << 20) / (sizeof(mcs_level1_sample) * (uint64_t)n_clusters);
+    if (const char* env = getenv("MCS_SERIES_CHUNK"))
+        if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
+    // (one workgroup per cluster and tile: the grid stays below 2^31)
+    const uint64_t grid_max = (0x7FFFFFFFull / n_clusters) * mcs::kLevel1Tile;
+    if (chunk > grid_max) chunk = grid_max;
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_samples) chunk = n_samples;
+    const uint64_t nj = e->job_off[n_clusters] ? e->job_off[n_clusters] : 1;
+    mcs_level1_sample* d_out = nullptr;
+    uint4* d_rec = nullptr;
+    uint32_t* d_summ = nullptr;
+    hipError_t st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_level1_sample));
+    if (st == hipSuccess) st = hipMalloc(&d_rec, nj * sizeof(uint4));
+    // (over segments with slack the summaries are indexed by capacity: series_summ_size)
+    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(nj, n_clusters) * sizeof(uint32_t));
+    mcs::WaitArgs w{};
+    w.jobs = e->d_jobs;
+    w.job_off = e->d_job_off;
+    w.job_cnt = seg ? e->d_job_cnt : nullptr;  // (rec follows job_off: the segments' capacity)
+    w.out_node = e->d_out_node;
+    w.out_start = e->d_out_start;
+    w.rec = d_rec;
+    w.max_wait = e->cfg.max_wait_s;
+    w.n_clusters = n_clusters;
+    mcs::Level1Args a{};
+    a.jobs = w.jobs;
+    a.job_off = w.job_off;
+    a.job_cnt = w.job_cnt;
+    a.rec = d_rec;
+    a.summ = d_summ;
+    a.out = d_out;
+    a.period = period_s;
+    a.n_clusters = n_clusters;
+    double total_ms = 0.0;
+    for (uint64_t k0 = 0; st == hipSuccess && k0 < n_samples; k0 += chunk) {
+        const uint32_t nk = (uint32_t)(n_samples - k0 < chunk ? n_samples - k0 : chunk);
+        a.t0 = (uint32_t)(t0_s + k0 * period_s);
+        a.n_samples = nk;
+        a.n_tiles = (nk + mcs::kLevel1Tile - 1u) / mcs::kLevel1Tile;
+        st = hipEventRecord(e->ev0, e->stream);
+        if (st == hipSuccess && k0 == 0) st = mcs::launch_wait_rec(w, e->stream);
+        if (st == hipSuccess && k0 == 0) st = mcs::launch_level1_summary(a, e->stream);
+        if (st == hipSuccess) st = mcs::launch_level1_series(a, e->stream);
+        if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
+        total_ms += ms;
+        if (st == hipSuccess)  // the chunk's columns of every cluster's row
+            st = hipMemcpy2D(out + k0, (size_t)n_samples * sizeof(mcs_level1_sample), d_out,
+                             (size_t)nk * sizeof(mcs_level1_sample), (size_t)nk * sizeof(mcs_level1_sample),
+                             n_clusters, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_out);
+    (void)hipFree(d_rec);
+    (void)hipFree(d_summ);
+    if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("level1 series: ") + hipGetErrorString(st));
+    if (kernel_ms) *kernel_ms = total_ms;
+    return MCS_OK;
+}

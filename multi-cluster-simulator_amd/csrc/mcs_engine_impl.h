@@ -46,6 +46,11 @@ inline bool is_dtrade(const mcs_engine* e);
 // seg: an online session's segments (job_off, d_job_cnt), for mcs_online_state_series
 int wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_wait_sample* out,
                 uint32_t n_clusters, double* kernel_ms, bool seg = false);
+// the body of mcs_level1_series behind its state checks (mcs_engine.cpp): wait_prep_kernel's records
+// and the level1_*_kernels over the engine's placements; seg as for wait_series
+// (mcs_online_level1_series)
+int level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, mcs_level1_sample* out,
+                  uint32_t n_clusters, double* kernel_ms, bool seg = false);
 // the bodies of mcs_cluster_states and mcs_cluster_state_series behind their state checks
 // (mcs_engine.cpp); a.job_cnt / a.s.job_cnt set: the rows are an online session's segments
 int series_args_check(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples, const void* out,

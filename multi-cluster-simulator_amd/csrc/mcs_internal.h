@@ -249,9 +249,35 @@ struct WaitArgs {
     uint2* ev;             // per job {the entry its Level1 placement steps over, that entry's run}: wait_skip_kernel
     mcs_wait_sample* out;  // [n_clusters][n_samples], cluster-major
     uint32_t max_wait, t0, period, n_samples, n_clusters;
+    uint64_t rec_off;      // rec[0] is row rec_off of the job array (0: rec covers every row; ev always does)
 };
+hipError_t launch_wait_rec(const WaitArgs& a, hipStream_t s);     // rec alone: the clamp scan (mcs_level1.hip reads it)
 hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s);    // rec and ev: once per call
 hipError_t launch_wait_series(const WaitArgs& a, hipStream_t s);  // one chunk of samples
+
+// The Level1 list over time (mcs_level1.hip): len(Level1), both contract sizes and the head row after
+// the Delay iteration at the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters,
+// from wait_prep_kernel's records; and the member rows of one cluster at one second.
+struct Level1Args {
+    const uint4* jobs;
+    const uint64_t* job_off;
+    const uint32_t* job_cnt;  // an online session: the rows of each segment (WaitArgs::job_cnt); else null
+    const uint4* rec;         // WaitArgs::rec
+    uint64_t rec_off;         // WaitArgs::rec_off
+    uint32_t* summ;           // per kSeriesBatch jobs the largest s among the jobs that move to Level1,
+                              // indexed as SeriesArgs::summ (series_summ_size words); the list kernel reads none
+    mcs_level1_sample* out;   // [n_clusters][n_samples], cluster-major
+    uint32_t t0, period, n_samples, n_clusters;
+    uint32_t n_tiles;         // ceil(n_samples / kLevel1Tile)
+    // the list kernel: cluster 0 of job_off at second t0
+    uint32_t cap;             // rows has room for cap entries
+    uint32_t* rows;
+    uint32_t* n_out;          // len(Level1), whatever cap is
+};
+constexpr uint32_t kLevel1Tile = 32;  // samples one workgroup walks, its scan bounds carried along
+hipError_t launch_level1_summary(const Level1Args& a, hipStream_t s);  // summ: once per call
+hipError_t launch_level1_series(const Level1Args& a, hipStream_t s);   // one chunk of samples
+hipError_t launch_level1_list(const Level1Args& a, hipStream_t s);
 
 // Launchers (mcs_kernels.hip).  Return hipSuccess or the launch error.
 hipError_t launch_fifo(const FifoArgs& a, int npl, int pool, bool hor, hipStream_t s);

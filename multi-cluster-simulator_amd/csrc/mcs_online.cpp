@@ -1,6 +1,6 @@
 // mcs_online.cpp — online mode of libmcs.so: mcs_run with a finite horizon,
-// mcs_append_jobs, mcs_rewind, mcs_read_job_offsets, mcs_online_state_series.  Host code plus the
-// small data-movement kernels it needs; compiled by hipcc.
+// mcs_append_jobs, mcs_rewind, mcs_read_job_offsets, mcs_online_state_series,
+// mcs_online_level1_series.  Host code plus the small data-movement kernels it needs; compiled by hipcc.
 //
 // The reference's scheduler is an infinite loop fed by HTTP POSTs (pkg/scheduler/server.go:23-78,
 // scheduler.go:216-369).  A Go caller replacing it through cgo advances the simulated clock in
@@ -616,6 +616,28 @@ int mcs_online_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     }
     if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
+}
+
+// ProvideJobs' view of an online session: the SEG instantiations of the wait records and the Level1
+// kernels over the session's segments, under the decided-frontier rules of mcs_online_state_series.
+int mcs_online_level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                             mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (!e->online)
+        return fail(e, MCS_E_STATE, "mcs_online_level1_series reads an online session (mcs_run with a horizon, "
+                                    "mcs_append_jobs); after a batch run: mcs_level1_series");
+    if (!e->has_run || !e->on_series_ok || !e->d_job_cnt)
+        return fail(e, MCS_E_STATE, "mcs_online_level1_series reads the session as its last mcs_run left it: run "
+                                    "first (after mcs_rewind, after a run that failed, after jobs appended "
+                                    "behind a drain)");
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
+    if (e->cfg.policy != MCS_POLICY_DELAY)
+        return fail(e, MCS_E_INVALID, "the Level1 series needs a DELAY session: Scheduler.Fifo has no Level1");
+    const uint32_t h = e->on_series_hor;
+    if (h != MCS_TIME_NONE && (uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s >= h)
+        return fail(e, MCS_E_INVALID, "the last sample lies at or past the last horizon " + std::to_string(h) +
+                                          ": only samples below it are decided");
+    return mcs::level1_series(e, t0_s, period_s, n_samples, out, n_clusters, kernel_ms, true);
 }
 
 int mcs_rewind(mcs_engine* e) {

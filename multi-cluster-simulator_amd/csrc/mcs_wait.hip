@@ -21,7 +21,8 @@
 //   wait_prep_kernel    d_j = min(s_j, max(a_j + W, d_{j-1} + 1)) is a clamp of d_{j-1} + 1, and
 //                       clamps compose to clamps: a scan in rounds of 256 jobs with a carried d.
 //                       Writes {h, m, s, a} per job (16 B), the times saturated at 0xFFFFFFFF (past
-//                       every sample second).
+//                       every sample second).  launch_wait_rec runs it alone: the Level1 kernels
+//                       (mcs_level1.hip) read the same records.
 //   wait_skip_kernel    one lane per Level1 placement P finds the entry it steps over and the length
 //                       of that entry's run of skipped seconds; writes {k, run} per job (8 B).
 //   wait_accum_kernel   per chunk of samples: every job adds its differences of A and B at the first
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(kWaitThreads) void wait_prep_kernel(WaitArgs a) {
     const uint4* __restrict__ jobs = a.jobs + j0;
     const int32_t* __restrict__ node = a.out_node + j0;
     const uint32_t* __restrict__ start = a.out_start + j0;
-    uint4* __restrict__ rec = a.rec + j0;
+    uint4* __restrict__ rec = a.rec + (j0 - a.rec_off);
     const long long W = (long long)a.max_wait;
     long long carry = -1;  // d_{-1}
     for (uint64_t base = 0; base < J; base += kWaitThreads) {  // 64-bit: base + 256 may pass 2^32
@@ -316,13 +317,18 @@ __global__ __launch_bounds__(kWaitThreads) void wait_finish_kernel(WaitArgs a) {
 
 }  // namespace
 
-hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s) {
+hipError_t launch_wait_rec(const WaitArgs& a, hipStream_t s) {
     if (a.n_clusters == 0) return hipSuccess;
     if (a.job_cnt)
         hipLaunchKernelGGL(wait_prep_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     else
         hipLaunchKernelGGL(wait_prep_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
-    hipError_t st = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s) {
+    if (a.n_clusters == 0) return hipSuccess;
+    hipError_t st = launch_wait_rec(a, s);
     if (st != hipSuccess) return st;
     if (a.job_cnt)
         hipLaunchKernelGGL(wait_skip_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);

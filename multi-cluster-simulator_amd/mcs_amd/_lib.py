@@ -155,6 +155,10 @@ class mcs_wait_sample(C.Structure):
     ]
 
 
+class mcs_level1_sample(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("len", "cores", "mem", "fast_time_s", "small_time_s", "head")]
+
+
 class mcs_delay_cluster_stats(C.Structure):
     _fields_ = [
         ("total_wait_ms", C.c_int64),
@@ -266,6 +270,11 @@ SIGNATURES = [
     ("mcs_online_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
                                           C.POINTER(mcs_wait_sample), C.POINTER(mcs_cluster_state), C.c_uint32,
                                           C.POINTER(C.c_double)]),
+    ("mcs_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),
+                                    C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_online_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),
+                                           C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_read_level1", C.c_int, [vp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]),
     # include/mcs_trade.h
     ("mcs_dtrade_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_cluster_sample),
                                           C.POINTER(mcs_wait_sample), C.POINTER(mcs_cluster_state), C.c_uint32,

@@ -148,6 +148,9 @@ CLUSTER_SAMPLE_DTYPE = np.dtype([("cores_utilization", "<f4"), ("memory_utilizat
 
 WAIT_SAMPLE_DTYPE = np.dtype([("average_wait_time", "<f8"), ("total_wait_ms", "<i8"), ("jobs_count", "<i8")])
 
+LEVEL1_SAMPLE_DTYPE = np.dtype([("len", "<u4"), ("cores", "<u4"), ("mem", "<u4"), ("fast_time_s", "<u4"),
+                                ("small_time_s", "<u4"), ("head", "<u4")])
+
 CONTRACT_DTYPE = np.dtype([("t", "<u4"), ("requester", "<u4"), ("winner", "<i4"), ("approvals", "<u4"),
                            ("policy", "<u4"), ("cores", "<u4"), ("mem", "<u4"), ("time_s", "<u4"), ("failed", "<u4"),
                            ("pad", "<u4")])
@@ -539,6 +542,46 @@ class Engine:
             first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
         return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
 
+    def _level1(self, fn, t0_s, period_s, n_samples, with_time):
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), LEVEL1_SAMPLE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(fn(self._h, int(t0_s), int(period_s), int(n_samples),
+                   samples.ctypes.data_as(C.POINTER(L.mcs_level1_sample)), n, C.byref(ms)))
+        return (samples, ms.value) if with_time else samples
+
+    def level1_series(self, t0_s: int, period_s: int, n_samples: int, with_time: bool = False):
+        """What ProvideJobs hands the trader over time (mcs_level1_series): len(Level1), the
+        ContractRequest of both sizings (cores, mem, fast_time_s / small_time_s) and the row of
+        Level1[0] after the Delay iteration at t0_s + k * period_s, k < n_samples, of the last DELAY
+        run, with or without trading, as an array of shape (num_clusters, n_samples) of
+        LEVEL1_SAMPLE_DTYPE.  with_time: (samples, kernel ms).  MCSError (MCS_E_STATE) before a run,
+        after a FIFO run, on a sharded engine and after append_jobs (online_level1_series)."""
+        return self._level1(L.lib().mcs_level1_series, t0_s, period_s, n_samples, with_time)
+
+    def online_level1_series(self, t0_s: int, period_s: int, n_samples: int, with_time: bool = False):
+        """level1_series of the current online DELAY session as its last run() left it
+        (mcs_online_level1_series), under online_state_series' rules: after a finite horizon every
+        sample lies below it and is final; after a drain any second is accepted."""
+        return self._level1(L.lib().mcs_online_level1_series, t0_s, period_s, n_samples, with_time)
+
+    def level1_at(self, cluster: int, t_s: int, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """ProvideJobs at one second (mcs_read_level1): the rows of Level1 of `cluster` after the Delay
+        iteration at t_s, in list order, as indices into the cluster's stream, and len(Level1).
+        cap (default: the whole list) bounds the rows returned; the length is the list's whatever
+        cap is."""
+        n = C.c_uint32()
+        if cap is None:
+            self._c(L.lib().mcs_read_level1(self._h, int(cluster), int(t_s), None, 0, C.byref(n)))
+            cap = n.value
+        rows = np.zeros(max(int(cap), 1), np.uint32)
+        self._c(L.lib().mcs_read_level1(self._h, int(cluster), int(t_s), L.ptr(rows, C.c_uint32), int(cap),
+                                        C.byref(n)))
+        return rows[:min(int(cap), n.value)], n.value
+
     def approve_trade(self, total_cores, total_memory, core_util, mem_util, cores, memory, time_s) -> np.ndarray:
         """mcs_approve_trade: Trader.ApproveTrade (trader.go:141-167) on the GPU for arrays of
         (responder totals + sample, contract) queries; returns 0/1 per query."""
@@ -608,4 +651,4 @@ def roofline_placements_per_s(peak_bytes_per_s: float = 8.0e12) -> float:
 
 __all__ = ["Engine", "GenParams", "JobStreams", "RunStats", "gen_cluster_host", "gen_streams_host",
            "scaled_lambda", "device_count", "CLUSTER_STATS_DTYPE", "DELAY_STATS_DTYPE", "CLUSTER_SAMPLE_DTYPE",
-           "WAIT_SAMPLE_DTYPE", "math"]
+           "WAIT_SAMPLE_DTYPE", "LEVEL1_SAMPLE_DTYPE", "math"]
