@@ -434,12 +434,59 @@ int mcs_wait_time_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint
  * were appended behind a drain, until the next run.  MCS_E_INVALID: as mcs_cluster_state_series, a
  * non-NULL wait under FIFO, a sample at or past a finite horizon.  Each call rebuilds its scratch
  * (batch summaries, wait records) from the session: its cost grows with the history, and nothing is
- * kept that a later run, append, rewind or segment relayout could leave stale.  kernel_ms (may be
- * NULL) receives the summed device time of the launches. */
+ * kept that a later run, append, rewind or segment relayout could leave stale (a caller that follows
+ * a long session subscribes instead: mcs_stream_open, below).  kernel_ms (may be NULL) receives the
+ * summed device time of the launches. */
 int mcs_online_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                             mcs_cluster_sample* out, mcs_wait_sample* wait /* may be NULL */,
                             mcs_cluster_state* first /* may be NULL */, uint32_t n_clusters,
                             double* kernel_ms);
+
+/* ---- a cursor on the Start stream of an online session ---------------------------------------- */
+/* mcs_online_state_series keeps nothing between calls, so a live slice's telemetry costs what the
+ * session's whole history costs.  A stream is a subscription: it remembers where it is, hands out each
+ * decided sample once, and keeps on the device what no later horizon or append can change (DESIGN.md
+ * §14), so that a call's cost follows the slice and the jobs still alive.  One stream per engine. */
+typedef struct mcs_stream_stats {
+    uint32_t n_written;    /* samples per cluster this call wrote                                   */
+    uint32_t t_first;      /* second of sample 0 of this call (undefined when n_written == 0)       */
+    uint32_t t_next;       /* the stream's next sample second after this call                       */
+    uint32_t pending;      /* decided samples not yet taken after this call                         */
+    uint64_t rows_scanned; /* distinct rows whose results (node/start/finish) or wait record this
+                              call's per-job loops loaded: whole batches of 256, counted on the device
+                              from the batch flags and summaries, never estimated                    */
+    uint64_t rows_retired; /* rows lying in retired batches after this call                         */
+    double kernel_ms;      /* HIP events on the engine stream, summed over the launches             */
+} mcs_stream_stats;
+
+/* Subscribes to the current online session (FIFO or DELAY without trading) at the cadence
+ * t0_s + k * period_s; with_wait != 0 adds the wait statistics (a DELAY session).  The stream may be
+ * opened mid-session with t0_s far below the horizon: the first mcs_stream_next then catches up over
+ * the history once.  MCS_E_STATE without an online session, after a run that failed, or when a stream
+ * is open; MCS_E_INVALID for period_s == 0 and for with_wait under FIFO. */
+int mcs_stream_open(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t with_wait);
+
+/* Let h be the horizon of the last successful finite mcs_run.  Writes the samples
+ * t_next + k * period_s < h, k < max_samples, to out[c * max_samples + k] (and to wait in the same
+ * shape: non-NULL exactly when the stream was opened with_wait) and advances t_next past them.  No
+ * sample to write is MCS_OK with n_written == 0.  n_clusters must equal mcs_num_clusters: the frontier
+ * is common to all clusters.  Every sample is, bit for bit, what mcs_online_state_series returns for
+ * that second on the same session at that moment, hence final (see there).
+ * mcs_run(MCS_TIME_NONE) does not move the frontier: after a drain the call still serves what is
+ * pending below the last finite horizon, then nothing (the tail of a finished session is
+ * mcs_online_state_series's).  The stream is closed by the first mcs_run after a drain, by mcs_rewind
+ * and any other restart of the session, by mcs_submit_jobs, mcs_generate_jobs and mcs_load_clusters, and
+ * by a run that failed; the call then returns MCS_E_STATE, mcs_last_error names the cause, and the
+ * caller reopens.  A segment relayout by mcs_append_jobs does not close it.  MCS_E_INVALID: out == NULL,
+ * max_samples == 0, n_clusters != mcs_num_clusters, wait not as the stream was opened.
+ * stats may be NULL. */
+int mcs_stream_next(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sample* out,
+                    mcs_wait_sample* wait /* NULL unless with_wait */, uint32_t n_clusters,
+                    mcs_stream_stats* stats /* may be NULL */);
+
+/* Ends the subscription and frees what it kept.  MCS_E_STATE when no stream was opened or the stream
+ * was closed already by this call. */
+int mcs_stream_close(mcs_engine* eng);
 
 /* ---- the Level1 list over time: what ProvideJobs hands the trader ---------------------------- */
 /* The other half of the ResourceChannel service (pkg/scheduler/trader_server.go): ProvideJobs (:69-94,

@@ -271,6 +271,7 @@ int mcs_load_clusters(mcs_engine* e, const uint32_t* cap_c, const uint32_t* cap_
         return fail(e, MCS_E_INVALID, "null node array");
 
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    mcs::stream_shut(e, "mcs_load_clusters");
     free_clusters(e);
     free_jobs(e);
     mcs::trade_free(e);
@@ -407,6 +408,7 @@ int mcs_submit_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
             return fail(e, MCS_E_INVALID, "simulated clock could exceed 2^32-1 seconds");
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    mcs::stream_shut(e, "mcs_submit_jobs");
     if (int st = alloc_jobs(e, job_offsets, true)) return st;
     e->last_arr.swap(last);
     e->sum_dur.swap(sum);
@@ -426,6 +428,7 @@ int mcs_generate_jobs(mcs_engine* e, const mcs_gen_params* p, uint64_t jobs_per_
     std::vector<uint64_t> off(e->C + 1);
     for (uint32_t c = 0; c <= e->C; ++c) off[c] = (uint64_t)c * jobs_per_cluster;
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    mcs::stream_shut(e, "mcs_generate_jobs");
     if (int st = alloc_jobs(e, off.data(), false)) return st;
     const uint32_t* mc = e->d_max_c;
     const uint32_t* mm = e->d_max_m;
@@ -527,7 +530,10 @@ int mcs_run(mcs_engine* e, uint32_t t_end_s, mcs_stats* stats) {
     if (e->online || t_end_s != MCS_TIME_NONE) { /* online mode (mcs_online.cpp) */
         if (e->cfg.borrow || e->cfg.trader)
             return fail(e, MCS_E_INVALID, "finite horizons are implemented for FIFO/DELAY without trading");
-        return mcs::online_run(e, t_end_s, stats);
+        mcs::stream_run_begin(e, t_end_s);
+        const int st = mcs::online_run(e, t_end_s, stats);
+        mcs::stream_run_end(e, t_end_s, st);
+        return st;
     }
     if (e->cfg.unchecked_horizon && !(e->cfg.borrow || e->cfg.trader)) {
         /* streams that skipped the host clock bound run through the online kernel variant, the one

@@ -70,6 +70,14 @@ int auto_pool(uint32_t max_n);
 // per-cluster clock bound of the streams in HBM: last arrival and sum of (dur + 1 + extra)
 int stream_bounds(mcs_engine* e, std::vector<uint32_t>& last, std::vector<uint64_t>& sum);
 uint32_t horizon_extra(const mcs_engine* e);  // max_wait_s under DELAY, else 0
+// the start-stream cursor (mcs_stream.cpp): mcs_stream_open / next / close
+void stream_shut(mcs_engine* e, const char* cause);  // closes an open stream; mcs_stream_next then names the cause
+void stream_run_begin(mcs_engine* e, uint32_t t_hor);  // before an online mcs_run: the first run after a drain closes
+void stream_run_end(mcs_engine* e, uint32_t t_hor, int status);  // moves the frontier, or closes after a failure
+// mcs_append_jobs relayouts the segments: the kept arrays follow (d_old_off / d_new_off: the segment
+// starts on the device, new_off the same on the host; d_job_cnt still holds the rows before the append)
+int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off,
+                    const std::vector<uint64_t>& new_off);
 
 // Lock-step tick loops: mcs_trade_stats.loop_form
 constexpr uint32_t kLoopGraph = 0;      // one engine, ticks replayed from a captured hipGraph
@@ -194,6 +202,22 @@ struct mcs_engine {
     bool on_series_ok = false;
     uint32_t on_series_hor = 0;        // that run's horizon (MCS_TIME_NONE: a drain)
     bool bounds_known = false;         // last_arr / sum_dur filled
+    bool on_run_failed = false;        // the session's last mcs_run returned an error
+    // the start-stream cursor of the session (mcs_stream.cpp): device arrays kept between calls
+    bool st_open = false;
+    std::string st_cause;              // what closed the last stream (empty: nothing did)
+    bool st_wait = false, st_drained = false;
+    uint32_t st_period = 0, st_next = 0, st_h = 0;  // cadence, next sample second, last finite horizon
+    uint64_t st_retired = 0;           // rows in retired batches
+    mcs::StreamCluster* d_st_cl = nullptr;
+    uint32_t* d_st_flags = nullptr;
+    uint2* d_st_summ = nullptr;
+    unsigned long long* d_st_bsum = nullptr;
+    uint4* d_st_rec = nullptr;
+    unsigned long long* d_st_tot = nullptr;
+    mcs_cluster_sample* d_st_out = nullptr;  // the call's samples on the device, st_out_cap per cluster
+    mcs_wait_sample* d_st_wout = nullptr;
+    uint64_t st_out_cap = 0;
 };
 
 inline bool mcs::is_dtrade(const mcs_engine* e) { return e->cfg.policy == MCS_POLICY_DELAY && e->cfg.trader; }

@@ -254,6 +254,57 @@ struct WaitArgs {
 hipError_t launch_wait_rec(const WaitArgs& a, hipStream_t s);     // rec alone: the clamp scan (mcs_level1.hip reads it)
 hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s);    // rec and ev: once per call
 hipError_t launch_wait_series(const WaitArgs& a, hipStream_t s);  // one chunk of samples
+hipError_t launch_wait_finish(const WaitArgs& a, hipStream_t s);  // wait_finish_kernel alone (mcs_stream.hip)
+
+// The start-stream cursor of an online session (mcs_stream.hip, mcs_stream_next): what
+// is kept per cluster between calls.  The unit is the batch of kSeriesBatch rows counted from the
+// cluster's first row; per batch the engine keeps a flag word, the summary pair of SeriesArgs::summ and
+// the batch's sum of s - a, all indexed as the summaries are (job_off[c] / kSeriesBatch + c), and per
+// row the wait record {h, m, s, a} of WaitArgs::rec (a stream with wait statistics only).
+struct StreamCluster {
+    long long d_carry;                // d of row p - 1 of wait_prep's recurrence (-1 before row 0)
+    unsigned long long a_base;        // sum of s - a over the rows of the retired batches (mod 2^64)
+    uint32_t p;                       // rows whose d is final (d below the horizon): a prefix
+    uint32_t first_live;              // every batch below this one is retired
+};
+constexpr uint32_t kStreamFinal = 1u;    // a full batch whose rows are all decided: summary, records and sum stay
+constexpr uint32_t kStreamRetired = 2u;  // final, and every finish below the frontier: no per-job loop reads it
+constexpr uint32_t kStreamLoaded = 4u;   // stream_prep_kernel read its rows in this call
+struct StreamArgs {
+    StateArgs s;               // the session's segments (job_cnt set); s.out and s.t are not used
+    StreamCluster* cl;         // [s.n_clusters]
+    uint32_t* flags;           // per batch
+    uint2* summ;               // per batch: SeriesArgs::summ
+    unsigned long long* bsum;  // per final batch: sum of s - a over its rows
+    uint4* rec;                // per row {h, m, s, arrival}; null without the wait statistics
+    mcs_wait_sample* wout;     // [s.n_clusters][n_samples] accumulators (stream_accum_kernel)
+    unsigned long long* tot;   // [0] rows this call loaded, [1] rows in retired batches
+    uint32_t hor;              // the last finite horizon: d below it is final
+    uint32_t max_wait;
+    uint32_t t0, period, n_samples;  // accum: the chunk; retire: the whole call
+    uint32_t chunk;            // retire: samples per chunk of the call's series launches
+    uint32_t frontier;         // retire: the stream's next sample second after this call
+};
+hipError_t launch_stream_prep(const StreamArgs& a, hipStream_t s);    // summaries, records, final flags
+hipError_t launch_stream_accum(const StreamArgs& a, hipStream_t s);   // the live batches into wout
+hipError_t launch_stream_retire(const StreamArgs& a, hipStream_t s);  // retire against the frontier, count
+// the kept arrays after a segment relayout: cluster c's batches and rows move from the old layout
+// (old_off) to the new one (s.job_off); s.job_cnt are the rows before the append
+struct StreamMoveArgs {
+    const uint64_t* old_off;
+    const uint64_t* new_off;
+    const uint32_t* job_cnt;
+    const uint32_t* flags_o;
+    uint32_t* flags_n;
+    const uint2* summ_o;
+    uint2* summ_n;
+    const unsigned long long* bsum_o;
+    unsigned long long* bsum_n;
+    const uint4* rec_o;  // null without the wait statistics
+    uint4* rec_n;
+    uint32_t n_clusters;
+};
+hipError_t launch_stream_move(const StreamMoveArgs& a, hipStream_t s);
 
 // The Level1 list over time (mcs_level1.hip): len(Level1), both contract sizes and the head row after
 // the Delay iteration at the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters,

@@ -177,6 +177,8 @@ int online_begin(mcs_engine* e) {
     }
     if (int st = alloc_state(e)) return st;
     if (int st = ensure_l1(e)) return st;
+    stream_shut(e, "a restart of the session");  // every row is undecided again: nothing kept holds
+    e->on_run_failed = false;
     e->on_cur = 0;
     HIPCHK(e, hipMemset(e->d_ost[0], 0, (e->C ? e->C : 1) * sizeof(OnlineState)));  // valid = 0: the spec
     // every row is undecided again.  The rows may hold an earlier pass's results (a batch run, or the
@@ -224,6 +226,7 @@ int stream_bounds(mcs_engine* e, std::vector<uint32_t>& last, std::vector<uint64
 }
 
 void online_free(mcs_engine* e) {
+    stream_shut(e, "the end of the online session");
     for (int k = 0; k < 2; ++k) {
         dfree(e->d_ost[k]);
         dfree(e->d_oimg[k]);
@@ -523,6 +526,7 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
             HIPCHK(e, hipGetLastError());
         }
         HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (int st = mcs::stream_relayout(e, e->d_job_off, d_noff, noff)) return st;  // an open stream's arrays follow
         dfree(e->d_jobs);
         dfree(e->d_out_node);
         dfree(e->d_out_start);
@@ -644,6 +648,7 @@ int mcs_rewind(mcs_engine* e) {
     if (int st = check_engine(e)) return st;
     if (!e->has_clusters || !e->has_jobs) return fail(e, MCS_E_STATE, "load clusters and jobs first");
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    mcs::stream_shut(e, "mcs_rewind");
     e->online = false;  // online_begin keeps the segments and counts
     return mcs::online_begin(e);
 }

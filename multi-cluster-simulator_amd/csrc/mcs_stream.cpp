@@ -1,0 +1,316 @@
+// mcs_stream.cpp — host side of the start-stream cursor (mcs_stream_open / next / close; kernels in
+// mcs_stream.hip).  Host code; compiled by hipcc.
+//
+// The engine owns the kept arrays: per batch of kSeriesBatch rows a flag word, the summary pair and the
+// sum of s - a (indexed as the series summaries are: by segment start, over segment capacity), per row
+// the wait record (a stream with wait statistics), per cluster a StreamCluster.  They are freed when
+// the stream closes and at destroy, and follow the segments through a relayout (stream_relayout).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "mcs_engine_impl.h"
+#include "mcs_internal.h"
+
+namespace mcs {
+namespace {
+
+void stream_free(mcs_engine* e) {
+    dfree(e->d_st_cl);
+    dfree(e->d_st_flags);
+    dfree(e->d_st_summ);
+    dfree(e->d_st_bsum);
+    dfree(e->d_st_rec);
+    dfree(e->d_st_tot);
+    dfree(e->d_st_out);
+    dfree(e->d_st_wout);
+    e->st_out_cap = 0;
+    e->st_open = false;
+}
+
+// the kept arrays for the segment layout `off` (capacity off[C]); the flags start at 0: nothing known
+int stream_alloc(mcs_engine* e, const std::vector<uint64_t>& off, uint32_t** flags, uint2** summ,
+                 unsigned long long** bsum, uint4** rec) {
+    const size_t nbat = series_summ_size(off[e->C], e->C);
+    HIPCHK(e, hipMalloc(flags, nbat * sizeof(uint32_t)));
+    HIPCHK(e, hipMemsetAsync(*flags, 0, nbat * sizeof(uint32_t), e->stream));
+    HIPCHK(e, hipMalloc(summ, nbat * sizeof(uint2)));
+    HIPCHK(e, hipMalloc(bsum, nbat * sizeof(unsigned long long)));
+    if (e->st_wait) HIPCHK(e, hipMalloc(rec, (size_t)(off[e->C] ? off[e->C] : 1) * sizeof(uint4)));
+    return MCS_OK;
+}
+
+}  // namespace
+
+void stream_shut(mcs_engine* e, const char* cause) {
+    if (!e->st_open) return;
+    (void)hipStreamSynchronize(e->stream);
+    stream_free(e);
+    e->st_cause = cause;
+}
+
+void stream_run_begin(mcs_engine* e, uint32_t t_hor) {
+    if (t_hor != MCS_TIME_NONE && t_hor < e->on_t_done) return;  // online_run refuses it: nothing runs
+    if (e->st_open && e->st_drained)
+        stream_shut(e, "an mcs_run after a drain (samples at or past the last finite horizon were not final)");
+}
+
+void stream_run_end(mcs_engine* e, uint32_t t_hor, int status) {
+    if (status == MCS_E_INVALID) return;  // a refused argument (a decreasing horizon): nothing ran
+    e->on_run_failed = status != MCS_OK;
+    if (!e->st_open) return;
+    if (status != MCS_OK)
+        stream_shut(e, "an mcs_run that failed");
+    else if (t_hor == MCS_TIME_NONE)
+        e->st_drained = true;  // the frontier stays at the last finite horizon
+    else
+        e->st_h = t_hor;
+}
+
+int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off,
+                    const std::vector<uint64_t>& new_off) {
+    if (!e->st_open) return MCS_OK;
+    uint32_t* flags = nullptr;
+    uint2* summ = nullptr;
+    unsigned long long* bsum = nullptr;
+    uint4* rec = nullptr;
+    int rc = stream_alloc(e, new_off, &flags, &summ, &bsum, &rec);
+    if (rc == MCS_OK) {
+        StreamMoveArgs m{};
+        m.old_off = d_old_off;
+        m.new_off = d_new_off;
+        m.job_cnt = e->d_job_cnt;
+        m.flags_o = e->d_st_flags;
+        m.flags_n = flags;
+        m.summ_o = e->d_st_summ;
+        m.summ_n = summ;
+        m.bsum_o = e->d_st_bsum;
+        m.bsum_n = bsum;
+        m.rec_o = e->d_st_rec;
+        m.rec_n = rec;
+        m.n_clusters = e->C;
+        hipError_t st = launch_stream_move(m, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        if (st != hipSuccess) rc = fail(e, MCS_E_HIP, std::string("stream relayout: ") + hipGetErrorString(st));
+    }
+    if (rc != MCS_OK) {
+        dfree(flags);
+        dfree(summ);
+        dfree(bsum);
+        dfree(rec);
+        const std::string msg = e->err;
+        stream_shut(e, "a segment relayout that failed");
+        e->err = msg;
+        return rc;
+    }
+    dfree(e->d_st_flags);
+    dfree(e->d_st_summ);
+    dfree(e->d_st_bsum);
+    dfree(e->d_st_rec);
+    e->d_st_flags = flags;
+    e->d_st_summ = summ;
+    e->d_st_bsum = bsum;
+    e->d_st_rec = rec;
+    return MCS_OK;
+}
+
+}  // namespace mcs
+
+extern "C" {
+
+int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    if (!e->online)
+        return fail(e, MCS_E_STATE, "mcs_stream_open subscribes to an online session (mcs_run with a horizon, "
+                                    "mcs_append_jobs; FIFO or DELAY without trading)");
+    if (e->st_open) return fail(e, MCS_E_STATE, "a stream is open already: one stream per engine (mcs_stream_close)");
+    if (e->on_run_failed)
+        return fail(e, MCS_E_STATE, "the session's last mcs_run failed: its rows are not a decided prefix (mcs_rewind)");
+    if (period_s == 0) return fail(e, MCS_E_INVALID, "period_s must be positive");
+    if (with_wait && e->cfg.policy != MCS_POLICY_DELAY)
+        return fail(e, MCS_E_INVALID, "the wait statistics need a DELAY session: only \"/delay\" feeds WaitTime");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->st_wait = with_wait != 0;
+    e->st_cause.clear();
+    int rc = mcs::stream_alloc(e, e->job_off, &e->d_st_flags, &e->d_st_summ, &e->d_st_bsum, &e->d_st_rec);
+    const size_t C = e->C ? e->C : 1;
+    hipError_t st = hipSuccess;
+    if (rc == MCS_OK) st = hipMalloc(&e->d_st_cl, C * sizeof(mcs::StreamCluster));
+    if (rc == MCS_OK && st == hipSuccess) st = hipMalloc(&e->d_st_tot, 2 * sizeof(unsigned long long));
+    if (rc == MCS_OK && st == hipSuccess) st = hipMemset(e->d_st_tot, 0, 2 * sizeof(unsigned long long));
+    if (rc == MCS_OK && st == hipSuccess) {
+        std::vector<mcs::StreamCluster> cl(C, mcs::StreamCluster{-1, 0ull, 0u, 0u});
+        st = hipMemcpy(e->d_st_cl, cl.data(), C * sizeof(mcs::StreamCluster), hipMemcpyHostToDevice);
+    }
+    if (rc == MCS_OK && st == hipSuccess) st = hipStreamSynchronize(e->stream);
+    if (rc == MCS_OK && st != hipSuccess)
+        rc = fail(e, MCS_E_HIP, std::string("mcs_stream_open: ") + hipGetErrorString(st));
+    if (rc != MCS_OK) {
+        mcs::stream_free(e);
+        return rc;
+    }
+    e->st_open = true;
+    e->st_period = period_s;
+    e->st_next = t0_s;
+    e->st_h = e->has_run ? e->on_t_hor : 0u;  // the last finite horizon of the session (0: none yet)
+    e->st_drained = e->has_run && e->on_series_hor == MCS_TIME_NONE;  // the last run was a drain
+    e->st_retired = 0;
+    return MCS_OK;
+}
+
+int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
+                    uint32_t n_clusters, mcs_stream_stats* stats) {
+    if (int st = check_engine(e)) return st;
+    if (stats) *stats = mcs_stream_stats{};
+    if (!e->st_open) {
+        if (e->st_cause.empty()) return fail(e, MCS_E_STATE, "no stream is open (mcs_stream_open)");
+        return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_stream_open)");
+    }
+    if (n_clusters != e->C)
+        return fail(e, MCS_E_INVALID, "n_clusters must equal mcs_num_clusters: the frontier is common to all clusters");
+    if (!out || max_samples == 0) return fail(e, MCS_E_INVALID, "bad output");
+    if ((wait != nullptr) != e->st_wait)
+        return fail(e, MCS_E_INVALID, "wait must be given exactly when the stream was opened with_wait");
+    const uint32_t period = e->st_period, t0 = e->st_next, h = e->st_h;
+    const uint64_t decided = t0 < h ? ((uint64_t)(h - t0) + period - 1) / period : 0ull;  // samples below h
+    const uint32_t n = (uint32_t)std::min<uint64_t>(decided, max_samples);
+    // the next sample second; past the uint32 range no second is ever decided: the stream rests there
+    const uint32_t t_after = (uint32_t)std::min<uint64_t>(t0 + (uint64_t)n * period, 0xFFFFFFFFull);
+    if (stats) {
+        stats->n_written = n;
+        stats->t_first = t0;
+        stats->t_next = t_after;
+        stats->pending = (uint32_t)std::min<uint64_t>(decided - n, 0xFFFFFFFFull);
+        stats->rows_retired = e->st_retired;
+    }
+    if (n == 0 || n_clusters == 0) {
+        e->st_next = t_after;
+        return MCS_OK;
+    }
+    if (e->st_wait)
+        for (uint32_t c = 0; c < e->C; ++c)  // job indices within a cluster are 32-bit on the device
+            if (e->job_cnt[c] > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
+    if (int st = mcs::ensure_job_records(e)) return st;
+    // samples per launch: the device buffers stay within 256 MiB (MCS_SERIES_CHUNK overrides the count)
+    uint64_t chunk = (256ull << 20) / ((sizeof(mcs_cluster_sample) + sizeof(mcs_wait_sample)) * (uint64_t)n_clusters);
+    if (const char* env = getenv("MCS_SERIES_CHUNK"))
+        if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n) chunk = n;
+    if (e->st_out_cap < chunk) {
+        dfree(e->d_st_out);
+        dfree(e->d_st_wout);
+        e->st_out_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(chunk, 16);
+        HIPCHK(e, hipMalloc(&e->d_st_out, (size_t)n_clusters * cap * sizeof(mcs_cluster_sample)));
+        if (e->st_wait) HIPCHK(e, hipMalloc(&e->d_st_wout, (size_t)n_clusters * cap * sizeof(mcs_wait_sample)));
+        e->st_out_cap = cap;
+    }
+    mcs::StreamArgs a{};
+    a.s.node_off = e->d_node_off;
+    a.s.cap = e->d_cap;
+    a.s.free0 = e->d_free0;
+    a.s.jobs = e->d_jobs;
+    a.s.job_off = e->d_job_off;
+    a.s.out_node = e->d_out_node;
+    a.s.out_start = e->d_out_start;
+    a.s.out_finish = e->d_out_finish;
+    a.s.n_clusters = n_clusters;
+    a.s.job_cnt = e->d_job_cnt;
+    a.cl = e->d_st_cl;
+    a.flags = e->d_st_flags;
+    a.summ = e->d_st_summ;
+    a.bsum = e->d_st_bsum;
+    a.rec = e->d_st_rec;
+    a.wout = e->d_st_wout;
+    a.tot = e->d_st_tot;
+    a.hor = h;
+    a.max_wait = e->cfg.max_wait_s;
+    a.period = period;
+    a.chunk = (uint32_t)chunk;
+    a.frontier = t_after;
+    mcs::SeriesArgs sa{};
+    sa.s = a.s;
+    sa.summ = e->d_st_summ;
+    sa.out = e->d_st_out;
+    sa.period = period;
+    sa.magic = period > 1 ? ~0ull / period + 1ull : 0ull;
+    mcs::WaitArgs wa{};
+    wa.jobs = e->d_jobs;
+    wa.job_off = e->d_job_off;
+    wa.job_cnt = e->d_job_cnt;
+    wa.out_node = e->d_out_node;
+    wa.out_start = e->d_out_start;
+    wa.rec = e->d_st_rec;
+    wa.out = e->d_st_wout;
+    wa.max_wait = e->cfg.max_wait_s;
+    wa.period = period;
+    wa.n_clusters = n_clusters;
+    double total_ms = 0.0;
+    unsigned long long tot[2] = {0ull, 0ull};
+    hipError_t st = hipMemsetAsync(e->d_st_tot, 0, sizeof(unsigned long long), e->stream);  // [0]: this call's rows
+    for (uint64_t k0 = 0; st == hipSuccess && k0 < n; k0 += chunk) {
+        const uint32_t nk = (uint32_t)(n - k0 < chunk ? n - k0 : chunk);
+        const bool last = k0 + nk == n;
+        a.t0 = sa.t0 = wa.t0 = (uint32_t)(t0 + k0 * period);
+        a.n_samples = sa.n_samples = wa.n_samples = nk;
+        st = hipEventRecord(e->ev0, e->stream);
+        if (st == hipSuccess && k0 == 0) st = mcs::launch_stream_prep(a, e->stream);
+        if (st == hipSuccess) st = mcs::launch_state_series(sa, e->max_n ? e->max_n : 1, e->stream);
+        if (st == hipSuccess && e->st_wait) {
+            st = hipMemsetAsync(e->d_st_wout, 0, (size_t)n_clusters * nk * sizeof(mcs_wait_sample), e->stream);
+            if (st == hipSuccess) st = mcs::launch_stream_accum(a, e->stream);
+            if (st == hipSuccess) st = mcs::launch_wait_finish(wa, e->stream);
+        }
+        if (st == hipSuccess && last) {  // the whole call's samples against the new frontier
+            a.t0 = t0;
+            a.n_samples = n;
+            st = mcs::launch_stream_retire(a, e->stream);
+        }
+        if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
+        float ms = 0.0f;
+        if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
+        total_ms += ms;
+        if (st == hipSuccess)  // the chunk's columns of every cluster's row
+            st = hipMemcpy2D(out + k0, (size_t)max_samples * sizeof(mcs_cluster_sample), e->d_st_out,
+                             (size_t)nk * sizeof(mcs_cluster_sample), (size_t)nk * sizeof(mcs_cluster_sample),
+                             n_clusters, hipMemcpyDeviceToHost);
+        if (st == hipSuccess && e->st_wait)
+            st = hipMemcpy2D(wait + k0, (size_t)max_samples * sizeof(mcs_wait_sample), e->d_st_wout,
+                             (size_t)nk * sizeof(mcs_wait_sample), (size_t)nk * sizeof(mcs_wait_sample), n_clusters,
+                             hipMemcpyDeviceToHost);
+    }
+    if (st == hipSuccess) st = hipMemcpy(tot, e->d_st_tot, sizeof(tot), hipMemcpyDeviceToHost);
+    if (st != hipSuccess) {
+        const int rc = fail(e, MCS_E_HIP, std::string("mcs_stream_next: ") + hipGetErrorString(st));
+        const std::string msg = e->err;
+        mcs::stream_shut(e, "a device error in mcs_stream_next");
+        e->err = msg;
+        return rc;
+    }
+    e->st_next = a.frontier;
+    e->st_retired = tot[1];
+    if (stats) {
+        stats->rows_scanned = tot[0];
+        stats->rows_retired = tot[1];
+        stats->kernel_ms = total_ms;
+    }
+    return MCS_OK;
+}
+
+int mcs_stream_close(mcs_engine* e) {
+    if (int st = check_engine(e)) return st;
+    if (!e->st_open) {
+        if (e->st_cause.empty()) return fail(e, MCS_E_STATE, "no stream is open");
+        e->st_cause.clear();  // closed by the engine already: acknowledged
+        return MCS_OK;
+    }
+    mcs::stream_shut(e, "mcs_stream_close");
+    e->st_cause.clear();
+    return MCS_OK;
+}
+
+}  // extern "C"

@@ -36,6 +36,7 @@
 // Each kernel has a SEG instantiation for an online session (mcs_online_state_series): J is then the
 // segment's job_cnt[c], not the distance to the next segment.
 #include "mcs_internal.h"
+#include "mcs_wait_dev.h"
 #include "mcs_wave.h"
 
 namespace mcs {
@@ -43,29 +44,8 @@ namespace mcs {
 namespace {
 
 constexpr int kWaitThreads = 256;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr long long kInf = 1ll << 60;  // s of a job that is never placed; beyond every a + W + J
-
-// x -> max(lo, min(hi, x + c)), lo <= hi
-struct Clamp {
-    long long lo, hi;
-    uint32_t c;
-};
-
-__device__ __forceinline__ long long clamp_apply(const Clamp& e, long long x) {
-    const long long y = x + (long long)e.c;
-    const long long z = y < e.hi ? y : e.hi;
-    return z > e.lo ? z : e.lo;
-}
-
-// `first`, then `second`: the bounds of `first`, shifted, clamped by `second`
-__device__ __forceinline__ Clamp clamp_then(const Clamp& first, const Clamp& second) {
-    Clamp r;
-    r.lo = clamp_apply(second, first.lo);
-    r.hi = clamp_apply(second, first.hi);
-    r.c = first.c + second.c;
-    return r;
-}
+constexpr uint32_t kNone = kWaitNone;
+constexpr long long kInf = kWaitInf;  // s of a job that is never placed (mcs_wait_dev.h)
 
 // The rows of cluster c.  SEG: the first job_cnt[c] rows of the segment at job_off[c] (an online
 // session, mcs_online_state_series); rec and ev are addressed by the same segment starts.  A job no
@@ -79,14 +59,12 @@ __device__ __forceinline__ uint32_t wait_rows(const WaitArgs& a, uint32_t c) {
         return (uint32_t)(a.job_off[c + 1] - a.job_off[c]);
 }
 
-__device__ __forceinline__ uint32_t sat32(long long x) { return x >= (long long)kNone ? kNone : (uint32_t)x; }
-
 template <bool SEG>
 __global__ __launch_bounds__(kWaitThreads) void wait_prep_kernel(WaitArgs a) {
     __shared__ Clamp wave_tot[kWaitThreads / kWave];
     __shared__ long long carry_s;
     const uint32_t c = blockIdx.x;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint64_t j0 = a.job_off[c];
     const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ jobs = a.jobs + j0;
@@ -109,22 +87,8 @@ __global__ __launch_bounds__(kWaitThreads) void wait_prep_kernel(WaitArgs a) {
             e.lo = arr + W < s ? arr + W : s;
             e.c = 1u;
         }
-        Clamp inc = e;  // inclusive scan over the wave
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            Clamp p;
-            p.lo = __shfl_up(inc.lo, o);
-            p.hi = __shfl_up(inc.hi, o);
-            p.c = __shfl_up(inc.c, o);
-            if (lane >= (uint32_t)o) inc = clamp_then(p, inc);
-        }
-        if (lane == 63u) wave_tot[wave] = inc;
-        __syncthreads();
-        long long x = carry;  // d of the job before this wave's first
-        for (uint32_t w = 0; w < wave; ++w) x = clamp_apply(wave_tot[w], x);
-        const long long d = clamp_apply(inc, x);
-        long long dprev = __shfl_up(d, 1);
-        if (lane == 0u) dprev = x;
+        long long dprev;
+        const long long d = clamp_scan_round(e, carry, wave_tot, dprev);
         if (live) {
             const long long h = arr > dprev + 1 ? arr : dprev + 1;
             const long long m = h > arr + W ? h : arr + W;
@@ -146,52 +110,8 @@ __global__ __launch_bounds__(kWaitThreads) void wait_skip_kernel(WaitArgs a) {
     for (uint64_t base = 0; base < J; base += kWaitThreads) {
         if (base + threadIdx.x >= J) continue;
         const uint32_t P = (uint32_t)(base + threadIdx.x);
-        uint2 res = make_uint2(kNone, 0u);
-        const uint4 rp = rec[P];
-        const uint32_t u = rp.z;
-        if (u != kNone && u > rp.y) {  // placed by the Level1 pass at u
-            // the entry behind P in Level1 at u: moved before u, not started before u; every job
-            // from the first with h >= u on has not reached the head yet
-            uint32_t k = kNone, mk = 0u;
-            for (uint32_t q = P + 1u; q < J; ++q) {
-                const uint4 r = rec[q];
-                if (r.x >= u) break;
-                if (r.y < u && r.z >= u) {
-                    k = q;
-                    mk = r.y;
-                    break;
-                }
-            }
-            if (k != kNone) {
-                // k was also stepped over at u - r iff it was in Level1 then (m_k < u - r) and an
-                // entry between the placement that skipped it at u - r + 1 and k started at u - r:
-                // the last such entry stood right before k
-                uint32_t r = 1u, lo = P;
-                while (r <= u) {
-                    const uint32_t tg = u - r;
-                    if (mk >= tg) break;
-                    uint32_t f = kNone;
-                    for (uint32_t q = k - 1u; q > lo; --q) {
-                        const uint4 x = rec[q];
-                        if (x.z == tg && tg > x.y) {
-                            f = q;
-                            break;
-                        }
-                    }
-                    if (f == kNone) break;
-                    ++r;
-                    lo = f;
-                }
-                res = make_uint2(k, r);
-            }
-        }
-        ev[P] = res;
+        ev[P] = wait_skip_of(rec, P, J);
     }
-}
-
-// a sample row as accumulators: [0] skip (pointwise), [1] A and [2] B (differences along the samples)
-__device__ __forceinline__ unsigned long long* acc_of(mcs_wait_sample* s) {
-    return reinterpret_cast<unsigned long long*>(s);
 }
 
 template <bool SEG>
@@ -201,53 +121,17 @@ __global__ __launch_bounds__(kWaitThreads) void wait_accum_kernel(WaitArgs a) {
     const uint32_t J = wait_rows<SEG>(a, c);
     const uint4* __restrict__ rec = a.rec + j0;
     const uint2* __restrict__ ev = a.ev + j0;
-    const uint32_t n = a.n_samples, period = a.period, t_first = a.t0;
-    mcs_wait_sample* const row = a.out + (size_t)c * n;
-    // index of the first sample at or after x, n when there is none
-    auto kt = [&](uint32_t x) -> uint32_t {
-        if (x <= t_first) return 0u;
-        const uint32_t q = (x - t_first - 1u) / period;
-        return q >= n ? n : q + 1u;
-    };
-    // every job before the chunk lands on sample 0: those differences are summed in registers and
-    // leave with one atomic per wave
-    unsigned long long pre_a = 0, pre_b = 0;
-    auto add = [&](uint32_t k, unsigned long long da, unsigned long long db) {
-        if (k == 0u) {
-            pre_a += da;
-            pre_b += db;
-        } else {
-            atomicAdd(acc_of(row + k) + 1, da);
-            if (db) atomicAdd(acc_of(row + k) + 2, db);
-        }
-    };
+    WaitAcc acc;
+    acc.n = a.n_samples;
+    acc.period = a.period;
+    acc.t_first = a.t0;
+    acc.row = a.out + (size_t)c * a.n_samples;
     for (uint64_t base = 0; base < J; base += kWaitThreads) {
         if (base + threadIdx.x >= J) continue;
         const uint32_t i = (uint32_t)(base + threadIdx.x);
-        const uint4 r = rec[i];  // {h, m, s, a}
-        const uint32_t kh = kt(r.x);
-        if (kh >= n) continue;  // h <= s: neither falls on a sample
-        const uint32_t ks = r.z != kNone ? kt(r.z) : n;
-        if (ks == kh) {  // reaches the head and starts within one sample: s - a for good
-            add(kh, (unsigned long long)r.z - (unsigned long long)r.w, 0ull);
-        } else {
-            add(kh, 0ull - (unsigned long long)r.w, 1ull);
-            if (ks < n) add(ks, (unsigned long long)r.z, ~0ull);
-        }
-        if (r.z != kNone && r.z > r.y && r.z >= t_first) {  // a Level1 placement: its skip at u = s
-            const uint2 e = ev[i];
-            const uint32_t y = r.z - t_first, q = y / period;
-            if (e.x != kNone && q < n && q * period == y) atomicAdd(acc_of(row + q), (unsigned long long)e.y);
-        }
+        acc.job(rec[i], [&]() { return ev[i]; });  // {h, m, s, a}
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        pre_a += __shfl_xor(pre_a, o);
-        pre_b += __shfl_xor(pre_b, o);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-        if (pre_a) atomicAdd(acc_of(row) + 1, pre_a);
-        if (pre_b) atomicAdd(acc_of(row) + 2, pre_b);
-    }
+    acc.flush();
 }
 
 template <bool SEG>
@@ -334,6 +218,14 @@ hipError_t launch_wait_prep(const WaitArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(wait_skip_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     else
         hipLaunchKernelGGL(wait_skip_kernel<false>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// the last step alone, over accumulators the caller filled (mcs_stream.hip): an online session's segments
+hipError_t launch_wait_finish(const WaitArgs& a, hipStream_t s) {
+    if (a.n_clusters == 0 || a.n_samples == 0) return hipSuccess;
+    if (!a.job_cnt) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wait_finish_kernel<true>, dim3(a.n_clusters), dim3(kWaitThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -542,6 +542,47 @@ class Engine:
             first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
         return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
 
+    def stream_open(self, t0_s: int, period_s: int, with_wait: Optional[bool] = None):
+        """mcs_stream_open: subscribe to the current online session at the cadence t0_s + k * period_s.
+        with_wait None: the wait statistics under DELAY, none under FIFO.  One stream per engine; it
+        may be opened mid-session, and the first stream_next then catches up over the history once."""
+        for v in (t0_s, period_s):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s and period_s are uint32")
+        if with_wait is None:
+            with_wait = self.policy == "DELAY"
+        self._c(L.lib().mcs_stream_open(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
+        self._stream_wait = bool(with_wait)
+
+    def stream_next(self, max_samples: int):
+        """mcs_stream_next: the decided samples the stream has not handed out yet, at most
+        max_samples of them: every second t_next + k * period_s below the last finite horizon, each
+        bit for bit what online_state_series returns for it.  Returns (samples, wait, stats):
+        (num_clusters, n) of CLUSTER_SAMPLE_DTYPE, the same shape of WAIT_SAMPLE_DTYPE (None for a
+        stream without wait statistics) and the mcs_stream_stats fields as a dict (n may be 0).
+        The cost follows the slice and the jobs still alive, not the session's age.  MCSError
+        (MCS_E_STATE) once the engine closed the stream: the message names the cause; reopen."""
+        if not 0 < int(max_samples) <= 0xFFFFFFFF:
+            raise L.MCSError(L.MCS_E_INVALID, "max_samples is a positive uint32")
+        n = self.num_clusters
+        m = int(max_samples)
+        with_wait = getattr(self, "_stream_wait", False)
+        # a cluster's row has max_samples columns, of which the first n_written are filled
+        samples = np.zeros((n, m), CLUSTER_SAMPLE_DTYPE)
+        wait = np.zeros((n, m), WAIT_SAMPLE_DTYPE) if with_wait else None
+        st = L.mcs_stream_stats()
+        self._c(L.lib().mcs_stream_next(
+            self._h, m, samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None, n, C.byref(st)))
+        k = int(st.n_written)
+        stats = {f: getattr(st, f) for f, _ in L.mcs_stream_stats._fields_}
+        return (np.ascontiguousarray(samples[:, :k]), np.ascontiguousarray(wait[:, :k]) if with_wait else None,
+                stats)
+
+    def stream_close(self):
+        """mcs_stream_close: end the subscription and free what it kept on the device."""
+        self._c(L.lib().mcs_stream_close(self._h))
+
     def _level1(self, fn, t0_s, period_s, n_samples, with_time):
         for v in (t0_s, period_s, n_samples):
             if not 0 <= int(v) <= 0xFFFFFFFF:
