@@ -241,7 +241,13 @@ int mcs_read_jobs(mcs_engine* eng, uint32_t* arrival_s, uint32_t* dur_s, uint32_
  * a run into horizons, with the jobs appended between them, gives bit-for-bit the placements of
  * the batch run over all the jobs.  Between horizons the placements of undecided jobs read
  * MCS_NODE_UNPLACED / MCS_TIME_NONE; the cluster and DELAY statistics are final after a drain.
- * Returns MCS_E_RANGE (results readable) when a cluster's clock leaves the uint32 range. */
+ * Returns MCS_E_RANGE (results readable) when a cluster's clock leaves the uint32 range.
+ *
+ * With MCS_POLICY_DELAY and cfg.trader on one engine the session is a trading session (mcs_trade.h,
+ * "trading sessions"): mcs_run(t_end_s) executes every lock-step tick T < t_end_s
+ * of the trading system, and does not stop at "every job so far decided" (samples and trader rounds go
+ * on); a horizon above t_max_s + 1 is MCS_E_INVALID.  FIFO trading (cfg.borrow, or cfg.trader under
+ * MCS_POLICY_FIFO) has no online mode: a finite t_end_s is MCS_E_INVALID there. */
 int mcs_run(mcs_engine* eng, uint32_t t_end_s, mcs_stats* stats);
 
 /* Online mode: append jobs to the clusters' streams (the "/" or "/delay" handler appending to the
@@ -250,7 +256,11 @@ int mcs_run(mcs_engine* eng, uint32_t t_end_s, mcs_stats* stats);
  * >= the last finite horizon run, and >= the cluster's own clock after the last drain (a cluster
  * whose drain ended earlier accepts earlier arrivals than one that ran longer).  Their ids continue the cluster's stream (dense order of
  * mcs_read_placements: per cluster, submitted then appended jobs in order).  Starts an online
- * session (state at t = 0) if none is active.  Not available with borrow/trader. */
+ * session (state at t = 0) if none is active.  In a trading session (MCS_POLICY_DELAY with cfg.trader,
+ * mcs_trade.h) the lock-step clock is common to all clusters: each arrival must also lie above the
+ * last executed tick, so after a drain that ended at tick T_d the floor is T_d + 1 for every cluster.
+ * MCS_E_STATE with FIFO trading (cfg.borrow, or cfg.trader under MCS_POLICY_FIFO), and for DELAY
+ * trading on a sharded engine or one with a communicator. */
 int mcs_append_jobs(mcs_engine* eng, const uint32_t* arrival_s, const uint32_t* dur_s,
                     const uint32_t* cores, const uint32_t* mem, const uint64_t* job_offsets);
 

@@ -211,6 +211,56 @@ int mcs_dtrade_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, u
                             mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
                             uint32_t n_clusters, double* kernel_ms);
 
+/* ---- trading sessions: online mode of a DELAY trading system ---------------------- */
+/* With MCS_POLICY_DELAY, cfg.trader = 1 and cfg.borrow = 0 on one engine (rank 0 of world 1, no
+ * communicator) the online calls of mcs.h drive the lock-step system live, as the reference deploys it
+ * (scheduler.go:116, pkg/client/server.go:53): the lock-step state stays in HBM between calls.
+ *   mcs_run(h), h finite    executes every lock-step tick T < h and stops.  "Every job so far decided"
+ *                           does not stop it: the samples keep coming every sample_period_s and the
+ *                           trader rounds keep falling due.  Horizons are non-decreasing and at most
+ *                           t_max_s + 1 (MCS_E_INVALID otherwise, nothing runs).
+ *   mcs_run(MCS_TIME_NONE)  a drain: until every job appended so far is decided; it stops after the tick
+ *                           that decides the last one (its samples and rounds included), where the batch
+ *                           run stops, or after tick t_max_s with MCS_FLAG_T_MAX; no tick when nothing is
+ *                           undecided.
+ *   mcs_append_jobs         per cluster, arrival-sorted: each arrival >= the cluster's last arrival, >=
+ *                           the last finite horizon and > the last executed tick (the clock is common to
+ *                           all clusters: after a drain that ended at tick T_d the floor is T_d + 1
+ *                           everywhere).  Starts a session at t = 0 over the submitted jobs if none is
+ *                           active.
+ *   mcs_rewind              restarts at t = 0 with every job so far.
+ * Between calls mcs_read_placements, mcs_read_cluster_stats, mcs_read_delay_stats and every reader of
+ * this header work on the session as its last mcs_run left it (undecided rows: MCS_NODE_UNPLACED /
+ * MCS_TIME_NONE); mcs_stats reports online = 1, t_horizon, placed = decided so far, pending = jobs -
+ * decided and the kernel_ms of the call.
+ * The guarantee: slicing never changes a decision.  After mcs_run(h) the readers return, bit for bit,
+ * the state of a batch run over all the jobs the session ever receives taken after that run's last tick
+ * below h (for as long as the batch run reaches that far); after the final drain they return the whole
+ * batch run, ticks and t_final included.  A horizon past the tick that decided the last job executes
+ * sample ticks and trader rounds the batch run never reaches: placements cannot change there, the logs
+ * and the trader state may grow with records whose t_s exceeds the batch run's t_final.
+ * A slot-pool or virtual-node overflow inside a slice escalates as the batch run does and replays the
+ * session from t = 0 up to the horizon (restarts counts it); when the capacity is exhausted the call
+ * returns MCS_E_CAPACITY and mcs_run returns MCS_E_STATE until mcs_rewind or a new submit.
+ * MCS_E_STATE: FIFO trading (borrow, or trader under FIFO), a sharded engine or one with a
+ * communicator, mcs_trade_begin during a session, and during a session every telemetry call
+ * (mcs_dtrade_state_series, mcs_level1_series, mcs_read_level1, mcs_online_state_series,
+ * mcs_online_level1_series, mcs_stream_open, mcs_cluster_states, mcs_cluster_state_series,
+ * mcs_wait_time_series). */
+typedef struct mcs_trade_session {
+    uint32_t t_horizon;      /* last finite horizon (0: none yet)                                      */
+    uint32_t t_last;         /* last executed tick                                                     */
+    uint32_t t_next;         /* the tick the session would execute next: the smaller of the tick the
+                                next-tick rule chose and the earliest arrival appended since            */
+    uint32_t ticks_last_run; /* ticks the last mcs_run executed (after a restart: those of the replay)  */
+    uint32_t ticks_total;    /* ticks since t = 0, the batch run's mcs_trade_stats.ticks                */
+    uint32_t restarts;       /* replays from t = 0 for a capacity escalation                            */
+    uint32_t drained;        /* 1: the last mcs_run was a drain                                         */
+    uint32_t failed;         /* 1: capacity exhausted (MCS_E_CAPACITY)                                  */
+} mcs_trade_session;
+/* MCS_E_STATE without a trading session. */
+int mcs_trade_session_info(mcs_engine* eng, mcs_trade_session* out);
+
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,
  * -1} (trader.go:47-52): a responder whose sample is {core_util, mem_util} and whose totals are

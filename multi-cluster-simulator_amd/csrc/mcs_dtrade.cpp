@@ -2,7 +2,9 @@
 // §11): device state, the tick loop (two kernels per tick; world 1: 256 ticks per captured
 // hipGraph, one host poll per replay; world > 1: an ncclAllGather of the exchange blocks between
 // the kernels, or the caller-driven phases), capacity escalation and the result readers of
-// mcs_trade.h.  Every decision is made by the gfx950 kernels of mcs_dtrade.hip; there is no CPU path.
+// mcs_trade.h; and trading sessions: the same system in online mode, resumed from
+// its control block slice by slice on the replayed kernels (dts_slice, dtrade_session_run).
+// Every decision is made by the gfx950 kernels of mcs_dtrade.hip; there is no CPU path.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -37,7 +39,8 @@ struct DtradeDev {
     mcs_foreign_rec* foreign = nullptr;
     unsigned char* xb = nullptr;  // world exchange blocks
     uint32_t* nv_all = nullptr;
-    DtCtl* h_ctl = nullptr;  // 3 entries: [0] the control block as last read; [1], [2] the graph loop's polls
+    DtCtl* h_ctl = nullptr;  // 4 entries: [0] the control block as last read; [1], [2] the graph loop's polls;
+                             // [3] a trading session's patch of the block (dts_slice)
     hipEvent_t pev[2] = {nullptr, nullptr};
     hipEvent_t tev[2] = {nullptr, nullptr};  // timing: the end of each pipelined replay
     double kernel_ms = 0.0;                  // device time of the last run (mcs_read_trade_stats)
@@ -92,7 +95,8 @@ int dtrade_alloc(mcs_engine* e) {
     d->tag[1] = 8u | (e->tr_agreed ? 4u : 0u);  // (8: the DELAY trading block)
     d->tag[2] = W;
     d->tag[3] = C;
-    const size_t nj = e->total_jobs ? e->total_jobs : 1;
+    // (a trading session: the segments' capacity, job_off holding the segment starts)
+    const size_t nj = std::max<uint64_t>(std::max<uint64_t>(e->total_jobs, e->job_off.empty() ? 0 : e->job_off[C]), 1);
     const uint64_t trade_cap = 1ull << 20;
     uint64_t foreign_cap = 1ull << 22;
     if (const char* env = getenv("MCS_DTRADE_FOREIGN_LOG_CAP"))  // tests: a Foreign log that overflows
@@ -115,7 +119,7 @@ int dtrade_alloc(mcs_engine* e) {
     HIPCHK(e, hipMalloc(&d->l1snap, (size_t)C * W * 8));
     HIPCHK(e, hipMalloc(&d->trades, trade_cap * sizeof(mcs_contract_rec)));
     HIPCHK(e, hipMalloc(&d->foreign, foreign_cap * sizeof(mcs_foreign_rec)));
-    HIPCHK(e, hipHostMalloc(&d->h_ctl, 3 * sizeof(DtCtl), hipHostMallocDefault));
+    HIPCHK(e, hipHostMalloc(&d->h_ctl, 4 * sizeof(DtCtl), hipHostMallocDefault));
     DtArgs& a = d->a;
     a.C = C;
     a.V = V;
@@ -160,6 +164,7 @@ int dtrade_alloc(mcs_engine* e) {
     a.l1snap = d->l1snap;
     a.trade_log = d->trades;
     a.foreign_log = d->foreign;
+    a.job_cnt = e->online ? e->d_job_cnt : nullptr;
     return MCS_OK;
 }
 
@@ -169,10 +174,10 @@ int dt_poll(mcs_engine* e) {
     return MCS_OK;
 }
 
-int dt_run_once(mcs_engine* e, double* kernel_ms) {
+// kDtGraphTicks ticks of the two kernels, captured once (released whenever a captured pointer changes)
+int dt_ensure_graph(mcs_engine* e) {
     DtradeDev* d = e->dtd;
-    hipError_t st = launch_dtrade_init(d->a, e->stream);
-    if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading init", st);
+    hipError_t st = hipSuccess;
     if (!d->graph) {
         hipGraph_t g = nullptr;
         HIPCHK(e, hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
@@ -189,15 +194,21 @@ int dt_run_once(mcs_engine* e, double* kernel_ms) {
         (void)hipGraphDestroy(g);
         if (st != hipSuccess) return dt_hip_fail(e, "hipGraphInstantiate", st);
     }
-    d->loop_form = kLoopGraph;
     for (hipEvent_t& ev : d->pev)
         if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     for (hipEvent_t& ev : d->tev)
         if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return MCS_OK;
+}
+
+// the replayed loop from the control block as it stands until it reports done (after dt_ensure_graph);
+// *end_ev_out: the end of the replay that finished the run
+int dt_graph_loop(mcs_engine* e, hipEvent_t* end_ev_out) {
+    DtradeDev* d = e->dtd;
+    d->loop_form = kLoopGraph;
     // the polls are pipelined: replay k + 1 is queued before replay k's control block is read, so
     // the GPU never idles through a host round trip (a run that ended in replay k runs one more
     // replay of finished ticks, whose kernels return at once and write nothing)
-    HIPCHK(e, hipEventRecord(e->ev0, e->stream));
     DtCtl* const hp = d->h_ctl + 1;
     hipEvent_t end_ev = nullptr;
     for (uint32_t k = 0;; ++k) {
@@ -214,6 +225,17 @@ int dt_run_once(mcs_engine* e, double* kernel_ms) {
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (int s = dt_poll(e)) return s;  // (the final control block into h_ctl[0])
+    *end_ev_out = end_ev;
+    return MCS_OK;
+}
+
+int dt_run_once(mcs_engine* e, double* kernel_ms) {
+    const hipError_t st = launch_dtrade_init(e->dtd->a, e->stream);
+    if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading init", st);
+    if (int s = dt_ensure_graph(e)) return s;
+    HIPCHK(e, hipEventRecord(e->ev0, e->stream));
+    hipEvent_t end_ev = nullptr;
+    if (int s = dt_graph_loop(e, &end_ev)) return s;
     float ms = 0.0f;
     HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, end_ev));
     *kernel_ms = ms;
@@ -355,7 +377,210 @@ int dt_clusters(mcs_engine* e, std::vector<DtCluster>& cl) {
     return MCS_OK;
 }
 
+// One slice of a trading session (DESIGN.md §14 "Trading sessions"): every tick T < t_hor from where
+// the session stands, or with t_hor = MCS_TIME_NONE every tick until each job held is decided.  The
+// lock-step state is in HBM as the last tick left it; the host only re-plans the control block: the
+// resume tick min(parked tick, earliest arrival appended since), the rounds due at it, the horizon.
+// Short slices run eagerly (8 ticks, then 32, each with one poll); longer ones through the graph.
+int dts_slice(mcs_engine* e, uint32_t t_hor, double* kernel_ms) {
+    DtradeDev* d = e->dtd;
+    *kernel_ms = 0.0;
+    e->ts_ticks_last = 0;
+    DtCtl& c = d->h_ctl[0];  // (the control block as the last slice, or the init kernel, left it)
+    const bool fresh = c.ticks == 0u && c.done == 0u;
+    if (!fresh && (c.flags & (MCS_FLAG_T_MAX | MCS_FLAG_OVERFLOW))) return MCS_OK;  // the clock stays at t_max_s
+    uint32_t t_res = 0u, any_due = 1u;
+    if (!fresh) {
+        t_res = std::min(e->ts_t_next, e->ts_pend_min);
+        any_due = t_res == e->ts_t_next ? e->ts_any_due : 0u;  // (below the parked tick no round is due)
+    }
+    if (t_hor != MCS_TIME_NONE) {
+        if (t_res >= t_hor) return MCS_OK;
+    } else {
+        std::vector<DtCluster> cl;
+        if (int s = dt_clusters(e, cl)) return s;
+        uint64_t decided = 0;
+        for (uint32_t k = 0; k < e->C; ++k) decided += cl[k].decided;
+        if (decided == e->total_jobs) return MCS_OK;  // a drain with nothing undecided executes no tick
+    }
+    const uint32_t ticks0 = c.ticks;
+    DtCtl& p = d->h_ctl[3];
+    p = c;
+    p.T = t_res;
+    p.done = 0u;
+    p.any_due = any_due;
+    p.pad0 = t_hor;
+    if (int s = dt_ensure_graph(e)) return s;  // (before the timed section: the capture is host work)
+    HIPCHK(e, hipEventRecord(e->ev0, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d->ctl, &p, sizeof(DtCtl), hipMemcpyHostToDevice, e->stream));
+    d->loop_form = kLoopGraph;
+    hipEvent_t end_ev = nullptr;
+    for (const uint32_t n : {8u, 32u}) {
+        for (uint32_t t = 0; t < n; ++t) {
+            const hipError_t st = launch_dtrade_tick(d->a, e->stream);
+            if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading tick", st);
+        }
+        HIPCHK(e, hipEventRecord(e->ev1, e->stream));
+        if (int s = dt_poll(e)) return s;
+        if (c.done) {
+            end_ev = e->ev1;
+            break;
+        }
+    }
+    if (!end_ev)
+        if (int s = dt_graph_loop(e, &end_ev)) return s;
+    float ms = 0.0f;
+    HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, end_ev));
+    *kernel_ms = ms;
+    e->ts_ticks_last = c.ticks - ticks0;
+    e->ts_ticks_total = c.ticks;
+    e->ts_t_last = c.T;
+    e->ts_pend_min = MCS_TIME_NONE;  // every arrival held was known to the last tick's next-tick rule
+    if (!(c.flags & (MCS_FLAG_T_MAX | MCS_FLAG_OVERFLOW))) {
+        e->ts_t_next = c.pad0;
+        e->ts_any_due = c.any_due;
+    }
+    return MCS_OK;
+}
+
 }  // namespace
+
+void dtrade_session_reset(mcs_engine* e) {
+    dtrade_free(e);  // (its arrays follow the segments: allocated again by the first run)
+    e->ts_begun = e->ts_failed = e->ts_drained = false;
+    e->ts_t_last = e->ts_t_next = 0u;
+    e->ts_any_due = 1u;
+    e->ts_pend_min = MCS_TIME_NONE;
+    e->ts_ticks_last = e->ts_ticks_total = e->ts_restarts = 0u;
+}
+
+int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
+    if (e->world != 1 || e->comm)
+        return fail(e, MCS_E_STATE, "a trading session runs on one engine that holds the whole system (rank 0 of "
+                                    "world 1, no communicator): sharded DELAY trading runs as a batch");
+    if (e->dtd && e->dtd->begun)
+        return fail(e, MCS_E_STATE, "a caller-driven lock-step run is in progress (mcs_trade_end first)");
+    if (!e->online)
+        if (int s = online_begin(e)) return s;
+    if (e->ts_failed)
+        return fail(e, MCS_E_STATE, "the trading session failed (capacity exhausted): mcs_rewind or submit again");
+    const uint32_t t_max = e->cfg.t_max_s ? e->cfg.t_max_s : 0xFFFFFFFEu;
+    if (t_hor != MCS_TIME_NONE && t_hor < e->on_t_hor)
+        return fail(e, MCS_E_INVALID, "horizons must be non-decreasing (last: " + std::to_string(e->on_t_hor) + ")");
+    if (t_hor != MCS_TIME_NONE && (uint64_t)t_hor > (uint64_t)t_max + 1u)
+        return fail(e, MCS_E_INVALID, "the horizon lies above t_max_s + 1 = " + std::to_string((uint64_t)t_max + 1u) +
+                                          ": cfg.t_max_s bounds the lock-step clock");
+    const auto w0 = std::chrono::steady_clock::now();
+    uint32_t escalations = 0;
+    double kms = 0.0;
+    for (;;) {
+        if (!e->ts_begun || !e->dtd) {  // from t = 0: the session's first run, or a replay after an escalation
+            if (!e->ts_begun) {  // (the capacities the last run of these inputs escalated to)
+                e->tr_slots = e->dt_learn_s;
+                e->dt_vnodes = e->dt_learn_v;
+            }
+            e->dt_ns = 0;
+            if (e->dtd) dtrade_free(e);
+            if (int s = dtrade_alloc(e)) return s;
+            const hipError_t st = launch_dtrade_init(e->dtd->a, e->stream);
+            if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading init", st);
+            if (int s = dt_poll(e)) return s;
+            e->ts_begun = true;
+            e->ts_t_last = e->ts_t_next = 0u;
+            e->ts_any_due = 1u;
+            e->ts_ticks_total = 0u;
+        }
+        double ms = 0.0;
+        if (int s = dts_slice(e, t_hor, &ms)) return s;
+        kms += ms;
+        const uint32_t flags = e->dtd->h_ctl->flags;
+        const uint32_t S = e->dtd->a.S, V = e->dtd->a.V;
+        const bool grow_s = (flags & MCS_FLAG_OVERFLOW) != 0, grow_v = (flags & MCS_FLAG_VNODE_OVERFLOW) != 0;
+        if (!grow_s && !grow_v) break;
+        if ((grow_s && (e->cfg.slot_pool || S >= kDtMaxSlots)) || (grow_v && V >= kDtMaxVnodes)) {
+            e->ts_failed = true;
+            return fail(e, MCS_E_CAPACITY, "DELAY trading capacity exhausted (slots or virtual nodes): the session "
+                                           "is failed until mcs_rewind or a new submit");
+        }
+        // as dtrade_run escalates; the session is replayed from t = 0 up to this horizon over every job
+        // held, which the slicing guarantee makes the state a session with these capacities would hold
+        const uint32_t ns = grow_s ? std::min<uint32_t>((S + S / 2u + 63u) / 64u * 64u, kDtMaxSlots) : S,
+                       nv = grow_v ? std::min<uint32_t>(V * 4u, kDtMaxVnodes) : V;
+        dtrade_free(e);
+        e->tr_slots = ns;
+        e->dt_vnodes = nv;
+        ++escalations;
+        ++e->ts_restarts;
+    }
+    e->dt_learn_s = e->cfg.slot_pool ? 0u : e->dtd->a.S;
+    e->dt_learn_v = e->dtd->a.V;
+    e->dtd->kernel_ms = kms;
+    e->has_run = true;
+    e->dtrade_run = true;
+    e->trade_run = false;
+    e->delay_run = true;
+    e->ts_drained = t_hor == MCS_TIME_NONE;
+    if (t_hor != MCS_TIME_NONE) e->on_t_hor = e->on_t_done = t_hor;
+    // the lock-step clock is common to all clusters: later arrivals lie above the last executed tick
+    if (e->ts_ticks_total) e->on_floor.assign(e->C, e->ts_t_last + 1u);
+    if (stats) {
+        std::vector<DtCluster> cl;
+        if (int s = dt_clusters(e, cl)) return s;
+        mcs_stats st{};
+        st.jobs = e->total_jobs;
+        for (uint32_t k = 0; k < e->C; ++k) {
+            st.placed += cl[k].decided;
+            st.waited += cl[k].moved;
+        }
+        st.pending = e->total_jobs - st.placed;
+        st.clusters = e->C;
+        st.escalations = escalations;
+        st.slot_pool = e->dtd->a.S / 64u;
+        st.kernel_ms = kms;
+        st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        st.t_horizon = t_hor;
+        st.online = 1u;
+        *stats = st;
+    }
+    return MCS_OK;
+}
+
+int dtrade_session_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off, size_t rows) {
+    DtradeDev* d = e->dtd;
+    if (!d) return MCS_OK;  // (no run yet: the first one allocates for the new segments)
+    unsigned long long* nw[3] = {nullptr, nullptr, nullptr};
+    for (auto& p : nw) HIPCHK(e, hipMalloc(&p, (rows ? rows : 1) * 8));
+    const unsigned long long* src[3] = {d->l1cm, d->l1jd, d->l1al};
+    const hipError_t st = launch_dtrade_relayout(d->cl, e->C, d_old_off, d_new_off, src, nw, e->stream);
+    if (st != hipSuccess) return dt_hip_fail(e, "Level1 relayout", st);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    dfree(d->l1cm);
+    dfree(d->l1jd);
+    dfree(d->l1al);
+    d->a.l1cm = d->l1cm = nw[0];
+    d->a.l1jd = d->l1jd = nw[1];
+    d->a.l1al = d->l1al = nw[2];
+    return MCS_OK;
+}
+
+void dtrade_session_rebind(mcs_engine* e) {
+    DtradeDev* d = e->dtd;
+    if (!d) return;
+    dtrade_release_graphs(e);  // (a captured graph holds the kernels' arguments by value)
+    d->a.jobs = e->d_jobs;
+    d->a.job_off = e->d_job_off;
+    d->a.out_node = e->d_out_node;
+    d->a.out_start = e->d_out_start;
+    d->a.out_finish = e->d_out_finish;
+    d->a.job_cnt = e->d_job_cnt;
+}
+
+int refuse_trade_session(mcs_engine* e, const char* call) {
+    if (!is_trade_session(e)) return MCS_OK;
+    return fail(e, MCS_E_STATE, std::string(call) + " is not available in a trading session (online mode with "
+                                    "MCS_POLICY_DELAY and cfg.trader): the telemetry calls read batch runs and "
+                                    "sessions without trading");
+}
 
 void dtrade_release_graphs(mcs_engine* e) {
     if (DtradeDev* d = e->dtd) {
@@ -405,6 +630,7 @@ int dtrade_run(mcs_engine* e, mcs_stats* stats) {
     if (e->world > 1 && !e->comm)
         return fail(e, MCS_E_STATE, "sharded DELAY trading run needs mcs_comm_init (or mcs_trade_phase)");
     const auto w0 = std::chrono::steady_clock::now();
+    if (e->dtd && e->dtd->a.job_cnt) dtrade_free(e);  // (a trading session's state: segments, not dense rows)
     // the capacities the last run of these inputs escalated to (reset when clusters, jobs or the
     // shard change): a re-run of the same system starts there instead of repeating the overflowed run
     e->tr_slots = e->dt_learn_s;
@@ -634,7 +860,7 @@ int dtrade_trade_stats(mcs_engine* e, mcs_trade_stats* out) {
     mcs_trade_stats s{};
     uint32_t flags = c.flags;
     for (uint32_t k = 0; k < e->C; ++k) {
-        const uint64_t J = e->job_off[k + 1] - e->job_off[k];
+        const uint64_t J = e->online ? e->job_cnt[k] : e->job_off[k + 1] - e->job_off[k];
         s.placed += cl[k].decided;
         s.waited += cl[k].moved;
         s.undecided += J - cl[k].decided;
@@ -678,6 +904,25 @@ int dtrade_read_vnode_counts(mcs_engine* e, uint32_t* out, uint32_t n) {
 }  // namespace mcs
 
 extern "C" {
+
+int mcs_trade_session_info(mcs_engine* e, mcs_trade_session* out) {
+    if (int st = check_engine(e)) return st;
+    if (!out) return fail(e, MCS_E_INVALID, "null output");
+    if (!mcs::is_trade_session(e))
+        return fail(e, MCS_E_STATE, "no trading session (online mode with MCS_POLICY_DELAY and cfg.trader: mcs_run "
+                                    "with a horizon, mcs_append_jobs, mcs_rewind)");
+    mcs_trade_session s{};
+    s.t_horizon = e->on_t_hor;
+    s.t_last = e->ts_t_last;
+    s.t_next = e->ts_ticks_total ? std::min(e->ts_t_next, e->ts_pend_min) : 0u;
+    s.ticks_last_run = e->ts_ticks_last;
+    s.ticks_total = e->ts_ticks_total;
+    s.restarts = e->ts_restarts;
+    s.drained = e->ts_drained ? 1u : 0u;
+    s.failed = e->ts_failed ? 1u : 0u;
+    *out = s;
+    return MCS_OK;
+}
 
 int mcs_read_contracts(mcs_engine* e, mcs_contract_rec* out, uint64_t cap, uint64_t* n) {
     if (int st = check_engine(e)) return st;
@@ -737,6 +982,7 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
                             mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
                             uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_dtrade_state_series")) return st;
     if (e->segmented)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from batch runs (not after mcs_append_jobs; "
                                     "in an online session: mcs_online_state_series)");

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(64) void dt_init_kernel(DtArgs a) {
     sm = dt_wave_sum_u32(sm);
     for (uint32_t s = lane; s < a.S; s += kWave) a.sfin[(size_t)c * a.S + s] = kEmpty;
     for (uint32_t i = lane; i < a.W; i += kWave) a.l1snap[(size_t)c * a.W + i] = 0ull;  // every node "grown"
-    const uint64_t j0 = a.job_off[c], j1 = a.job_off[c + 1];
+    const uint64_t j0 = a.job_off[c], j1 = j0 + (a.job_cnt ? dt_rows<true>(a, c, j0) : dt_rows<false>(a, c, j0));
     for (uint64_t j = j0 + lane; j < j1; j += kWave) {
         a.out_node[j] = MCS_NODE_UNPLACED;
         a.out_start[j] = MCS_TIME_NONE;
@@ -69,12 +69,15 @@ __global__ __launch_bounds__(64) void dt_init_kernel(DtArgs a) {
     if (c == 0 && lane == 0) {
         DtCtl z{};
         z.any_due = 1u;
+        z.pad0 = MCS_TIME_NONE;  // no horizon (a trading session patches its own in)
         *a.ctl = z;
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// Phase A: one Delay iteration of cluster c at tick T.
+// Phase A: one Delay iteration of cluster c at tick T.  SES: a trading session's instantiation (rows from
+// job_cnt; in dt_trader_kernel the next-tick rule with a horizon); a batch run's is the code as it was.
+template <bool SES>
 __global__ __launch_bounds__(64) void dt_step_kernel(DtArgs a) {
     __shared__ unsigned long long nodes[kDtMaxNodes + kDtMaxVnodes];
     __shared__ uint32_t sfin[kDtMaxSlots];
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(64) void dt_step_kernel(DtArgs a) {
     const uint32_t c = blockIdx.x, lane = threadIdx.x;
     const uint32_t n0 = a.node_off[c], N = a.node_off[c + 1] - n0;
     const uint64_t j0 = a.job_off[c];
-    const uint32_t J = (uint32_t)(a.job_off[c + 1] - j0);
+    const uint32_t J = dt_rows<SES>(a, c, j0);
     const uint4* __restrict__ jobs = a.jobs + j0;
     unsigned long long* __restrict__ l1cm = a.l1cm + j0;
     unsigned long long* __restrict__ l1jd = a.l1jd + j0;
@@ -180,6 +183,7 @@ __global__ __launch_bounds__(64) void dt_step_kernel(DtArgs a) {
 // runs it on the same gathered records and replicated trader state, so every decision is identical
 // on every rank; a rank applies the side effects on its own clusters (Foreign jobs, virtual nodes)
 // to its live state as well as to the snapshot the later rounds of this tick read.
+template <bool SES>
 __global__ __launch_bounds__(64) void dt_trader_kernel(DtArgs a) {
     __shared__ DtTrader trs[kDtMaxClusters];
     __shared__ uint32_t appr[kDtMaxClusters];
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(64) void dt_trader_kernel(DtArgs a) {
     const unsigned long long n_trades = k.n_trades, n_won = k.n_won, n_for = k.n_for;
     const uint32_t lflags = k.lflags;
 
-    const DtCtl nc = dt_next_ctl(a, lane, c0, trs, srec, lflags, n_trades, n_won, n_for);
+    const DtCtl nc = dt_next_ctl<SES>(a, lane, c0, trs, srec, lflags, n_trades, n_won, n_for);
     __syncthreads();
     for (uint32_t q = lane; q < Ct; q += kWave) {
         a.tr[q] = trs[q];
@@ -241,6 +245,7 @@ __global__ __launch_bounds__(64) void dt_trader_kernel(DtArgs a) {
         ctl->T = nc.T;
         ctl->done = nc.done;
         ctl->any_due = nc.any_due;
+        if constexpr (SES) ctl->pad0 = nc.pad0;
         ctl->ticks = nc.ticks;
         ctl->flags = nc.flags;
         ctl->n_trades = nc.n_trades;
@@ -254,6 +259,26 @@ __global__ __launch_bounds__(64) void dt_trader_kernel(DtArgs a) {
         g_dt_maxsum[8] += wall_clock64() - tr_t0;
         g_dt_maxsum[9] += 1ull;
 #endif
+    }
+}
+
+// A trading session whose segments grow (mcs_append_jobs): cluster c's Level1 list,
+// len(Level1) entries of each of its three arrays, from the old segment start to the new one.  The
+// jobs and the result rows move with the plain session's relayout; nothing else is indexed by job.
+__global__ __launch_bounds__(256) void dt_relayout_kernel(const DtCluster* cl, const uint64_t* off_o,
+                                                          const uint64_t* off_n, const unsigned long long* cm_o,
+                                                          unsigned long long* cm_n, const unsigned long long* jd_o,
+                                                          unsigned long long* jd_n, const unsigned long long* al_o,
+                                                          unsigned long long* al_n) {
+    const uint32_t c = blockIdx.y;
+    const uint64_t o = off_o[c], n = off_n[c];
+    // (never past either segment: len(Level1) <= the cluster's rows <= both capacities)
+    const uint64_t room = off_o[c + 1] - o < off_n[c + 1] - n ? off_o[c + 1] - o : off_n[c + 1] - n;
+    const uint32_t len = cl[c].l1n < room ? cl[c].l1n : (uint32_t)room;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < len; i += gridDim.x * 256u) {
+        cm_n[n + i] = cm_o[o + i];
+        jd_n[n + i] = jd_o[o + i];
+        al_n[n + i] = al_o[o + i];
     }
 }
 
@@ -281,16 +306,27 @@ hipError_t launch_dtrade_init(const DtArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_dtrade_relayout(const DtCluster* cl, uint32_t C, const uint64_t* off_old, const uint64_t* off_new,
+                                  const unsigned long long* const* src, unsigned long long* const* dst, hipStream_t s) {
+    if (C == 0) return hipSuccess;
+    hipLaunchKernelGGL(dt_relayout_kernel, dim3(8, C), dim3(256), 0, s, cl, off_old, off_new, src[0], dst[0], src[1],
+                       dst[1], src[2], dst[2]);
+    return hipGetLastError();
+}
+
 hipError_t launch_dtrade_step(const DtArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(dt_step_kernel, dim3(a.C), dim3(kWave), 0, s, a);
+    if (a.job_cnt) hipLaunchKernelGGL(dt_step_kernel<true>, dim3(a.C), dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL(dt_step_kernel<false>, dim3(a.C), dim3(kWave), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_dtrade_trader(const DtArgs& a, hipStream_t s) {
     const size_t lds = (size_t)a.Ct * sizeof(DtRec);
-    const hipError_t st = hipFuncSetAttribute((const void*)dt_trader_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const void* fn = a.job_cnt ? (const void*)dt_trader_kernel<true> : (const void*)dt_trader_kernel<false>;
+    const hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(dt_trader_kernel, dim3(1), dim3(kWave), lds, s, a);
+    if (a.job_cnt) hipLaunchKernelGGL(dt_trader_kernel<true>, dim3(1), dim3(kWave), lds, s, a);
+    else hipLaunchKernelGGL(dt_trader_kernel<false>, dim3(1), dim3(kWave), lds, s, a);
     return hipGetLastError();
 }
 

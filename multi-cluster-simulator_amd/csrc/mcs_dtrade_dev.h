@@ -77,6 +77,17 @@ __device__ __forceinline__ unsigned long long* dt_snap(const DtArgs& a, uint32_t
            (size_t)c * a.W;
 }
 
+// the job rows of local cluster c, whose segment starts at j0 = job_off[c]: the whole segment in a
+// batch run, its first job_cnt[c] rows in a trading session (segments with slack, as
+// rows_of / wait_rows read them for the SEG kernels)
+// SES: the session instantiation of the replayed kernels (a batch run's kernels never look at
+// job_cnt: their code is what it was)
+template <bool SES>
+__device__ __forceinline__ uint32_t dt_rows(const DtArgs& a, const uint32_t c, const uint64_t j0) {
+    if constexpr (SES) return a.job_cnt[c];
+    else return (uint32_t)(a.job_off[c + 1] - j0);
+}
+
 #ifdef MCS_STAMPS
 // the probe build's dt_step segment times (s_memrealtime, 100 MHz), summed over clusters and ticks:
 // 0 state in + LDS copies, 1 releases, 2 arrivals, 3 Level1 pass, 4 Level0 head, 5 copies out +
@@ -1007,7 +1018,16 @@ __device__ __forceinline__ DtCounts dt_rounds(const DtArgs& a, const uint32_t la
 }
 
 // the next tick: T+1 while any cluster has a queued job, else the next arrival, sample tick or
-// trader round (oracle/mcs_oracle_dtrade.c); the control block that follows tick T
+// trader round (oracle/mcs_oracle_dtrade.c); the control block that follows tick T.
+// HOR (the replayed kernels of a trading session; DESIGN.md §14 "Trading sessions"): the control block carries a horizon h
+// in pad0 (MCS_TIME_NONE: none), read from memory so that a captured graph sees a new one.  With a
+// horizon "every job decided" ends nothing (the Go loops go on sampling and trading), and a next tick
+// >= h parks the run: done = 2, T stays the last executed tick (what every reader reports) and pad0
+// takes the tick the rule chose, any_due the rounds due at it; the host resumes from those.  A run
+// that ends on "every job decided" (no horizon) parks the same way with done = 1, so that a session
+// can go on from a drain.  HOR = false is the rule as it was: the resident tick (mcs_dtrade_mw.hip) and
+// the replayed kernels of every run that is not a session (batch, RCCL, caller-driven).
+template <bool HOR>
 __device__ __forceinline__ DtCtl dt_next_ctl(const DtArgs& a, const uint32_t lane, const DtCtl& c0,
                                              const DtTrader* trs, const DtRec* srec, const uint32_t lflags,
                                              const unsigned long long n_trades, const unsigned long long n_won,
@@ -1032,17 +1052,39 @@ __device__ __forceinline__ DtCtl dt_next_ctl(const DtArgs& a, const uint32_t lan
     DtCtl n = c0;
     uint32_t flags = c0.flags | fl | lflags;
     uint32_t done = 0, Tn = T;
-    if (done_all || (flags & MCS_FLAG_OVERFLOW)) {
-        done = 1u;
-    } else if (T >= a.t_max) {
-        done = 1u;
-        flags |= MCS_FLAG_T_MAX;
+    if constexpr (HOR) {
+        const uint32_t hor = c0.pad0;
+        const uint32_t cand = (queued_any || nxt <= T + 1u) ? T + 1u : nxt;
+        bool park = false;
+        if (flags & MCS_FLAG_OVERFLOW) {
+            done = 1u;
+        } else if (hor == MCS_TIME_NONE && done_all) {
+            done = 1u;
+            park = true;
+        } else if (T >= a.t_max) {
+            done = 1u;
+            flags |= MCS_FLAG_T_MAX;
+        } else if (hor != MCS_TIME_NONE && cand >= hor) {
+            done = 2u;
+            park = true;
+        } else {
+            Tn = cand;
+        }
+        n.any_due = ndue <= (park ? cand : Tn) ? 1u : 0u;
+        if (park) n.pad0 = cand;
     } else {
-        Tn = (queued_any || nxt <= T + 1u) ? T + 1u : nxt;
+        if (done_all || (flags & MCS_FLAG_OVERFLOW)) {
+            done = 1u;
+        } else if (T >= a.t_max) {
+            done = 1u;
+            flags |= MCS_FLAG_T_MAX;
+        } else {
+            Tn = (queued_any || nxt <= T + 1u) ? T + 1u : nxt;
+        }
+        n.any_due = ndue <= Tn ? 1u : 0u;
     }
     n.T = Tn;
     n.done = done;
-    n.any_due = ndue <= Tn ? 1u : 0u;
     n.ticks = c0.ticks + 1u;
     n.flags = flags;
     n.n_trades = n_trades;

@@ -91,11 +91,16 @@ struct DtTrader {
 
 struct DtCtl {
     uint32_t T, done, ticks, flags;
-    uint32_t any_due, pad0;  // a trader round is due at T (phase A then sizes contracts)
+    uint32_t any_due, pad0;  // a trader round is due at T (phase A then sizes contracts); pad0: the
+                             // replayed kernels' horizon while a run goes on (MCS_TIME_NONE: none),
+                             // the tick the next-tick rule chose once it is parked (dt_next_ctl)
     unsigned long long n_trades, n_won, n_foreign;
 };
 
-struct DtArgs {
+// (DtArgsCore: the arguments of every tick form, and the resident tick's kernel parameter as it was;
+// DtArgs adds what only the replayed kernels read, so that the resident kernel's argument layout and
+// code stay what they were)
+struct DtArgsCore {
     uint32_t C, V, S;
     uint32_t base, Ct;   // global index of local cluster 0; clusters in the system (world * C)
     uint32_t NS, W;      // snapshot stride: physical nodes, physical + virtual
@@ -129,6 +134,9 @@ struct DtArgs {
     mcs_contract_rec* trade_log;
     mcs_foreign_rec* foreign_log;
 };
+struct DtArgs : DtArgsCore {
+    const uint32_t* job_cnt;  // a trading session: rows per cluster, job_off = segment starts (null: batch)
+};
 
 // The resident tick (mcs_dtrade_mw.hip, world 1): one wave per cluster, 4 per workgroup, and a
 // trader wave, exchanging granules through one XCD's L2; a launch runs up to `budget` ticks.
@@ -153,5 +161,9 @@ hipError_t launch_approve(const mcs_approve_query* q, uint32_t n, int32_t* out, 
 hipError_t launch_dtrade_step(const DtArgs& a, hipStream_t s);
 hipError_t launch_dtrade_trader(const DtArgs& a, hipStream_t s);
 hipError_t launch_dtrade_tick(const DtArgs& a, hipStream_t s);  // world 1: both
+// a trading session whose segments grow (mcs_append_jobs): the first len(Level1) entries of every
+// cluster's three Level1 arrays from the old segment starts to the new ones
+hipError_t launch_dtrade_relayout(const DtCluster* cl, uint32_t C, const uint64_t* off_old, const uint64_t* off_new,
+                                  const unsigned long long* const* src, unsigned long long* const* dst, hipStream_t s);
 
 }  // namespace mcs

@@ -529,7 +529,7 @@ __device__ __forceinline__ void dm_trader(const DtArgs& a, const DtResArgs& m, c
         n_won = k.n_won;
         n_for = k.n_for;
         const uint32_t lflags = k.lflags;
-        const DtCtl nc = dt_next_ctl(a, lane, c0, trs, srec, lflags, n_trades, n_won, n_for);
+        const DtCtl nc = dt_next_ctl<false>(a, lane, c0, trs, srec, lflags, n_trades, n_won, n_for);
         if (any_due) {  // X2: the rounds' side effects, every cluster's next round and the clock
             dt_wave_sync();
             const uint32_t on = lane < Ct ? opn[lane] : 0u;
@@ -575,7 +575,10 @@ __device__ __forceinline__ void dm_trader(const DtArgs& a, const DtResArgs& m, c
     if (lane == 0u) *a.ctl = c0;
 }
 
-__global__ __launch_bounds__(kDmThreads) void dt_mw_kernel(DtArgs a, DtResArgs m) {
+__global__ __launch_bounds__(kDmThreads) void dt_mw_kernel(DtArgsCore ac, DtResArgs m) {
+    DtArgs a;  // (batch runs only: no session's row counts)
+    static_cast<DtArgsCore&>(a) = ac;
+    a.job_cnt = nullptr;
     // the workers are blocks 0, 8, 16, ...: one XCD under the dispatcher's round-robin placement
     if (blockIdx.x % 8u != 0u) return;
     __shared__ unsigned long long s_nodes[kDmWaves][kDtResMaxNN];
@@ -674,7 +677,7 @@ hipError_t launch_dtrade_mw(const DtArgs& a, const DtResArgs& m, hipStream_t s) 
     if (st != hipSuccess) return st;
     st = hipMemsetAsync(m.gu, 0, dtrade_mw_gu_bytes(), s);
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(dt_mw_kernel, dim3(8u * m.nwg + 1u), dim3(kDmThreads), 0, s, a, m);
+    hipLaunchKernelGGL(dt_mw_kernel, dim3(8u * m.nwg + 1u), dim3(kDmThreads), 0, s, static_cast<const DtArgsCore&>(a), m);
     return hipGetLastError();
 }
 

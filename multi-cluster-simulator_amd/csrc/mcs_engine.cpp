@@ -528,8 +528,11 @@ int mcs_run(mcs_engine* e, uint32_t t_end_s, mcs_stats* stats) {
     if (stats) *stats = mcs_stats{};
     if (!e->has_clusters || !e->has_jobs) return fail(e, MCS_E_STATE, "load clusters and jobs first");
     if (e->online || t_end_s != MCS_TIME_NONE) { /* online mode (mcs_online.cpp) */
-        if (e->cfg.borrow || e->cfg.trader)
-            return fail(e, MCS_E_INVALID, "finite horizons are implemented for FIFO/DELAY without trading");
+        if (e->cfg.borrow || (e->cfg.trader && !mcs::is_dtrade(e)))
+            return fail(e, MCS_E_INVALID, "finite horizons are not built for FIFO trading (cfg.borrow, or cfg.trader "
+                                          "under MCS_POLICY_FIFO): sessions run FIFO and DELAY without trading, and "
+                                          "DELAY with traders");
+        if (mcs::is_dtrade(e)) return mcs::dtrade_session_run(e, t_end_s, stats);
         mcs::stream_run_begin(e, t_end_s);
         const int st = mcs::online_run(e, t_end_s, stats);
         mcs::stream_run_end(e, t_end_s, st);
@@ -827,6 +830,7 @@ int mcs_resource_utilization(mcs_engine* e, uint32_t cluster, float* core_util,
 int mcs_cluster_states(mcs_engine* e, uint32_t t_s, mcs_cluster_state* out, uint32_t n_clusters,
                        double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_cluster_states")) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
     if (e->dtrade_run)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading "
@@ -884,6 +888,7 @@ int mcs_cluster_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, ui
                              mcs_cluster_sample* out, mcs_cluster_state* first, uint32_t n_clusters,
                              double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_cluster_state_series")) return st;
     if (!e->has_run) return fail(e, MCS_E_STATE, "mcs_run first");
     if (e->dtrade_run)
         return fail(e, MCS_E_STATE, "cluster states are rebuilt from a FIFO/DELAY run without trading "
@@ -983,6 +988,7 @@ extern "C" {
 int mcs_wait_time_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                          mcs_wait_sample* out, uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_wait_time_series")) return st;
     if (!e->has_run || !e->delay_run) return fail(e, MCS_E_STATE, "no DELAY run");
     if (e->trade_run || e->dtrade_run)
         return fail(e, MCS_E_STATE, "the wait time series is rebuilt from a DELAY run without trading "
@@ -1062,6 +1068,7 @@ int mcs::wait_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n
 // mcs_level1_series and mcs_read_level1 read the placements of a DELAY run, with or without trading,
 // that this engine holds whole
 static int level1_state_check(mcs_engine* e) {
+    if (int st = mcs::refuse_trade_session(e, "mcs_level1_series / mcs_read_level1")) return st;
     if (!e->has_run || !e->delay_run) return fail(e, MCS_E_STATE, "no DELAY run");
     if (e->world != 1)
         return fail(e, MCS_E_STATE, "the Level1 series is rebuilt on one engine that holds the whole system "

@@ -41,6 +41,18 @@ int dtrade_phase(mcs_engine* e, uint32_t phase, const void* in, uint64_t in_byte
                  uint64_t out_bytes, uint32_t* done);
 int dtrade_end(mcs_engine* e, mcs_stats* stats);
 inline bool is_dtrade(const mcs_engine* e);
+// a trading session: online mode of a DELAY trading system on one engine (mcs_dtrade.cpp, DESIGN.md
+// §14 "Trading sessions").  online_begin starts it (dtrade_session_reset: the next run starts at
+// t = 0); mcs_run goes through dtrade_session_run; mcs_append_jobs moves the Level1 lists when the
+// segments grow (dtrade_session_relayout, before the old segment starts are freed) and points the
+// kernels at the new arrays (dtrade_session_rebind, after the engine's pointers changed).
+inline bool is_trade_session(const mcs_engine* e);
+void dtrade_session_reset(mcs_engine* e);
+int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats);
+int dtrade_session_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off, size_t rows);
+void dtrade_session_rebind(mcs_engine* e);
+// the telemetry calls refuse a trading session (they are rebuilt from batch runs and plain sessions)
+int refuse_trade_session(mcs_engine* e, const char* call);
 // the body of mcs_wait_time_series behind its state checks (mcs_engine.cpp): the wait_*_kernels over
 // the engine's placements, whichever DELAY run wrote them (mcs_dtrade_state_series reuses it)
 // seg: an online session's segments (job_off, d_job_cnt), for mcs_online_state_series
@@ -203,6 +215,15 @@ struct mcs_engine {
     uint32_t on_series_hor = 0;        // that run's horizon (MCS_TIME_NONE: a drain)
     bool bounds_known = false;         // last_arr / sum_dur filled
     bool on_run_failed = false;        // the session's last mcs_run returned an error
+    // a trading session (online && is_dtrade; mcs_dtrade.cpp): the lock-step state stays in HBM
+    bool ts_begun = false;             // the device holds the session's state (false: the next run starts at t = 0)
+    bool ts_failed = false;            // capacity exhausted: mcs_run refuses until mcs_rewind or a new submit
+    bool ts_drained = false;           // the last mcs_run was a drain
+    uint32_t ts_t_last = 0;            // last executed tick
+    uint32_t ts_t_next = 0;            // the tick the next-tick rule chose when the run parked
+    uint32_t ts_any_due = 1;           // ... and whether a trader round is due at it
+    uint32_t ts_pend_min = 0xFFFFFFFFu;  // earliest arrival appended since the last executed tick
+    uint32_t ts_ticks_last = 0, ts_ticks_total = 0, ts_restarts = 0;
     // the start-stream cursor of the session (mcs_stream.cpp): device arrays kept between calls
     bool st_open = false;
     std::string st_cause;              // what closed the last stream (empty: nothing did)
@@ -221,6 +242,7 @@ struct mcs_engine {
 };
 
 inline bool mcs::is_dtrade(const mcs_engine* e) { return e->cfg.policy == MCS_POLICY_DELAY && e->cfg.trader; }
+inline bool mcs::is_trade_session(const mcs_engine* e) { return e->online && is_dtrade(e); }
 
 inline int fail(mcs_engine* e, int code, const std::string& msg) {
     if (e) e->err = msg;

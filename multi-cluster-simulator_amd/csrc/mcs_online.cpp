@@ -9,6 +9,8 @@
 // and writes the other, so a slot-pool overflow re-runs the horizon from the untouched input).
 // Streams live in per-cluster segments with slack (job_off = segment starts, job_cnt = lengths),
 // grown by doubling when an append does not fit.
+// With MCS_POLICY_DELAY and cfg.trader the session is a trading session: the same segments and append
+// path, but the state between calls is the lock-step system's and mcs_run goes to mcs_dtrade.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -160,8 +162,15 @@ int ensure_l1(mcs_engine* e) {
 
 // a session at t = 0 over the streams in HBM
 int online_begin(mcs_engine* e) {
-    if (e->cfg.borrow || e->cfg.trader)
-        return fail(e, MCS_E_STATE, "online mode (finite horizons, appends) is not available with borrow/trader");
+    if (e->cfg.borrow || (e->cfg.trader && !is_dtrade(e)))
+        return fail(e, MCS_E_STATE, "online mode (finite horizons, appends) is not built for FIFO trading (cfg.borrow, "
+                                    "or cfg.trader under MCS_POLICY_FIFO)");
+    const bool dts = is_dtrade(e);  // a trading session (mcs_dtrade.cpp): the lock-step state instead of OnlineState
+    if (dts && (e->world != 1 || e->comm))
+        return fail(e, MCS_E_STATE, "a trading session runs on one engine that holds the whole system (rank 0 of "
+                                    "world 1, no communicator): sharded DELAY trading runs as a batch");
+    if (dts)
+        if (int st = ensure_job_records(e)) return st;
     if (e->gen.on) {  // a fused synthetic stream: online runs read records
         if (int st = ensure_job_records(e)) return st;
         e->gen.on = 0;
@@ -175,12 +184,16 @@ int online_begin(mcs_engine* e) {
         if (int st = stream_bounds(e, e->last_arr, e->sum_dur)) return st;
         e->bounds_known = true;
     }
-    if (int st = alloc_state(e)) return st;
-    if (int st = ensure_l1(e)) return st;
+    if (dts) {
+        dtrade_session_reset(e);
+    } else {
+        if (int st = alloc_state(e)) return st;
+        if (int st = ensure_l1(e)) return st;
+    }
     stream_shut(e, "a restart of the session");  // every row is undecided again: nothing kept holds
     e->on_run_failed = false;
     e->on_cur = 0;
-    HIPCHK(e, hipMemset(e->d_ost[0], 0, (e->C ? e->C : 1) * sizeof(OnlineState)));  // valid = 0: the spec
+    if (!dts) HIPCHK(e, hipMemset(e->d_ost[0], 0, (e->C ? e->C : 1) * sizeof(OnlineState)));  // valid = 0: the spec
     // every row is undecided again.  The rows may hold an earlier pass's results (a batch run, or the
     // session before mcs_rewind), and the HOR kernels write a row only when they decide it: jobs
     // appended to the restarted session can change later decisions, so a stale start below the next
@@ -443,8 +456,9 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
                     const uint32_t* mem, const uint64_t* job_offsets) {
     if (int st = check_engine(e)) return st;
     if (!e->has_clusters) return fail(e, MCS_E_STATE, "mcs_load_clusters first");
-    if (e->cfg.borrow || e->cfg.trader)
-        return fail(e, MCS_E_STATE, "online mode (finite horizons, appends) is not available with borrow/trader");
+    if (e->cfg.borrow || (e->cfg.trader && !mcs::is_dtrade(e)))
+        return fail(e, MCS_E_STATE, "online mode (finite horizons, appends) is not built for FIFO trading (cfg.borrow, "
+                                    "or cfg.trader under MCS_POLICY_FIFO)");
     if (!job_offsets) return fail(e, MCS_E_INVALID, "null job_offsets");
     if (job_offsets[0] != 0) return fail(e, MCS_E_INVALID, "job_offsets[0] must be 0");
     const uint32_t C = e->C;
@@ -527,6 +541,8 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
         }
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (int st = mcs::stream_relayout(e, e->d_job_off, d_noff, noff)) return st;  // an open stream's arrays follow
+        if (mcs::is_dtrade(e))  // a trading session's Level1 lists follow
+            if (int st = mcs::dtrade_session_relayout(e, e->d_job_off, d_noff, nt)) return st;
         dfree(e->d_jobs);
         dfree(e->d_out_node);
         dfree(e->d_out_start);
@@ -543,7 +559,8 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
         e->d_job_off = d_noff;
         e->job_off = noff;
         e->segmented = true;
-        if (int st = mcs::ensure_l1(e)) return st;  // the backup follows the capacity
+        if (mcs::is_dtrade(e)) mcs::dtrade_session_rebind(e);
+        else if (int st = mcs::ensure_l1(e)) return st;  // the backup follows the capacity
     }
     // the new records, after each cluster's jobs
     if (na) {
@@ -570,6 +587,7 @@ int mcs_append_jobs(mcs_engine* e, const uint32_t* arrival_s, const uint32_t* du
         const uint64_t n = job_offsets[c + 1] - job_offsets[c];
         if (!n) continue;
         e->job_cnt[c] += (uint32_t)n;
+        e->ts_pend_min = std::min(e->ts_pend_min, arrival_s[job_offsets[c]]);  // (a trading session's resume tick)
         e->last_arr[c] = arrival_s[job_offsets[c + 1] - 1];
         e->sum_dur[c] += add_sum[c];
     }
@@ -590,6 +608,7 @@ int mcs_online_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
                             mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
                             uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_online_state_series")) return st;
     if (!e->online)
         return fail(e, MCS_E_STATE, "mcs_online_state_series reads an online session (mcs_run with a horizon, "
                                     "mcs_append_jobs); after a batch run: mcs_cluster_state_series and "
@@ -627,6 +646,7 @@ int mcs_online_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
 int mcs_online_level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                              mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_online_level1_series")) return st;
     if (!e->online)
         return fail(e, MCS_E_STATE, "mcs_online_level1_series reads an online session (mcs_run with a horizon, "
                                     "mcs_append_jobs); after a batch run: mcs_level1_series");

@@ -122,6 +122,7 @@ extern "C" {
 
 int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
     if (int st = check_engine(e)) return st;
+    if (int st = mcs::refuse_trade_session(e, "mcs_stream_open")) return st;
     if (!e->online)
         return fail(e, MCS_E_STATE, "mcs_stream_open subscribes to an online session (mcs_run with a horizon, "
                                     "mcs_append_jobs; FIFO or DELAY without trading)");

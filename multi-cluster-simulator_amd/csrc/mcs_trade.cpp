@@ -837,6 +837,9 @@ int mcs_trade_begin(mcs_engine* e) {
     if (int st = check_engine(e)) return st;
     if (mcs::is_dtrade(e)) {
         if (!e->has_jobs) return fail(e, MCS_E_STATE, "mcs_submit_jobs first");
+        if (mcs::is_trade_session(e))
+            return fail(e, MCS_E_STATE, "a trading session is active (mcs_run with a horizon, mcs_append_jobs): the "
+                                        "caller-driven lock-step starts from submitted jobs (mcs_submit_jobs)");
         if (int st = mcs::ensure_job_records(e)) return st;
         return mcs::dtrade_begin(e);
     }

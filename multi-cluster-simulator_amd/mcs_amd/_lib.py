@@ -226,6 +226,11 @@ class mcs_trade_stats(C.Structure):
 MCS_TRADE_SHAPE_WORDS = 8
 
 
+class mcs_trade_session(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("t_horizon", "t_last", "t_next", "ticks_last_run", "ticks_total",
+                                          "restarts", "drained", "failed")]
+
+
 class mcs_approve_query(C.Structure):
     _fields_ = [("total_cores", C.c_uint32), ("total_memory", C.c_uint32), ("core_util", C.c_float),
                 ("mem_util", C.c_float), ("cores", C.c_uint32), ("memory", C.c_uint32), ("time_s", C.c_uint32),
@@ -312,6 +317,7 @@ SIGNATURES = [
     ("mcs_read_foreign", C.c_int, [vp, C.POINTER(mcs_foreign_rec), C.c_uint64, u64p]),
     ("mcs_read_virtual_node_caps", C.c_int, [vp, C.c_uint32, u32p, u32p, C.c_uint32, u32p]),
     ("mcs_approve_trade", C.c_int, [vp, C.POINTER(mcs_approve_query), C.c_uint32, i32p]),
+    ("mcs_trade_session_info", C.c_int, [vp, C.POINTER(mcs_trade_session)]),
 ]
 
 _lib = None

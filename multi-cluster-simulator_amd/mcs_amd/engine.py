@@ -315,6 +315,13 @@ class Engine:
         self._c(L.lib().mcs_read_trade_stats(self._h, C.byref(ts)))
         return {k: getattr(ts, k) for k, _ in L.mcs_trade_stats._fields_ if k != "pad"}
 
+    def trade_session_info(self) -> dict:
+        """mcs_trade_session_info: where a trading session stands (online mode of a DELAY trading system,
+        DESIGN.md §14): t_horizon, t_last, t_next, ticks_last_run, ticks_total, restarts, drained, failed."""
+        ts = L.mcs_trade_session()
+        self._c(L.lib().mcs_trade_session_info(self._h, C.byref(ts)))
+        return {k: getattr(ts, k) for k, _ in L.mcs_trade_session._fields_}
+
     def lent(self) -> np.ndarray:
         """Lent runs of this engine's clusters (LENT_DTYPE), sorted by (start, lender, borrower, job)."""
         n = C.c_uint64()
@@ -374,7 +381,8 @@ class Engine:
     def run(self, t_end: Optional[int] = None) -> RunStats:
         """mcs_run: a batch run (t_end None, no online session), or online mode:
         every decision at simulated seconds < t_end, or with t_end None a drain of every job
-        appended so far."""
+        appended so far.  With policy DELAY and trader=True the session is a trading session: every
+        lock-step tick below t_end, trader rounds and samples included (trade_session_info())."""
         st = L.mcs_stats()
         self._c(L.lib().mcs_run(self._h, L.MCS_TIME_NONE if t_end is None else int(t_end), C.byref(st)))
         return RunStats.from_c(st)
