@@ -243,10 +243,11 @@ int mcs_dtrade_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, u
  * session from t = 0 up to the horizon (restarts counts it); when the capacity is exhausted the call
  * returns MCS_E_CAPACITY and mcs_run returns MCS_E_STATE until mcs_rewind or a new submit.
  * MCS_E_STATE: FIFO trading (borrow, or trader under FIFO), a sharded engine or one with a
- * communicator, mcs_trade_begin during a session, and during a session every telemetry call
- * (mcs_dtrade_state_series, mcs_level1_series, mcs_read_level1, mcs_online_state_series,
- * mcs_online_level1_series, mcs_stream_open, mcs_cluster_states, mcs_cluster_state_series,
- * mcs_wait_time_series). */
+ * communicator, mcs_trade_begin during a session, and during a session every telemetry call of
+ * batch runs and plain sessions (mcs_dtrade_state_series, mcs_level1_series, mcs_read_level1,
+ * mcs_online_state_series, mcs_online_level1_series, mcs_stream_open, mcs_cluster_states,
+ * mcs_cluster_state_series, mcs_wait_time_series): a trading session's Start stream is read with
+ * mcs_trade_session_state_series and mcs_trade_session_level1_series below. */
 typedef struct mcs_trade_session {
     uint32_t t_horizon;      /* last finite horizon (0: none yet)                                      */
     uint32_t t_last;         /* last executed tick                                                     */
@@ -260,6 +261,36 @@ typedef struct mcs_trade_session {
 } mcs_trade_session;
 /* MCS_E_STATE without a trading session. */
 int mcs_trade_session_info(mcs_engine* eng, mcs_trade_session* out);
+
+/* The Start stream of a trading session (DESIGN.md §14 "The Start stream of a trading session"): the
+ * record of mcs_dtrade_state_series, argument for argument, read from the session as its last mcs_run
+ * left it.  Rows: the physical nodes, then the virtual nodes the cluster has received so far; own jobs
+ * hold on start <= t < finish, Foreign jobs on start_s < t < finish_s; uint64 counters that wrap; float32
+ * terms in row order over the physical totals; running, queued and the wait statistics as there.  wait
+ * and first may be NULL.
+ *   - After mcs_run(h), h finite, every sample second must lie below h (MCS_E_INVALID otherwise; the
+ *     message names h).  Such a sample is final: it equals, bit for bit, what mcs_dtrade_state_series
+ *     returns for that second after a batch run over all the jobs the session ever receives, as long as
+ *     that run reaches the second.
+ *   - After a drain any second up to 0xFFFFFFFE is accepted; the samples are those of the batch run over
+ *     the jobs held, the Go loop of the wait statistics continued past its end.
+ * MCS_E_INVALID otherwise as mcs_cluster_state_series.  MCS_E_STATE, with the cause in mcs_last_error:
+ * without a trading session; after mcs_rewind (or the session's begin) until the next mcs_run; after the
+ * session failed (MCS_E_CAPACITY); after jobs appended behind a drain until the next mcs_run; and when
+ * the run's flags carry a Foreign-log or contract-log overflow (MCS_FLAG_LOG_OVERFLOW) or a virtual-node
+ * overflow, as mcs_dtrade_state_series refuses.  Nothing is kept between calls.  The Foreign log, which
+ * grows with the session's age, is compacted per call to the records that can hold at one of the call's
+ * samples once the log and the call are long enough for that to pay; MCS_DT_FOREIGN_FILTER in the
+ * environment at mcs_create forces the choice (0: the log is scanned as it is; any other value: always
+ * compacted; A/B runs and tests; the bytes are equal).  Not available: a cursor (mcs_stream_*),
+ * mcs_read_level1, sharded engines. */
+int mcs_trade_session_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                                   mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                                   uint32_t n_clusters, double* kernel_ms);
+/* What ProvideJobs hands the trader in a trading session: mcs_online_level1_series (mcs.h) over the
+ * trading session's rows, under the frontier and the refusals of mcs_trade_session_state_series. */
+int mcs_trade_session_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                                    mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms);
 
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,

@@ -3,7 +3,8 @@
 // hipGraph, one host poll per replay; world > 1: an ncclAllGather of the exchange blocks between
 // the kernels, or the caller-driven phases), capacity escalation and the result readers of
 // mcs_trade.h; and trading sessions: the same system in online mode, resumed from
-// its control block slice by slice on the replayed kernels (dts_slice, dtrade_session_run).
+// its control block slice by slice on the replayed kernels (dts_slice, dtrade_session_run), and the
+// session's Start stream (mcs_trade_session_state_series, mcs_trade_session_level1_series).
 // Every decision is made by the gfx950 kernels of mcs_dtrade.hip; there is no CPU path.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -471,6 +472,7 @@ int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
         return fail(e, MCS_E_INVALID, "the horizon lies above t_max_s + 1 = " + std::to_string((uint64_t)t_max + 1u) +
                                           ": cfg.t_max_s bounds the lock-step clock");
     const auto w0 = std::chrono::steady_clock::now();
+    e->on_series_ok = false;  // until this run has ended well (mcs_trade_session_state_series)
     uint32_t escalations = 0;
     double kms = 0.0;
     for (;;) {
@@ -520,6 +522,8 @@ int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     e->trade_run = false;
     e->delay_run = true;
     e->ts_drained = t_hor == MCS_TIME_NONE;
+    e->on_series_ok = true;
+    e->on_series_hor = t_hor;
     if (t_hor != MCS_TIME_NONE) e->on_t_hor = e->on_t_done = t_hor;
     // the lock-step clock is common to all clusters: later arrivals lie above the last executed tick
     if (e->ts_ticks_total) e->on_floor.assign(e->C, e->ts_t_last + 1u);
@@ -578,8 +582,9 @@ void dtrade_session_rebind(mcs_engine* e) {
 int refuse_trade_session(mcs_engine* e, const char* call) {
     if (!is_trade_session(e)) return MCS_OK;
     return fail(e, MCS_E_STATE, std::string(call) + " is not available in a trading session (online mode with "
-                                    "MCS_POLICY_DELAY and cfg.trader): the telemetry calls read batch runs and "
-                                    "sessions without trading");
+                                    "MCS_POLICY_DELAY and cfg.trader): it reads batch runs and sessions without "
+                                    "trading (in a trading session: mcs_trade_session_state_series, "
+                                    "mcs_trade_session_level1_series)");
 }
 
 void dtrade_release_graphs(mcs_engine* e) {
@@ -975,6 +980,30 @@ int mcs_read_virtual_node_caps(mcs_engine* e, uint32_t cluster, uint32_t* cores,
     return MCS_OK;
 }
 
+}  // extern "C"
+
+static int dt_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                           mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                           uint32_t n_clusters, double* kernel_ms, bool seg, uint32_t hor);
+
+// the run's flags (dt_clusters has just read the control block): the telemetry refuses a run that an
+// overflow cut short or whose logs dropped records
+static int dt_flags_check(mcs_engine* e, const std::vector<mcs::DtCluster>& cl) {
+    const mcs::DtradeDev* d = e->dtd;
+    const mcs::DtCtl ctl = *d->h_ctl;
+    uint32_t flags = ctl.flags;
+    for (uint32_t k = 0; k < e->C; ++k) flags |= cl[k].flags;
+    if (flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))
+        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run that a slot-pool overflow or a "
+                                    "virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW) cut short");
+    if ((flags & MCS_FLAG_LOG_OVERFLOW) || ctl.n_foreign > d->a.foreign_cap || ctl.n_trades > d->a.trade_cap)
+        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run whose Foreign or contract log "
+                                    "overflowed (MCS_FLAG_LOG_OVERFLOW): records were dropped");
+    return MCS_OK;
+}
+
+extern "C" {
+
 // The ClusterState record and the wait statistics of a DELAY trading run: the third
 // form of the state kernels (mcs_state.hip, dt_*) over the placements, the virtual-node table and the
 // Foreign log, and the wait_*_kernels over the placements.
@@ -994,23 +1023,42 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     if (e->world != 1)
         return fail(e, MCS_E_STATE, "cluster states of a sharded DELAY trading run: the placements of the other "
                                     "ranks' clusters live there (run the system on one engine)");
+    return dt_state_series(e, t0_s, period_s, n_samples, out, wait, first, n_clusters, kernel_ms, false, MCS_TIME_NONE);
+}
+
+}  // extern "C"
+
+// A session's call compacts the Foreign log (dt_foreign_live_kernel) when the direct scan it replaces is at
+// least this many scan rounds: a workgroup reads the log in rounds of 256 records, once per tile of the call.
+// The pre-pass (a 4-byte fill and a launch) costs 3.6 us and a round 0.2 us, so it pays from 18 rounds on:
+// a one-tile call over a log of 4353 records, or 18 tiles over a log of up to 256 (DESIGN.md §14 has the
+// measurement; below the break-even the direct scan was faster by more than the spread between rounds).
+// The two costs are a model fitted to calls of 1, 8 and 40 tiles over logs of at most 232 records, one
+// round per tile: the pre-pass lost at 8 rounds and won at 40, nothing was measured between them or with
+// several rounds per tile, so the 4353 records are an extrapolation.  A heuristic: it takes the tile
+// count of the widest cluster (max_nn) for all, and either choice returns the same bytes.
+static constexpr uint64_t kDtForeignFilterMinRounds = 18;
+
+// The body of mcs_dtrade_state_series behind its state checks.  seg: a trading session
+// (mcs_trade_session_state_series): the SEG kernels over the session's segments, the virtual-node table
+// and the Foreign log as the last mcs_run left them; hor is then the decided frontier (MCS_TIME_NONE
+// after a drain, and for a batch run), checked after the argument checks of mcs_cluster_state_series.
+static int dt_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                           mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                           uint32_t n_clusters, double* kernel_ms, bool seg, uint32_t hor) {
     mcs::DtradeDev* d = e->dtd;
     std::vector<mcs::DtCluster> cl;
     if (int st = mcs::dt_clusters(e, cl)) return st;
     const mcs::DtCtl ctl = *d->h_ctl;
-    uint32_t flags = ctl.flags;
-    for (uint32_t k = 0; k < e->C; ++k) flags |= cl[k].flags;
-    if (flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))
-        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run that a slot-pool overflow or a "
-                                    "virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW) cut short");
-    if ((flags & MCS_FLAG_LOG_OVERFLOW) || ctl.n_foreign > d->a.foreign_cap || ctl.n_trades > d->a.trade_cap)
-        return fail(e, MCS_E_STATE, "cluster states of a DELAY trading run whose Foreign or contract log "
-                                    "overflowed (MCS_FLAG_LOG_OVERFLOW): records were dropped");
+    if (int st = dt_flags_check(e, cl)) return st;
     if (!out || n_clusters > e->C) return fail(e, MCS_E_INVALID, "bad output");
     if (period_s == 0 || n_samples == 0) return fail(e, MCS_E_INVALID, "period_s and n_samples must be positive");
     if ((uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s > 0xFFFFFFFEull)
         return fail(e, MCS_E_INVALID, "the last sample lies past second 0xFFFFFFFE");
     if (ctl.n_foreign > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "more than 2^32 - 2 Foreign jobs");
+    if (hor != MCS_TIME_NONE && (uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s >= hor)
+        return fail(e, MCS_E_INVALID, "the last sample lies at or past the last horizon " + std::to_string(hor) +
+                                          ": only samples below it are decided");
     if (int st = mcs::ensure_job_records(e)) return st;
     if (n_clusters == 0) {
         if (kernel_ms) *kernel_ms = 0.0;
@@ -1019,7 +1067,7 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     double total_ms = 0.0;
     if (wait) {  // (its own argument checks repeat the ones above and add the per-cluster job limit)
         double ms = 0.0;
-        if (int st = mcs::wait_series(e, t0_s, period_s, n_samples, wait, n_clusters, &ms)) return st;
+        if (int st = mcs::wait_series(e, t0_s, period_s, n_samples, wait, n_clusters, &ms, seg)) return st;
         total_ms += ms;
     }
     const uint32_t V = d->a.V;
@@ -1039,11 +1087,22 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     mcs_cluster_sample* d_out = nullptr;
     mcs_cluster_state* d_first = nullptr;
     uint2* d_summ = nullptr;
+    mcs_foreign_rec* d_live = nullptr;  // a session's call: the Foreign records that can hold at one of its samples
+    uint32_t* d_live_n = nullptr;
+    const uint32_t n_foreign = (uint32_t)ctl.n_foreign;
+    const uint64_t scan_rounds = ((uint64_t)n_foreign + 255u) / 256u *
+                                 (((uint64_t)n_samples + mcs::dt_series_tile(max_nn) - 1u) / mcs::dt_series_tile(max_nn));
+    const bool filter = seg && n_foreign > 0 &&
+                        (e->dt_foreign_filter < 0 ? scan_rounds >= kDtForeignFilterMinRounds : e->dt_foreign_filter != 0);
     hipError_t st = hipMalloc(&d_nv, e->C * sizeof(uint32_t));
     if (st == hipSuccess) st = hipMemcpy(d_nv, nv.data(), e->C * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (st == hipSuccess) st = hipMalloc(&d_out, (size_t)n_clusters * chunk * sizeof(mcs_cluster_sample));
-    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(e->total_jobs, e->C) * sizeof(uint2));
+    // (over segments with slack the summaries are indexed by capacity: series_summ_size)
+    const uint64_t rows = seg ? e->job_off[e->C] : e->total_jobs;
+    if (st == hipSuccess) st = hipMalloc(&d_summ, mcs::series_summ_size(rows, e->C) * sizeof(uint2));
     if (st == hipSuccess && first) st = hipMalloc(&d_first, n_clusters * sizeof(mcs_cluster_state));
+    if (st == hipSuccess && filter) st = hipMalloc(&d_live, (size_t)n_foreign * sizeof(mcs_foreign_rec));
+    if (st == hipSuccess && filter) st = hipMalloc(&d_live_n, sizeof(uint32_t));
     mcs::DtSeriesArgs a{};
     a.d.s.node_off = e->d_node_off;
     a.d.s.cap = e->d_cap;
@@ -1056,10 +1115,11 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     a.d.s.out = d_first;
     a.d.s.t = t0_s;
     a.d.s.n_clusters = n_clusters;
+    a.d.s.job_cnt = seg ? e->d_job_cnt : nullptr;
     a.d.vcap = d->vcap;
     a.d.nv = d_nv;
     a.d.flog = d->foreign;
-    a.d.n_foreign = (uint32_t)ctl.n_foreign;
+    a.d.n_foreign = n_foreign;
     a.d.V = V;
     a.summ = d_summ;
     a.out = d_out;
@@ -1074,6 +1134,13 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
             // the stream's first message: a plain scan at t0_s, independent of the tile walk
             if (first) st = mcs::launch_dt_state(a.d, max_nn, e->stream);
             if (st == hipSuccess) st = mcs::launch_dt_series_summary(a, e->stream);
+            if (st == hipSuccess && filter) {  // once per call: the bounds are those of all its chunks
+                st = mcs::launch_dt_foreign_live(d->foreign, n_foreign, t0_s,
+                                                 (uint32_t)(t0_s + (uint64_t)(n_samples - 1) * period_s), d_live,
+                                                 d_live_n, e->stream);
+                a.live = d_live;
+                a.live_n = d_live_n;
+            }
         }
         if (st == hipSuccess) st = mcs::launch_dt_state_series(a, max_nn, e->stream);
         if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
@@ -1092,9 +1159,67 @@ int mcs_dtrade_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uin
     (void)hipFree(d_out);
     (void)hipFree(d_summ);
     if (d_first) (void)hipFree(d_first);
+    if (d_live) (void)hipFree(d_live);
+    if (d_live_n) (void)hipFree(d_live_n);
     if (st != hipSuccess) return fail(e, MCS_E_HIP, std::string("DELAY trading state series: ") + hipGetErrorString(st));
     if (kernel_ms) *kernel_ms = total_ms;
     return MCS_OK;
+}
+
+// what both calls of a trading session check before their arguments: a session whose rows are as its
+// last mcs_run left them
+static int trade_session_series_check(mcs_engine* e, const char* call) {
+    const std::string c(call);
+    if (!mcs::is_trade_session(e))
+        return fail(e, MCS_E_STATE, c + " reads a trading session (online mode with MCS_POLICY_DELAY and "
+                                        "cfg.trader: mcs_run with a horizon, mcs_append_jobs); there is no trading "
+                                        "session (after a batch DELAY trading run: mcs_dtrade_state_series, "
+                                        "mcs_level1_series; in a session without trading: mcs_online_state_series, "
+                                        "mcs_online_level1_series)");
+    if (e->ts_failed)
+        return fail(e, MCS_E_STATE, c + ": the trading session failed (capacity exhausted, MCS_E_CAPACITY): "
+                                        "mcs_rewind or submit again, then run");
+    if (!e->has_run || !e->dtrade_run || !e->dtd || !e->d_job_cnt)
+        return fail(e, MCS_E_STATE, c + " reads the session as its last mcs_run left it: run first (no run since "
+                                        "the session began or since mcs_rewind)");
+    if (!e->on_series_ok)
+        return fail(e, MCS_E_STATE, c + " reads the session as its last mcs_run left it: run first (the last run "
+                                        "failed, or jobs were appended behind a drain and no run has seen them)");
+    return MCS_OK;
+}
+
+extern "C" {
+
+// The Start stream of a trading session (DESIGN.md §14 "The Start stream of a trading session"): the
+// record of mcs_dtrade_state_series read from the session as its last mcs_run left it.  Nothing is kept
+// between calls: the summaries, the wait records and the compacted Foreign list are rebuilt by every
+// call and freed with it.
+int mcs_trade_session_state_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                                   mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
+                                   uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (int st = trade_session_series_check(e, "mcs_trade_session_state_series")) return st;
+    return dt_state_series(e, t0_s, period_s, n_samples, out, wait, first, n_clusters, kernel_ms, true,
+                           e->on_series_hor);
+}
+
+// ProvideJobs' view of a trading session: mcs_online_level1_series' kernels over the session's rows
+// (Level1 depends on arrivals, starts and max_wait_s alone), under the same frontier.
+int mcs_trade_session_level1_series(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
+                                    mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms) {
+    if (int st = check_engine(e)) return st;
+    if (int st = trade_session_series_check(e, "mcs_trade_session_level1_series")) return st;
+    {  // the run's flags refuse as they do for the state series
+        std::vector<mcs::DtCluster> cl;
+        if (int st = mcs::dt_clusters(e, cl)) return st;
+        if (int st = dt_flags_check(e, cl)) return st;
+    }
+    if (int st = mcs::series_args_check(e, t0_s, period_s, n_samples, out, n_clusters)) return st;
+    const uint32_t h = e->on_series_hor;
+    if (h != MCS_TIME_NONE && (uint64_t)t0_s + (uint64_t)(n_samples - 1) * period_s >= h)
+        return fail(e, MCS_E_INVALID, "the last sample lies at or past the last horizon " + std::to_string(h) +
+                                          ": only samples below it are decided");
+    return mcs::level1_series(e, t0_s, period_s, n_samples, out, n_clusters, kernel_ms, true);
 }
 
 int mcs_approve_trade(mcs_engine* e, const mcs_approve_query* q, uint32_t n, int32_t* out) {

@@ -204,6 +204,8 @@ int mcs_engine_create(const mcs_config* cfg, int device, mcs_engine** out) {
     if (!e) return MCS_E_NOMEM;
     e->cfg = c;
     e->device = device;
+    if (const char* env = getenv("MCS_DT_FOREIGN_FILTER"))  // "0": a trading session's series scan the Foreign
+        e->dt_foreign_filter = strcmp(env, "0") != 0 ? 1 : 0;  // log as it is; any other value: always compacted
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
         delete e;

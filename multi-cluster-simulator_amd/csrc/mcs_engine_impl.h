@@ -51,7 +51,8 @@ void dtrade_session_reset(mcs_engine* e);
 int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats);
 int dtrade_session_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off, size_t rows);
 void dtrade_session_rebind(mcs_engine* e);
-// the telemetry calls refuse a trading session (they are rebuilt from batch runs and plain sessions)
+// the telemetry calls of batch runs and plain sessions refuse a trading session, whose own are
+// mcs_trade_session_state_series and mcs_trade_session_level1_series (mcs_dtrade.cpp)
 int refuse_trade_session(mcs_engine* e, const char* call);
 // the body of mcs_wait_time_series behind its state checks (mcs_engine.cpp): the wait_*_kernels over
 // the engine's placements, whichever DELAY run wrote them (mcs_dtrade_state_series reuses it)
@@ -224,6 +225,10 @@ struct mcs_engine {
     uint32_t ts_any_due = 1;           // ... and whether a trader round is due at it
     uint32_t ts_pend_min = 0xFFFFFFFFu;  // earliest arrival appended since the last executed tick
     uint32_t ts_ticks_last = 0, ts_ticks_total = 0, ts_restarts = 0;
+    // mcs_trade_session_state_series: compact the Foreign log per call (dt_foreign_live_kernel).
+    // -1: when the direct scan would take at least kDtForeignFilterMinRounds rounds (mcs_dtrade.cpp);
+    // MCS_DT_FOREIGN_FILTER at mcs_create: 0 never, any other value always
+    int dt_foreign_filter = -1;
     // the start-stream cursor of the session (mcs_stream.cpp): device arrays kept between calls
     bool st_open = false;
     std::string st_cause;              // what closed the last stream (empty: nothing did)

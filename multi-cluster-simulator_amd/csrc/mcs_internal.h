@@ -224,6 +224,11 @@ struct DtSeriesArgs {
     mcs_cluster_sample* out;  // [d.s.n_clusters][n_samples], cluster-major
     uint32_t t0, period, n_samples;
     unsigned long long magic;
+    // a trading session's call (d.s.job_cnt set) with the pre-pass: dt_foreign_live_kernel's list of the
+    // Foreign records that can hold at one of the call's samples, scanned in place of d.flog, and its
+    // length on the device (at most d.n_foreign).  Null: the log is scanned as it is.
+    const mcs_foreign_rec* live;
+    const uint32_t* live_n;
 };
 // samples per tile of a cluster of nn = N + nv rows: 2 nn LDS rows of u64, then the u32 rows of
 // series_rows(0); odd, as series_tile.  nn <= 1280 leaves a tile of 3 samples.
@@ -236,6 +241,8 @@ __host__ __device__ inline uint32_t dt_series_tile(uint32_t nn) {
 hipError_t launch_dt_state(const DtStateArgs& a, uint32_t max_nn, hipStream_t s);
 hipError_t launch_dt_series_summary(const DtSeriesArgs& a, hipStream_t s);
 hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStream_t s);
+hipError_t launch_dt_foreign_live(const mcs_foreign_rec* flog, uint32_t n_foreign, uint32_t t_first, uint32_t t_last,
+                                  mcs_foreign_rec* live, uint32_t* live_n, hipStream_t s);
 
 // The average wait time series of a DELAY run (mcs_wait.hip): WaitTime after the Delay iteration at
 // the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters.

@@ -32,7 +32,9 @@
 // the per-lender lists from the engine's lent log (execution order, 32 B records) once per run.
 //
 // After a DELAY trading run (mcs_dtrade_state_series) dt_state_kernel and dt_series_kernel, further
-// down, rebuild the record with virtual-node rows, Foreign jobs and 64-bit wrapping counters.
+// down, rebuild the record with virtual-node rows, Foreign jobs and 64-bit wrapping counters; in a
+// trading session (mcs_trade_session_state_series) their SEG instantiations do, behind
+// dt_foreign_live_kernel's per-call compaction of the Foreign log.
 //
 // In an online session (mcs_online_state_series) the kernels are the SEG instantiations
 // of the plain code: a cluster's rows are the first job_cnt[c] of the segment at job_off[c], and its
@@ -522,6 +524,13 @@ __global__ __launch_bounds__(kStateThreads) void series_kernel(SeriesArgs a) {
 //     workgroup (C5-DELAY logs 232 records, 9 KB, §13); no order is assumed, the loop is bounded by
 //     the record count passed at launch.
 //   - the utilization sums run over the NN rows in order; the totals stay the physical sums.
+// In a trading session (mcs_trade_session_state_series) both kernels are their SEG
+// instantiations: the row count comes from job_cnt (rows_of) and the summaries are the TRADE summary
+// kernel's SEG form, indexed over segment capacity.  Nothing else differs in dt_state_kernel.  The SEG
+// series kernel scans, in place of the log, the list dt_foreign_live_kernel compacted from it for
+// the call (a session's log grows with its age; the list holds what can hold at one of the call's
+// samples).  The list's order is arbitrary: a Foreign hold is two integer adds modulo 2^64 into the
+// row accumulators and an integer range count, all commutative and exact, so the order changes no bit.
 __device__ __forceinline__ void range_add64(unsigned long long* row, uint32_t lo, uint32_t hi, uint32_t tsa,
                                             unsigned long long v) {
     if (lo < hi) {
@@ -530,6 +539,7 @@ __device__ __forceinline__ void range_add64(unsigned long long* row, uint32_t lo
     }
 }
 
+template <bool SEG = false>
 __global__ __launch_bounds__(kStateThreads) void dt_state_kernel(DtStateArgs a) {
     extern __shared__ unsigned long long used64[];  // [2 * max_nn]: cores then memory per row
     const uint32_t c = blockIdx.x;
@@ -540,7 +550,7 @@ __global__ __launch_bounds__(kStateThreads) void dt_state_kernel(DtStateArgs a) 
     __syncthreads();
 
     const uint64_t j0 = a.s.job_off[c];
-    const uint32_t J = (uint32_t)(a.s.job_off[c + 1] - j0);
+    const uint32_t J = (uint32_t)rows_of<SEG>(a.s, c);
     const int32_t* __restrict__ node = a.s.out_node + j0;
     const uint32_t* __restrict__ start = a.s.out_start + j0;
     const uint32_t* __restrict__ finish = a.s.out_finish + j0;
@@ -606,6 +616,7 @@ __global__ __launch_bounds__(kStateThreads) void dt_state_kernel(DtStateArgs a) 
 
 // series_kernel's tile walk with 64-bit node rows: LDS holds 2 NN rows of TS u64 (cores, memory),
 // then 2 kSeriesRep counter rows and two result rows of TS u32, TS = dt_series_tile(NN).
+template <bool SEG = false>
 __global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a) {
     extern __shared__ unsigned long long d64[];  // [2 NN][TS] u64, then [2 kSeriesRep + 2][TS] u32
     __shared__ uint64_t masks[3][4];
@@ -617,7 +628,7 @@ __global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a
     const uint32_t n0 = s_.node_off[c], N = s_.node_off[c + 1] - n0;
     const uint32_t nvc = a.d.nv[c] < a.d.V ? a.d.nv[c] : a.d.V, NN = N + nvc;
     const uint64_t j0 = s_.job_off[c];
-    const uint64_t J = s_.job_off[c + 1] - j0;
+    const uint64_t J = rows_of<SEG>(s_, c);
     const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
     const int32_t* __restrict__ node = s_.out_node + j0;
     const uint32_t* __restrict__ start = s_.out_start + j0;
@@ -652,6 +663,18 @@ __global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a
     }
     __syncthreads();
     const float ftc = (float)tot[0], ftm = (float)tot[1];
+    // the Foreign records a tile scans: the log as it is, or (SEG, a trading session's call with the
+    // pre-pass) dt_foreign_live_kernel's list, whose length is read here: the pre-pass ran before
+    // this launch on the same stream
+    const mcs_foreign_rec* __restrict__ flog = a.d.flog;
+    uint32_t n_foreign = a.d.n_foreign;
+    if constexpr (SEG) {
+        if (a.live_n) {
+            const uint32_t nl = *a.live_n;
+            flog = a.live;
+            n_foreign = nl < n_foreign ? nl : n_foreign;  // (the list is sized to the log)
+        }
+    }
 
     uint64_t b_lo = 0;
     for (uint32_t k0 = 0; k0 < n; k0 += TS) {
@@ -733,8 +756,8 @@ __global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a
             if (any_past) break;
         }
         // the Foreign jobs of this responder: they hold on start_s < t < finish_s
-        for (uint32_t i = tid; i < a.d.n_foreign; i += kStateThreads) {
-            const mcs_foreign_rec* __restrict__ r = a.d.flog + i;
+        for (uint32_t i = tid; i < n_foreign; i += kStateThreads) {
+            const mcs_foreign_rec* __restrict__ r = flog + i;
             if (r->responder != c) continue;
             const uint32_t fs = r->start_s, ff = r->finish_s;
             if (fs >= t_last || ff <= t_first) continue;  // (fs < t_last <= 0xFFFFFFFE: fs + 1 fits)
@@ -799,6 +822,37 @@ __global__ __launch_bounds__(kStateThreads) void dt_series_kernel(DtSeriesArgs a
             reinterpret_cast<uint4*>(a.out)[(size_t)c * n + k0 + tid] = v;
         }
         __syncthreads();  // the rows are zeroed for the next tile
+    }
+}
+
+// The pre-pass of a trading session's call: the Foreign records that can hold at one of the call's
+// samples, which lie in [t_first, t_last]: start_s < t_last, finish_s > t_first and a window that is
+// not empty.  One record per thread.  A wave counts its keepers with a ballot, lane 0 takes the wave's
+// room in the list with one atomic, and every keeper stores its record behind the keepers of the
+// lower lanes: the list's order is the order in which the waves arrive, which no reader depends on
+// (see above).  The list has room for the whole log, so it cannot overflow; the store is guarded all
+// the same.
+__global__ __launch_bounds__(kStateThreads) void dt_foreign_live_kernel(const mcs_foreign_rec* __restrict__ flog,
+                                                                        uint32_t n_foreign, uint32_t t_first,
+                                                                        uint32_t t_last,
+                                                                        mcs_foreign_rec* __restrict__ live,
+                                                                        uint32_t* __restrict__ live_n) {
+    const uint32_t i = blockIdx.x * kStateThreads + threadIdx.x;  // (n_foreign <= 2^32 - 2: no wrap below it)
+    const uint32_t lane = threadIdx.x & 63u;
+    mcs_foreign_rec r{};
+    bool keep = false;
+    if (i < n_foreign) {
+        r = flog[i];
+        keep = r.start_s < t_last && r.finish_s > t_first && r.start_s != r.finish_s;
+    }
+    const uint64_t km = __ballot(keep);
+    if (km == 0ull) return;  // (uniform over the wave)
+    uint32_t base = 0u;
+    if (lane == 0u) base = atomicAdd(live_n, (uint32_t)__popcll(km));
+    base = (uint32_t)__shfl((int)base, 0);
+    if (keep) {
+        const uint32_t at = base + (uint32_t)__popcll(km & ((1ull << lane) - 1ull));
+        if (at < n_foreign) live[at] = r;
     }
 }
 
@@ -1004,8 +1058,24 @@ hipError_t launch_state_series(const SeriesArgs& a, uint32_t max_n, hipStream_t 
 hipError_t launch_dt_state(const DtStateArgs& a, uint32_t max_nn, hipStream_t s) {
     if (a.s.n_clusters == 0) return hipSuccess;
     if (max_nn == 0 || max_nn > 1280u) return hipErrorInvalidValue;  // 1024 physical + 256 virtual rows: 20 KB
-    hipLaunchKernelGGL(dt_state_kernel, dim3(a.s.n_clusters), dim3(kStateThreads),
-                       2 * max_nn * sizeof(unsigned long long), s, a);
+    if (a.s.job_cnt)  // a trading session's segments
+        hipLaunchKernelGGL(dt_state_kernel<true>, dim3(a.s.n_clusters), dim3(kStateThreads),
+                           2 * max_nn * sizeof(unsigned long long), s, a);
+    else
+        hipLaunchKernelGGL(dt_state_kernel<false>, dim3(a.s.n_clusters), dim3(kStateThreads),
+                           2 * max_nn * sizeof(unsigned long long), s, a);
+    return hipGetLastError();
+}
+
+// the list of the Foreign records that can hold at a sample in [t_first, t_last]; live has room for
+// n_foreign records, *live_n is their count afterwards
+hipError_t launch_dt_foreign_live(const mcs_foreign_rec* flog, uint32_t n_foreign, uint32_t t_first, uint32_t t_last,
+                                  mcs_foreign_rec* live, uint32_t* live_n, hipStream_t s) {
+    hipError_t st = hipMemsetAsync(live_n, 0, sizeof(uint32_t), s);
+    if (st != hipSuccess || n_foreign == 0) return st;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n_foreign + kStateThreads - 1u) / kStateThreads);
+    hipLaunchKernelGGL(dt_foreign_live_kernel, dim3(blocks), dim3(kStateThreads), 0, s, flog, n_foreign, t_first,
+                       t_last, live, live_n);
     return hipGetLastError();
 }
 
@@ -1016,7 +1086,10 @@ hipError_t launch_dt_series_summary(const DtSeriesArgs& a, hipStream_t s) {
     SeriesArgs p{};
     p.s = a.d.s;
     p.summ = a.summ;
-    hipLaunchKernelGGL(series_summary_kernel<true>, dim3(a.d.s.n_clusters), dim3(kStateThreads), 0, s, p);
+    if (p.s.job_cnt)
+        hipLaunchKernelGGL((series_summary_kernel<true, true>), dim3(a.d.s.n_clusters), dim3(kStateThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(series_summary_kernel<true>, dim3(a.d.s.n_clusters), dim3(kStateThreads), 0, s, p);
     return hipGetLastError();
 }
 
@@ -1026,10 +1099,15 @@ hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStr
     if (max_nn == 0 || max_nn > 1280u) return hipErrorInvalidValue;  // a tile of at least 3 samples
     uint32_t lds = dt_series_bytes(max_nn) * kSeriesMaxTile;
     if (lds > kSeriesLds) lds = kSeriesLds;
-    hipError_t st = hipFuncSetAttribute(reinterpret_cast<const void*>(dt_series_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
+    if (!a.d.s.job_cnt && (a.live || a.live_n)) return hipErrorInvalidValue;  // the list is a session's
+    const void* fn = a.d.s.job_cnt ? reinterpret_cast<const void*>(dt_series_kernel<true>)
+                                   : reinterpret_cast<const void*>(dt_series_kernel<false>);
+    hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSeriesLds);
     if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(dt_series_kernel, dim3(a.d.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    if (a.d.s.job_cnt)
+        hipLaunchKernelGGL(dt_series_kernel<true>, dim3(a.d.s.n_clusters), dim3(kStateThreads), lds, s, a);
+    else
+        hipLaunchKernelGGL(dt_series_kernel<false>, dim3(a.d.s.n_clusters), dim3(kStateThreads), lds, s, a);
     return hipGetLastError();
 }
 

@@ -318,6 +318,11 @@ SIGNATURES = [
     ("mcs_read_virtual_node_caps", C.c_int, [vp, C.c_uint32, u32p, u32p, C.c_uint32, u32p]),
     ("mcs_approve_trade", C.c_int, [vp, C.POINTER(mcs_approve_query), C.c_uint32, i32p]),
     ("mcs_trade_session_info", C.c_int, [vp, C.POINTER(mcs_trade_session)]),
+    ("mcs_trade_session_state_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
+                                                 C.POINTER(mcs_cluster_state), C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_trade_session_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(mcs_level1_sample), C.c_uint32, C.POINTER(C.c_double)]),
 ]
 
 _lib = None

@@ -550,6 +550,32 @@ class Engine:
             first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
         return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
 
+    def trade_session_state_series(self, t0_s: int, period_s: int, n_samples: int, with_wait: bool = True,
+                                   with_time: bool = False):
+        """The Start stream of the current trading session (mcs_trade_session_state_series; policy
+        DELAY with trader, run(h), append_jobs) as its last run() left it: dtrade_state_series'
+        record at t0_s + k * period_s, k < n_samples, over the physical nodes and the virtual nodes
+        received so far.  After a finite horizon h every sample must lie below h, and is then final:
+        equal, bit for bit, to what dtrade_state_series returns after a batch run over every job the
+        session ever receives (for as long as that run reaches the second).  After a drain any
+        second is accepted.  Returns (samples, wait, first) as dtrade_state_series does; with_time
+        adds the kernel ms.  MCSError (MCS_E_STATE) without a trading session, after rewind() until
+        the next run, after the session failed, after jobs appended behind a drain and after a log
+        or virtual-node overflow."""
+        for v in (t0_s, period_s, n_samples):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s, period_s and n_samples are uint32")
+        n = self.num_clusters
+        samples = np.zeros((n, max(int(n_samples), 0)), CLUSTER_SAMPLE_DTYPE)
+        wait = np.zeros((n, max(int(n_samples), 0)), WAIT_SAMPLE_DTYPE) if with_wait else None
+        first = np.zeros(n, CLUSTER_STATE_DTYPE)
+        ms = C.c_double(0.0)
+        self._c(L.lib().mcs_trade_session_state_series(
+            self._h, int(t0_s), int(period_s), int(n_samples), samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None,
+            first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
+        return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
+
     def stream_open(self, t0_s: int, period_s: int, with_wait: Optional[bool] = None):
         """mcs_stream_open: subscribe to the current online session at the cadence t0_s + k * period_s.
         with_wait None: the wait statistics under DELAY, none under FIFO.  One stream per engine; it
@@ -616,6 +642,12 @@ class Engine:
         (mcs_online_level1_series), under online_state_series' rules: after a finite horizon every
         sample lies below it and is final; after a drain any second is accepted."""
         return self._level1(L.lib().mcs_online_level1_series, t0_s, period_s, n_samples, with_time)
+
+    def trade_session_level1_series(self, t0_s: int, period_s: int, n_samples: int, with_time: bool = False):
+        """level1_series of the current trading session as its last run() left it
+        (mcs_trade_session_level1_series), under trade_session_state_series' rules: after a finite
+        horizon every sample lies below it and is final; after a drain any second is accepted."""
+        return self._level1(L.lib().mcs_trade_session_level1_series, t0_s, period_s, n_samples, with_time)
 
     def level1_at(self, cluster: int, t_s: int, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
         """ProvideJobs at one second (mcs_read_level1): the rows of Level1 of `cluster` after the Delay
