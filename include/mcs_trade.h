@@ -247,7 +247,8 @@ int mcs_dtrade_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, u
  * batch runs and plain sessions (mcs_dtrade_state_series, mcs_level1_series, mcs_read_level1,
  * mcs_online_state_series, mcs_online_level1_series, mcs_stream_open, mcs_cluster_states,
  * mcs_cluster_state_series, mcs_wait_time_series): a trading session's Start stream is read with
- * mcs_trade_session_state_series and mcs_trade_session_level1_series below. */
+ * mcs_trade_session_state_series and mcs_trade_session_level1_series below, and subscribed to with
+ * mcs_trade_stream_open / next / close. */
 typedef struct mcs_trade_session {
     uint32_t t_horizon;      /* last finite horizon (0: none yet)                                      */
     uint32_t t_last;         /* last executed tick                                                     */
@@ -282,8 +283,9 @@ int mcs_trade_session_info(mcs_engine* eng, mcs_trade_session* out);
  * grows with the session's age, is compacted per call to the records that can hold at one of the call's
  * samples once the log and the call are long enough for that to pay; MCS_DT_FOREIGN_FILTER in the
  * environment at mcs_create forces the choice (0: the log is scanned as it is; any other value: always
- * compacted; A/B runs and tests; the bytes are equal).  Not available: a cursor (mcs_stream_*),
- * mcs_read_level1, sharded engines. */
+ * compacted; A/B runs and tests; the bytes are equal).  A subscriber that wants each decided sample
+ * once, at a cost that does not grow with the session's age, uses the cursor below
+ * (mcs_trade_stream_open / next / close).  Not available: mcs_read_level1, sharded engines. */
 int mcs_trade_session_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                                    mcs_cluster_sample* out, mcs_wait_sample* wait, mcs_cluster_state* first,
                                    uint32_t n_clusters, double* kernel_ms);
@@ -291,6 +293,51 @@ int mcs_trade_session_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t peri
  * trading session's rows, under the frontier and the refusals of mcs_trade_session_state_series. */
 int mcs_trade_session_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                                     mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms);
+
+/* A cursor on the Start stream of a trading session (DESIGN.md §14 "A cursor on a trading session's Start
+ * stream"): mcs_stream_open / next / close (mcs.h) for a trading session.  mcs_trade_stream_next writes
+ * the samples t_next + k * period_s below the frontier F* that it has not handed out yet, at most
+ * max_samples of them, each bit for bit what mcs_trade_session_state_series returns for that second on the
+ * same session at that moment (and therefore final).  Layout, argument checks and `pending` are
+ * mcs_stream_next's: out (and wait, given exactly when the stream was opened with_wait) hold n_clusters
+ * rows of max_samples columns, of which the first n_written are filled; n_clusters must equal
+ * mcs_num_clusters.  Between calls the engine keeps, per batch of 256 rows, a flag word, the summary pair
+ * and the sum of start - arrival, per row the wait record (with_wait), per cluster the carries, and the
+ * list of the Foreign records that can still hold: the cost of a call follows the slice, the jobs still
+ * alive and the Foreign jobs still holding, not the session's age.
+ *   The frontier.  The lock-step clock is common to all clusters and appended arrivals must lie above the
+ * last executed tick, so a drain that ends at tick T_d decides exactly as mcs_run(T_d + 1) would.
+ * F* = max over the session's runs of (a finite horizon h; after a drain, t_last + 1); it never decreases.
+ * A drain does not close the stream, nor does the first mcs_run after it, and samples below F* stay
+ * servable after jobs were appended behind a drain and before the next run (where
+ * mcs_trade_session_state_series refuses).
+ *   Restarts.  A capacity escalation that replays the session from t = 0 inside mcs_run
+ * (mcs_trade_session.restarts) does not close the stream: it keeps t_next, drops everything it kept, and
+ * the next call that writes samples rebuilds once (rebuilt = 1; rows_retired starts again from 0).
+ *   Closing.  mcs_rewind and any other restart of the session by the caller, mcs_submit_jobs,
+ * mcs_generate_jobs, mcs_load_clusters, a run that failed (MCS_E_CAPACITY), a run whose flags carry a
+ * Foreign-log, contract-log or virtual-node overflow, and a device error close the stream:
+ * mcs_trade_stream_next then returns MCS_E_STATE, mcs_last_error names the cause, and the caller reopens.
+ * A segment relayout by mcs_append_jobs does not close it.  One stream per engine; t0_s may lie far below
+ * the frontier, and the first call then catches up once.  MCS_E_STATE without a trading session (a session
+ * without trading subscribes with mcs_stream_open, which keeps refusing a trading session).  Level1
+ * samples are not part of a cursor (mcs_trade_session_level1_series), nor is the record at t0_s. */
+typedef struct mcs_trade_stream_stats {
+    uint32_t n_written, t_first, t_next, pending; /* as mcs_stream_stats                                  */
+    uint64_t rows_scanned, rows_retired;          /* as mcs_stream_stats, counted on the device           */
+    uint32_t foreign_scanned; /* Foreign-log records this call read from the log (new since the last call
+                                 that wrote samples)                                                      */
+    uint32_t foreign_live;    /* records on the kept list that this call's tiles scanned                  */
+    uint32_t rebuilt;         /* 1: this call rebuilt the kept state from the session (the first call that
+                                 writes samples; after a replay)                                          */
+    uint32_t frontier;        /* F*                                                                       */
+    double kernel_ms;
+} mcs_trade_stream_stats;
+int mcs_trade_stream_open(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t with_wait);
+int mcs_trade_stream_next(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sample* out,
+                          mcs_wait_sample* wait /* NULL unless with_wait */, uint32_t n_clusters,
+                          mcs_trade_stream_stats* stats /* may be NULL */);
+int mcs_trade_stream_close(mcs_engine* eng);
 
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,

@@ -455,6 +455,25 @@ void dtrade_session_reset(mcs_engine* e) {
     e->ts_ticks_last = e->ts_ticks_total = e->ts_restarts = 0u;
 }
 
+bool dtrade_stream_view(mcs_engine* e, DtStreamView* v) {
+    const DtradeDev* d = e->dtd;
+    if (!d) return false;
+    static_assert(sizeof(DtCluster) % sizeof(uint32_t) == 0, "nv is read with a word stride");
+    v->vcap = d->vcap;
+    v->flog = d->foreign;
+    v->nv_src = &d->cl->nv;
+    v->nv_stride = (uint32_t)(sizeof(DtCluster) / sizeof(uint32_t));
+    v->V = d->a.V;
+    v->flags = d->h_ctl->flags;
+    v->n_foreign = d->h_ctl->n_foreign;
+    v->foreign_cap = d->a.foreign_cap;
+    v->n_trades = d->h_ctl->n_trades;
+    v->trade_cap = d->a.trade_cap;
+    return true;
+}
+
+static int dtrade_session_run_body(mcs_engine* e, uint32_t t_hor, mcs_stats* stats);
+
 int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     if (e->world != 1 || e->comm)
         return fail(e, MCS_E_STATE, "a trading session runs on one engine that holds the whole system (rank 0 of "
@@ -471,6 +490,13 @@ int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     if (t_hor != MCS_TIME_NONE && (uint64_t)t_hor > (uint64_t)t_max + 1u)
         return fail(e, MCS_E_INVALID, "the horizon lies above t_max_s + 1 = " + std::to_string((uint64_t)t_max + 1u) +
                                           ": cfg.t_max_s bounds the lock-step clock");
+    // (a call refused above executed nothing: an open stream stays as it is)
+    const int st = dtrade_session_run_body(e, t_hor, stats);
+    trade_stream_run_end(e, t_hor, st);
+    return st;
+}
+
+static int dtrade_session_run_body(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     const auto w0 = std::chrono::steady_clock::now();
     e->on_series_ok = false;  // until this run has ended well (mcs_trade_session_state_series)
     uint32_t escalations = 0;
@@ -513,6 +539,7 @@ int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
         e->dt_vnodes = nv;
         ++escalations;
         ++e->ts_restarts;
+        trade_stream_restart(e);  // (an open stream keeps t_next and rebuilds once)
     }
     e->dt_learn_s = e->cfg.slot_pool ? 0u : e->dtd->a.S;
     e->dt_learn_v = e->dtd->a.V;
@@ -584,7 +611,7 @@ int refuse_trade_session(mcs_engine* e, const char* call) {
     return fail(e, MCS_E_STATE, std::string(call) + " is not available in a trading session (online mode with "
                                     "MCS_POLICY_DELAY and cfg.trader): it reads batch runs and sessions without "
                                     "trading (in a trading session: mcs_trade_session_state_series, "
-                                    "mcs_trade_session_level1_series)");
+                                    "mcs_trade_session_level1_series, mcs_trade_stream_open)");
 }
 
 void dtrade_release_graphs(mcs_engine* e) {

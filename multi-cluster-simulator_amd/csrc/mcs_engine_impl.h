@@ -91,6 +91,28 @@ void stream_run_end(mcs_engine* e, uint32_t t_hor, int status);  // moves the fr
 // starts on the device, new_off the same on the host; d_job_cnt still holds the rows before the append)
 int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off,
                     const std::vector<uint64_t>& new_off);
+// what mcs_stream_open and mcs_trade_stream_open (mcs_dtrade.cpp) share: the kept arrays for the current
+// segments, nothing known yet; and their initial values again (a trading session's replay from t = 0)
+int stream_alloc_kept(mcs_engine* e, const char* call);
+int stream_reset_kept(mcs_engine* e);
+void stream_free(mcs_engine* e);
+// A trading session's stream (mcs_trade_stream_open / next / close; host in mcs_stream.cpp).  What it
+// reads of the lock-step state (mcs_dtrade.cpp): the device arrays, and the control block's counters and
+// flags as the last run's final poll left them on the host.  False: no lock-step state is allocated.
+struct DtStreamView {
+    const uint2* vcap;
+    const mcs_foreign_rec* flog;
+    const uint32_t* nv_src;  // DtCluster::nv of cluster 0 on the device
+    uint32_t nv_stride;      // 32-bit words between two clusters' nv
+    uint32_t V;
+    uint32_t flags;          // DtCtl::flags
+    uint64_t n_foreign, foreign_cap, n_trades, trade_cap;
+};
+bool dtrade_stream_view(mcs_engine* e, DtStreamView* v);
+// dtrade_session_run's hooks: a replay from t = 0 empties what the stream kept (it stays open); the end
+// of a run moves the frontier F*, or closes the stream (a failed run, an overflow in the run's flags)
+void trade_stream_restart(mcs_engine* e);
+void trade_stream_run_end(mcs_engine* e, uint32_t t_hor, int status);
 
 // Lock-step tick loops: mcs_trade_stats.loop_form
 constexpr uint32_t kLoopGraph = 0;      // one engine, ticks replayed from a captured hipGraph
@@ -244,6 +266,17 @@ struct mcs_engine {
     mcs_cluster_sample* d_st_out = nullptr;  // the call's samples on the device, st_out_cap per cluster
     mcs_wait_sample* d_st_wout = nullptr;
     uint64_t st_out_cap = 0;
+    // a trading session's stream (mcs_trade_stream_*, mcs_dtrade.cpp) shares the fields above: plain and
+    // trading sessions exclude each other.  st_h is then the frontier F* (DESIGN.md §14).
+    bool st_trade = false;             // the stream (or the one last closed) is a trading session's
+    bool st_rebuild = false;           // the kept state is empty: the next call that writes samples rebuilds it
+    uint32_t st_seen = 0;              // Foreign-log records taken so far
+    uint32_t st_fl_n = 0;              // records on the kept Foreign list
+    uint32_t st_fl_cap = 0;            // records either list has room for
+    int st_fl_cur = 0;                 // which list is the kept one
+    mcs_foreign_rec* d_st_fl[2] = {nullptr, nullptr};
+    uint32_t* d_st_fl_n = nullptr;     // the new list's length
+    uint32_t* d_st_nv = nullptr;       // [C] virtual rows of the current call
 };
 
 inline bool mcs::is_dtrade(const mcs_engine* e) { return e->cfg.policy == MCS_POLICY_DELAY && e->cfg.trader; }

@@ -243,6 +243,29 @@ hipError_t launch_dt_series_summary(const DtSeriesArgs& a, hipStream_t s);
 hipError_t launch_dt_state_series(const DtSeriesArgs& a, uint32_t max_nn, hipStream_t s);
 hipError_t launch_dt_foreign_live(const mcs_foreign_rec* flog, uint32_t n_foreign, uint32_t t_first, uint32_t t_last,
                                   mcs_foreign_rec* live, uint32_t* live_n, hipStream_t s);
+// The Foreign take of a trading session's stream (mcs_state.hip, dt_stream_foreign_kernel; once per
+// mcs_trade_stream_next call that writes samples): the list the call's tiles scan, built from the list
+// the last call kept (its records with finish_s > t_first) and the log records appended since, at
+// [seen, n_log) (those with start_s != finish_s and finish_s > t_first).  t_first is the call's first
+// sample second: a record holds on start_s < t < finish_s, so none with finish_s <= t_first is seen at or
+// after it.  Two lists in ping-pong, each with room for `cap` >= n_log records, so that the new one
+// cannot overflow (the store is guarded all the same).  The kernel also writes the call's row counts:
+// nv_out[c] = min(nv_src[c * nv_stride], V), the value dt_series_kernel and stream_retire_kernel read.
+struct DtStreamForeignArgs {
+    const mcs_foreign_rec* flog;
+    const mcs_foreign_rec* old_list;
+    mcs_foreign_rec* new_list;
+    uint32_t* new_n;          // zeroed by the launcher; afterwards the new list's length
+    uint32_t old_n;           // the old list's length (the host read it back after the last call)
+    uint32_t seen, n_log;     // log positions
+    uint32_t t_first;
+    uint32_t cap;             // records either list has room for
+    const uint32_t* nv_src;   // DtCluster::nv of cluster 0
+    uint32_t nv_stride;       // words between two clusters' nv
+    uint32_t V, n_clusters;
+    uint32_t* nv_out;         // [n_clusters]
+};
+hipError_t launch_dt_stream_foreign(const DtStreamForeignArgs& a, hipStream_t s);
 
 // The average wait time series of a DELAY run (mcs_wait.hip): WaitTime after the Delay iteration at
 // the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters.
@@ -292,9 +315,17 @@ struct StreamArgs {
     uint32_t chunk;            // retire: samples per chunk of the call's series launches
     uint32_t frontier;         // retire: the stream's next sample second after this call
 };
+// A trading session's stream (mcs_trade_stream_next): the TRADE instantiation of the retire kernel takes
+// the plain arguments and, behind them, per cluster the virtual rows of this call, min(nv, V), on the
+// device.  The plain kernels' parameter keeps its layout (as DtArgsCore / DtArgs).
+struct TradeStreamArgs : StreamArgs {
+    const uint32_t* nv;
+};
 hipError_t launch_stream_prep(const StreamArgs& a, hipStream_t s);    // summaries, records, final flags
 hipError_t launch_stream_accum(const StreamArgs& a, hipStream_t s);   // the live batches into wout
 hipError_t launch_stream_retire(const StreamArgs& a, hipStream_t s);  // retire against the frontier, count
+hipError_t launch_trade_stream_prep(const StreamArgs& a, hipStream_t s);  // the TRADE forms of both
+hipError_t launch_trade_stream_retire(const TradeStreamArgs& a, hipStream_t s);
 // the kept arrays after a segment relayout: cluster c's batches and rows move from the old layout
 // (old_off) to the new one (s.job_off); s.job_cnt are the rows before the append
 struct StreamMoveArgs {

@@ -34,7 +34,8 @@
 // After a DELAY trading run (mcs_dtrade_state_series) dt_state_kernel and dt_series_kernel, further
 // down, rebuild the record with virtual-node rows, Foreign jobs and 64-bit wrapping counters; in a
 // trading session (mcs_trade_session_state_series) their SEG instantiations do, behind
-// dt_foreign_live_kernel's per-call compaction of the Foreign log.
+// dt_foreign_live_kernel's per-call compaction of the Foreign log.  A trading session's cursor
+// (mcs_trade_stream_next) keeps that list between calls: dt_stream_foreign_kernel.
 //
 // In an online session (mcs_online_state_series) the kernels are the SEG instantiations
 // of the plain code: a cluster's rows are the first job_cnt[c] of the segment at job_off[c], and its
@@ -856,6 +857,41 @@ __global__ __launch_bounds__(kStateThreads) void dt_foreign_live_kernel(const mc
     }
 }
 
+// The Foreign take of a trading session's stream (mcs_trade_stream_next): the same
+// compaction over two sources, one record per thread: thread i < old_n takes record i of the list the
+// last call kept and keeps it while finish_s > t_first; the threads behind them take the log records
+// appended since, [seen, n_log), and keep those with a window that is not empty and finish_s > t_first.
+// Retiring is lazy: a record is dropped by the first call whose first sample it can no longer reach.
+// Workgroup 0 also writes the call's virtual row counts from the session's cluster records.
+__global__ __launch_bounds__(kStateThreads) void dt_stream_foreign_kernel(DtStreamForeignArgs a) {
+    const uint32_t i = blockIdx.x * kStateThreads + threadIdx.x;  // (old_n + n_log - seen <= n_log <= 2^32 - 2)
+    const uint32_t lane = threadIdx.x & 63u;
+    if (blockIdx.x == 0u)
+        for (uint32_t c = threadIdx.x; c < a.n_clusters; c += kStateThreads) {
+            const uint32_t nv = a.nv_src[(size_t)c * a.nv_stride];
+            a.nv_out[c] = nv < a.V ? nv : a.V;
+        }
+    const uint32_t n_new = a.n_log - a.seen;
+    mcs_foreign_rec r{};
+    bool keep = false;
+    if (i < a.old_n) {
+        r = a.old_list[i];
+        keep = r.finish_s > a.t_first;
+    } else if (i - a.old_n < n_new) {
+        r = a.flog[a.seen + (i - a.old_n)];
+        keep = r.start_s != r.finish_s && r.finish_s > a.t_first;
+    }
+    const uint64_t km = __ballot(keep);
+    if (km == 0ull) return;  // (uniform over the wave)
+    uint32_t base = 0u;
+    if (lane == 0u) base = atomicAdd(a.new_n, (uint32_t)__popcll(km));
+    base = (uint32_t)__shfl((int)base, 0);
+    if (keep) {
+        const uint32_t at = base + (uint32_t)__popcll(km & ((1ull << lane) - 1ull));
+        if (at < a.cap) a.new_list[at] = r;
+    }
+}
+
 // ---- the pre-pass over a FIFO trading run's lent log ---------------------------------------------
 //
 // The log is in execution order (starts ascend), every lender's records interleaved.  A counting
@@ -1076,6 +1112,20 @@ hipError_t launch_dt_foreign_live(const mcs_foreign_rec* flog, uint32_t n_foreig
     const uint32_t blocks = (uint32_t)(((uint64_t)n_foreign + kStateThreads - 1u) / kStateThreads);
     hipLaunchKernelGGL(dt_foreign_live_kernel, dim3(blocks), dim3(kStateThreads), 0, s, flog, n_foreign, t_first,
                        t_last, live, live_n);
+    return hipGetLastError();
+}
+
+hipError_t launch_dt_stream_foreign(const DtStreamForeignArgs& a, hipStream_t s) {
+    // every index the kernel forms stays inside its array: the old list and the log within their lengths,
+    // the new list within cap
+    if (a.seen > a.n_log || a.old_n > a.seen || a.n_log > a.cap || !a.new_n || !a.nv_out || !a.nv_src)
+        return hipErrorInvalidValue;
+    if ((a.old_n && !a.old_list) || (a.n_log && (!a.flog || !a.new_list))) return hipErrorInvalidValue;
+    hipError_t st = hipMemsetAsync(a.new_n, 0, sizeof(uint32_t), s);
+    if (st != hipSuccess) return st;
+    const uint64_t n = (uint64_t)a.old_n + (a.n_log - a.seen);
+    const uint32_t blocks = n ? (uint32_t)((n + kStateThreads - 1u) / kStateThreads) : 1u;  // (workgroup 0 writes nv_out)
+    hipLaunchKernelGGL(dt_stream_foreign_kernel, dim3(blocks), dim3(kStateThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -5,6 +5,9 @@
 // sum of s - a (indexed as the series summaries are: by segment start, over segment capacity), per row
 // the wait record (a stream with wait statistics), per cluster a StreamCluster.  They are freed when
 // the stream closes and at destroy, and follow the segments through a relayout (stream_relayout).
+// A trading session's cursor (mcs_trade_stream_open / next / close, mcs_trade.h) shares all of it, since
+// plain and trading sessions exclude each other, and adds the two Foreign lists, the log position and
+// the row counts of the current call; its frontier F* and its hooks in dtrade_session_run are below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,7 +18,6 @@
 #include "mcs_internal.h"
 
 namespace mcs {
-namespace {
 
 void stream_free(mcs_engine* e) {
     dfree(e->d_st_cl);
@@ -26,9 +28,16 @@ void stream_free(mcs_engine* e) {
     dfree(e->d_st_tot);
     dfree(e->d_st_out);
     dfree(e->d_st_wout);
+    dfree(e->d_st_fl[0]);
+    dfree(e->d_st_fl[1]);
+    dfree(e->d_st_fl_n);
+    dfree(e->d_st_nv);
+    e->st_fl_cap = e->st_fl_n = e->st_seen = 0;
     e->st_out_cap = 0;
     e->st_open = false;
 }
+
+namespace {
 
 // the kept arrays for the segment layout `off` (capacity off[C]); the flags start at 0: nothing known
 int stream_alloc(mcs_engine* e, const std::vector<uint64_t>& off, uint32_t** flags, uint2** summ,
@@ -43,6 +52,30 @@ int stream_alloc(mcs_engine* e, const std::vector<uint64_t>& off, uint32_t** fla
 }
 
 }  // namespace
+
+int stream_reset_kept(mcs_engine* e) {
+    const size_t C = e->C ? e->C : 1;
+    const size_t nbat = series_summ_size(e->job_off[e->C], e->C);
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemset(e->d_st_flags, 0, nbat * sizeof(uint32_t)));
+    HIPCHK(e, hipMemset(e->d_st_tot, 0, 2 * sizeof(unsigned long long)));
+    std::vector<StreamCluster> cl(C, StreamCluster{-1, 0ull, 0u, 0u});
+    HIPCHK(e, hipMemcpy(e->d_st_cl, cl.data(), C * sizeof(StreamCluster), hipMemcpyHostToDevice));
+    e->st_retired = 0;
+    return MCS_OK;
+}
+
+int stream_alloc_kept(mcs_engine* e, const char* call) {
+    int rc = stream_alloc(e, e->job_off, &e->d_st_flags, &e->d_st_summ, &e->d_st_bsum, &e->d_st_rec);
+    const size_t C = e->C ? e->C : 1;
+    hipError_t st = hipSuccess;
+    if (rc == MCS_OK) st = hipMalloc(&e->d_st_cl, C * sizeof(StreamCluster));
+    if (rc == MCS_OK && st == hipSuccess) st = hipMalloc(&e->d_st_tot, 2 * sizeof(unsigned long long));
+    if (rc == MCS_OK && st != hipSuccess) rc = fail(e, MCS_E_HIP, std::string(call) + ": " + hipGetErrorString(st));
+    if (rc == MCS_OK) rc = stream_reset_kept(e);
+    if (rc != MCS_OK) stream_free(e);
+    return rc;
+}
 
 void stream_shut(mcs_engine* e, const char* cause) {
     if (!e->st_open) return;
@@ -67,6 +100,50 @@ void stream_run_end(mcs_engine* e, uint32_t t_hor, int status) {
         e->st_drained = true;  // the frontier stays at the last finite horizon
     else
         e->st_h = t_hor;
+}
+
+// ---- a trading session's stream: the frontier F* and the replay --------------------
+//
+// The lock-step clock is common to all clusters and appended arrivals lie above the last executed tick,
+// so a drain that ends at tick T_d decides exactly as mcs_run(T_d + 1) would: F* is the largest of the
+// session's finite horizons and, where a tick has been executed, t_last + 1.  It never decreases.
+static uint32_t trade_frontier(const mcs_engine* e) {
+    if (!e->has_run) return 0u;
+    return std::max(e->on_t_hor, e->ts_ticks_total ? e->ts_t_last + 1u : 0u);
+}
+
+void trade_stream_restart(mcs_engine* e) {
+    if (!e->st_open || !e->st_trade) return;
+    // nothing is proved about the kept state across a replay: it is dropped and rebuilt once
+    if (stream_reset_kept(e) != MCS_OK) {
+        const std::string msg = e->err;
+        stream_shut(e, "a replay of the session whose reset of the kept state failed");
+        e->err = msg;
+        return;
+    }
+    e->st_seen = 0;
+    e->st_fl_n = 0;
+    e->st_rebuild = true;
+}
+
+void trade_stream_run_end(mcs_engine* e, uint32_t t_hor, int status) {
+    (void)t_hor;
+    e->on_run_failed = status != MCS_OK;
+    if (!e->st_open || !e->st_trade) return;
+    if (status != MCS_OK) {
+        stream_shut(e, "an mcs_run that failed");
+        return;
+    }
+    DtStreamView v{};
+    if (!dtrade_stream_view(e, &v)) return;
+    // (a slot-pool or virtual-node overflow never ends a run well: dtrade_session_run escalates and replays,
+    // or fails with MCS_E_CAPACITY, which the branch above closes on)
+    if ((v.flags & MCS_FLAG_LOG_OVERFLOW) || v.n_foreign > v.foreign_cap || v.n_trades > v.trade_cap) {
+        stream_shut(e, "an mcs_run whose Foreign or contract log overflowed (MCS_FLAG_LOG_OVERFLOW): records "
+                       "were dropped");
+        return;
+    }
+    e->st_h = std::max(e->st_h, trade_frontier(e));
 }
 
 int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_new_off,
@@ -135,23 +212,8 @@ int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t wi
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->st_wait = with_wait != 0;
     e->st_cause.clear();
-    int rc = mcs::stream_alloc(e, e->job_off, &e->d_st_flags, &e->d_st_summ, &e->d_st_bsum, &e->d_st_rec);
-    const size_t C = e->C ? e->C : 1;
-    hipError_t st = hipSuccess;
-    if (rc == MCS_OK) st = hipMalloc(&e->d_st_cl, C * sizeof(mcs::StreamCluster));
-    if (rc == MCS_OK && st == hipSuccess) st = hipMalloc(&e->d_st_tot, 2 * sizeof(unsigned long long));
-    if (rc == MCS_OK && st == hipSuccess) st = hipMemset(e->d_st_tot, 0, 2 * sizeof(unsigned long long));
-    if (rc == MCS_OK && st == hipSuccess) {
-        std::vector<mcs::StreamCluster> cl(C, mcs::StreamCluster{-1, 0ull, 0u, 0u});
-        st = hipMemcpy(e->d_st_cl, cl.data(), C * sizeof(mcs::StreamCluster), hipMemcpyHostToDevice);
-    }
-    if (rc == MCS_OK && st == hipSuccess) st = hipStreamSynchronize(e->stream);
-    if (rc == MCS_OK && st != hipSuccess)
-        rc = fail(e, MCS_E_HIP, std::string("mcs_stream_open: ") + hipGetErrorString(st));
-    if (rc != MCS_OK) {
-        mcs::stream_free(e);
-        return rc;
-    }
+    e->st_trade = false;
+    if (int rc = mcs::stream_alloc_kept(e, "mcs_stream_open")) return rc;
     e->st_open = true;
     e->st_period = period_s;
     e->st_next = t0_s;
@@ -161,14 +223,15 @@ int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t wi
     return MCS_OK;
 }
 
-int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
-                    uint32_t n_clusters, mcs_stream_stats* stats) {
-    if (int st = check_engine(e)) return st;
-    if (stats) *stats = mcs_stream_stats{};
-    if (!e->st_open) {
-        if (e->st_cause.empty()) return fail(e, MCS_E_STATE, "no stream is open (mcs_stream_open)");
-        return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_stream_open)");
-    }
+}  // extern "C"
+
+// The body of mcs_stream_next and mcs_trade_stream_next behind their state checks.  A trading session's
+// call differs in three places: the Foreign take before the prep kernel, dt_series_kernel over the kept
+// summaries and the kept Foreign list in place of series_kernel, and the TRADE instantiations of the prep
+// and the retire kernel (StreamArgs::nv).
+static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs_cluster_sample* out,
+                            mcs_wait_sample* wait, uint32_t n_clusters, mcs_trade_stream_stats* stats) {
+    const std::string call = trade ? "mcs_trade_stream_next" : "mcs_stream_next";
     if (n_clusters != e->C)
         return fail(e, MCS_E_INVALID, "n_clusters must equal mcs_num_clusters: the frontier is common to all clusters");
     if (!out || max_samples == 0) return fail(e, MCS_E_INVALID, "bad output");
@@ -209,7 +272,54 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
         if (e->st_wait) HIPCHK(e, hipMalloc(&e->d_st_wout, (size_t)n_clusters * cap * sizeof(mcs_wait_sample)));
         e->st_out_cap = cap;
     }
-    mcs::StreamArgs a{};
+    mcs::DtStreamView v{};
+    mcs::DtStreamForeignArgs fa{};
+    uint32_t n_log = 0;
+    const bool rebuilt = trade && e->st_rebuild;
+    if (trade) {
+        if (!mcs::dtrade_stream_view(e, &v))
+            return fail(e, MCS_E_STATE, call + ": the trading session holds no lock-step state (mcs_run first)");
+        if (v.n_foreign > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "more than 2^32 - 2 Foreign jobs");
+        n_log = (uint32_t)std::min<uint64_t>(v.n_foreign, v.foreign_cap);
+        if (!e->d_st_nv) HIPCHK(e, hipMalloc(&e->d_st_nv, (size_t)n_clusters * sizeof(uint32_t)));
+        if (!e->d_st_fl_n) HIPCHK(e, hipMalloc(&e->d_st_fl_n, sizeof(uint32_t)));
+        if (e->st_fl_cap < n_log || !e->d_st_fl[0]) {  // both lists hold the log as it stands: no overflow
+            const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(2ull * n_log, 1024), std::max<uint64_t>(v.foreign_cap, 1));
+            mcs_foreign_rec* nl[2] = {nullptr, nullptr};
+            hipError_t gs = hipMalloc(&nl[0], (size_t)cap * sizeof(mcs_foreign_rec));
+            if (gs == hipSuccess) gs = hipMalloc(&nl[1], (size_t)cap * sizeof(mcs_foreign_rec));
+            if (gs == hipSuccess && e->st_fl_n)  // the kept list moves to the larger buffer
+                gs = hipMemcpy(nl[0], e->d_st_fl[e->st_fl_cur], (size_t)e->st_fl_n * sizeof(mcs_foreign_rec),
+                               hipMemcpyDeviceToDevice);
+            if (gs != hipSuccess) {  // (the stream stays as it was: the kept list is untouched)
+                dfree(nl[0]);
+                dfree(nl[1]);
+                return fail(e, MCS_E_HIP, call + ": growing the Foreign lists: " + hipGetErrorString(gs));
+            }
+            dfree(e->d_st_fl[0]);
+            dfree(e->d_st_fl[1]);
+            e->d_st_fl[0] = nl[0];
+            e->d_st_fl[1] = nl[1];
+            e->st_fl_cur = 0;
+            e->st_fl_cap = (uint32_t)cap;
+        }
+        fa.flog = v.flog;
+        fa.old_list = e->d_st_fl[e->st_fl_cur];
+        fa.new_list = e->d_st_fl[e->st_fl_cur ^ 1];
+        fa.new_n = e->d_st_fl_n;
+        fa.old_n = e->st_fl_n;
+        fa.seen = e->st_seen;
+        fa.n_log = n_log;
+        fa.t_first = t0;
+        fa.cap = e->st_fl_cap;
+        fa.nv_src = v.nv_src;
+        fa.nv_stride = v.nv_stride;
+        fa.V = v.V;
+        fa.n_clusters = n_clusters;
+        fa.nv_out = e->d_st_nv;
+    }
+    mcs::TradeStreamArgs a{};  // (a plain session's launches take its StreamArgs part)
+    a.nv = trade ? e->d_st_nv : nullptr;
     a.s.node_off = e->d_node_off;
     a.s.cap = e->d_cap;
     a.s.free0 = e->d_free0;
@@ -238,6 +348,25 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
     sa.out = e->d_st_out;
     sa.period = period;
     sa.magic = period > 1 ? ~0ull / period + 1ull : 0ull;
+    mcs::DtSeriesArgs da{};
+    uint32_t max_nn = 1;
+    if (trade) {
+        da.d.s = a.s;
+        da.d.vcap = v.vcap;
+        da.d.nv = e->d_st_nv;
+        da.d.flog = v.flog;
+        da.d.n_foreign = n_log;  // bounds the list's length as the kernel reads it
+        da.d.V = v.V;
+        da.summ = e->d_st_summ;
+        da.out = e->d_st_out;
+        da.period = period;
+        da.magic = sa.magic;
+        da.live = fa.new_list;
+        da.live_n = e->d_st_fl_n;
+        // the LDS a launch asks for: the widest cluster the session can hold (the kernel cuts its tiles
+        // by the rows the device's nv gives, which need no more)
+        max_nn = std::min<uint32_t>(std::max<uint32_t>(e->max_n, 1u) + v.V, 1280u);
+    }
     mcs::WaitArgs wa{};
     wa.jobs = e->d_jobs;
     wa.job_off = e->d_job_off;
@@ -255,11 +384,14 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
     for (uint64_t k0 = 0; st == hipSuccess && k0 < n; k0 += chunk) {
         const uint32_t nk = (uint32_t)(n - k0 < chunk ? n - k0 : chunk);
         const bool last = k0 + nk == n;
-        a.t0 = sa.t0 = wa.t0 = (uint32_t)(t0 + k0 * period);
-        a.n_samples = sa.n_samples = wa.n_samples = nk;
+        a.t0 = sa.t0 = wa.t0 = da.t0 = (uint32_t)(t0 + k0 * period);
+        a.n_samples = sa.n_samples = wa.n_samples = da.n_samples = nk;
         st = hipEventRecord(e->ev0, e->stream);
-        if (st == hipSuccess && k0 == 0) st = mcs::launch_stream_prep(a, e->stream);
-        if (st == hipSuccess) st = mcs::launch_state_series(sa, e->max_n ? e->max_n : 1, e->stream);
+        if (st == hipSuccess && k0 == 0 && trade) st = mcs::launch_dt_stream_foreign(fa, e->stream);
+        if (st == hipSuccess && k0 == 0)
+            st = trade ? mcs::launch_trade_stream_prep(a, e->stream) : mcs::launch_stream_prep(a, e->stream);
+        if (st == hipSuccess && trade) st = mcs::launch_dt_state_series(da, max_nn, e->stream);
+        if (st == hipSuccess && !trade) st = mcs::launch_state_series(sa, e->max_n ? e->max_n : 1, e->stream);
         if (st == hipSuccess && e->st_wait) {
             st = hipMemsetAsync(e->d_st_wout, 0, (size_t)n_clusters * nk * sizeof(mcs_wait_sample), e->stream);
             if (st == hipSuccess) st = mcs::launch_stream_accum(a, e->stream);
@@ -268,7 +400,7 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
         if (st == hipSuccess && last) {  // the whole call's samples against the new frontier
             a.t0 = t0;
             a.n_samples = n;
-            st = mcs::launch_stream_retire(a, e->stream);
+            st = trade ? mcs::launch_trade_stream_retire(a, e->stream) : mcs::launch_stream_retire(a, e->stream);
         }
         if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
         if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
@@ -285,15 +417,28 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
                              hipMemcpyDeviceToHost);
     }
     if (st == hipSuccess) st = hipMemcpy(tot, e->d_st_tot, sizeof(tot), hipMemcpyDeviceToHost);
+    uint32_t fl_n = 0;
+    if (st == hipSuccess && trade) st = hipMemcpy(&fl_n, e->d_st_fl_n, sizeof(fl_n), hipMemcpyDeviceToHost);
     if (st != hipSuccess) {
-        const int rc = fail(e, MCS_E_HIP, std::string("mcs_stream_next: ") + hipGetErrorString(st));
+        const int rc = fail(e, MCS_E_HIP, call + ": " + hipGetErrorString(st));
         const std::string msg = e->err;
-        mcs::stream_shut(e, "a device error in mcs_stream_next");
+        mcs::stream_shut(e, trade ? "a device error in mcs_trade_stream_next" : "a device error in mcs_stream_next");
         e->err = msg;
         return rc;
     }
     e->st_next = a.frontier;
     e->st_retired = tot[1];
+    if (trade) {  // the new list is the kept one; the log is taken up to n_log
+        e->st_fl_cur ^= 1;
+        e->st_fl_n = std::min(fl_n, e->st_fl_cap);
+        e->st_rebuild = false;
+        if (stats) {
+            stats->foreign_scanned = n_log - e->st_seen;
+            stats->foreign_live = e->st_fl_n;
+            stats->rebuilt = rebuilt ? 1u : 0u;
+        }
+        e->st_seen = n_log;
+    }
     if (stats) {
         stats->rows_scanned = tot[0];
         stats->rows_retired = tot[1];
@@ -302,14 +447,118 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
     return MCS_OK;
 }
 
+extern "C" {
+
+int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
+                    uint32_t n_clusters, mcs_stream_stats* stats) {
+    if (int st = check_engine(e)) return st;
+    if (stats) *stats = mcs_stream_stats{};
+    if (e->st_trade && (e->st_open || !e->st_cause.empty()))
+        return fail(e, MCS_E_STATE, "the engine's stream is a trading session's (mcs_trade_stream_next, "
+                                    "mcs_trade_stream_close)");
+    if (!e->st_open) {
+        if (e->st_cause.empty()) return fail(e, MCS_E_STATE, "no stream is open (mcs_stream_open)");
+        return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_stream_open)");
+    }
+    mcs_trade_stream_stats ts{};
+    const int rc = stream_next_impl(e, false, max_samples, out, wait, n_clusters, &ts);
+    if (stats) {
+        stats->n_written = ts.n_written;
+        stats->t_first = ts.t_first;
+        stats->t_next = ts.t_next;
+        stats->pending = ts.pending;
+        stats->rows_scanned = ts.rows_scanned;
+        stats->rows_retired = ts.rows_retired;
+        stats->kernel_ms = ts.kernel_ms;
+    }
+    return rc;
+}
+
 int mcs_stream_close(mcs_engine* e) {
     if (int st = check_engine(e)) return st;
+    if (e->st_trade && (e->st_open || !e->st_cause.empty()))
+        return fail(e, MCS_E_STATE, "the engine's stream is a trading session's (mcs_trade_stream_close)");
     if (!e->st_open) {
         if (e->st_cause.empty()) return fail(e, MCS_E_STATE, "no stream is open");
         e->st_cause.clear();  // closed by the engine already: acknowledged
         return MCS_OK;
     }
     mcs::stream_shut(e, "mcs_stream_close");
+    e->st_cause.clear();
+    return MCS_OK;
+}
+
+// ---- the cursor of a trading session (mcs_trade.h) ----------------------------------
+
+static int no_trade_session(mcs_engine* e, const char* call) {
+    return fail(e, MCS_E_STATE, std::string(call) + " subscribes to a trading session (online mode with "
+                                    "MCS_POLICY_DELAY and cfg.trader: mcs_run with a horizon, mcs_append_jobs); "
+                                    "there is no trading session (in a session without trading: mcs_stream_open)");
+}
+
+int mcs_trade_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    if (!mcs::is_trade_session(e)) return no_trade_session(e, "mcs_trade_stream_open");
+    if (e->st_open)
+        return fail(e, MCS_E_STATE, "a stream is open already: one stream per engine (mcs_trade_stream_close)");
+    if (e->ts_failed)
+        return fail(e, MCS_E_STATE, "mcs_trade_stream_open: the trading session failed (capacity exhausted, "
+                                    "MCS_E_CAPACITY): mcs_rewind or submit again, then run");
+    if (e->on_run_failed)
+        return fail(e, MCS_E_STATE, "the session's last mcs_run failed: its rows are not a decided prefix (mcs_rewind)");
+    mcs::DtStreamView v{};
+    if (e->has_run && mcs::dtrade_stream_view(e, &v)) {  // the cases in which the series call refuses
+        if (v.flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))
+            return fail(e, MCS_E_STATE, "mcs_trade_stream_open: the session's last run was cut short by a slot-pool "
+                                        "or virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW)");
+        if ((v.flags & MCS_FLAG_LOG_OVERFLOW) || v.n_foreign > v.foreign_cap || v.n_trades > v.trade_cap)
+            return fail(e, MCS_E_STATE, "mcs_trade_stream_open: the session's Foreign or contract log overflowed "
+                                        "(MCS_FLAG_LOG_OVERFLOW): records were dropped");
+    }
+    if (period_s == 0) return fail(e, MCS_E_INVALID, "period_s must be positive");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->st_wait = with_wait != 0;
+    e->st_cause.clear();
+    e->st_trade = true;
+    if (int rc = mcs::stream_alloc_kept(e, "mcs_trade_stream_open")) return rc;
+    e->st_open = true;
+    e->st_period = period_s;
+    e->st_next = t0_s;
+    e->st_h = mcs::trade_frontier(e);
+    e->st_drained = false;
+    e->st_retired = 0;
+    e->st_seen = e->st_fl_n = 0;
+    e->st_fl_cur = 0;
+    e->st_rebuild = true;  // the first call that writes samples builds the kept state
+    return MCS_OK;
+}
+
+int mcs_trade_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
+                          uint32_t n_clusters, mcs_trade_stream_stats* stats) {
+    if (int st = check_engine(e)) return st;
+    if (stats) *stats = mcs_trade_stream_stats{};
+    if (!mcs::is_trade_session(e) && !(e->st_trade && !e->st_cause.empty()))
+        return no_trade_session(e, "mcs_trade_stream_next");
+    if (!e->st_open || !e->st_trade) {
+        if (e->st_cause.empty() || !e->st_trade)
+            return fail(e, MCS_E_STATE, "no stream is open (mcs_trade_stream_open)");
+        return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_trade_stream_open)");
+    }
+    const int rc = stream_next_impl(e, true, max_samples, out, wait, n_clusters, stats);
+    if (stats) stats->frontier = e->st_h;
+    return rc;
+}
+
+int mcs_trade_stream_close(mcs_engine* e) {
+    if (int st = check_engine(e)) return st;
+    if (!e->st_trade && e->st_open)
+        return fail(e, MCS_E_STATE, "the engine's stream is a plain session's (mcs_stream_close)");
+    if (!e->st_open) {
+        if (e->st_cause.empty() || !e->st_trade) return fail(e, MCS_E_STATE, "no stream is open");
+        e->st_cause.clear();  // closed by the engine already: acknowledged
+        return MCS_OK;
+    }
+    mcs::stream_shut(e, "mcs_trade_stream_close");
     e->st_cause.clear();
     return MCS_OK;
 }

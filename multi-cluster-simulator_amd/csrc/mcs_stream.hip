@@ -27,7 +27,13 @@
 //                         the call loaded from the flags and the summaries (series_kernel reads the
 //                         batches that its tiles hit: arrival_min <= t_last and end_max > t_first).
 // stream_move_kernel carries the kept arrays over a segment relayout.
+// A trading session's stream (mcs_trade_stream_next) runs the TRADE instantiations of the prep and the
+// retire kernel, dt_series_kernel in place of series_kernel and, before them, dt_stream_foreign_kernel
+// (mcs_state.hip): the two differences are stated at the templates.  The plain instantiations are the
+// code they were.
 // Every loop is bounded by a row, batch or sample count; no workgroup waits for another.
+#include <type_traits>
+
 #include "mcs_internal.h"
 #include "mcs_wait_dev.h"
 #include "mcs_wave.h"
@@ -39,6 +45,8 @@ namespace {
 constexpr int kStreamThreads = 256;
 static_assert(kStreamThreads == (int)kSeriesBatch, "one thread per row of a batch");
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+template <bool TRADE>
+using StreamArgsOf = std::conditional_t<TRADE, TradeStreamArgs, StreamArgs>;
 
 // The batches base + i, i < 256, below nb whose flags hold none of `mask`, in stream order: list[] (LDS,
 // 256 entries) receives their i, the count is returned.  The caller synchronises before the next call.
@@ -60,6 +68,11 @@ __device__ __forceinline__ uint32_t pick_batches(const uint32_t* __restrict__ fl
     return total;
 }
 
+// TRADE: a trading session's rows.  An own job runs on a physical node or on a virtual one (k >= N), so
+// the summary's end is the TRADE summaries' rule (launch_dt_series_summary, `apply` in dt_series_kernel):
+// the finish of every job with k >= 0.  With the plain test such a job would drop out of end_max and its
+// batch would retire while the job still holds its row.
+template <bool TRADE>
 __global__ __launch_bounds__(kStreamThreads) void stream_prep_kernel(StreamArgs a) {
     __shared__ Clamp wave_tot[kStreamThreads / kWave];
     __shared__ long long carry_s, pd_s;
@@ -104,7 +117,11 @@ __global__ __launch_bounds__(kStreamThreads) void stream_prep_kernel(StreamArgs 
                 s32 = start[i];
                 const uint32_t f = finish[i];
                 placed_w = k >= 0 && s32 != kNone;                   // wait_prep_kernel's test
-                const bool placed_s = k >= 0 && (uint32_t)k < N;     // series_summary_kernel's
+                bool placed_s;
+                if constexpr (TRADE)
+                    placed_s = k >= 0;                               // the TRADE summaries' (a DELAY run borrows nothing)
+                else
+                    placed_s = k >= 0 && (uint32_t)k < N;            // series_summary_kernel's
                 end = placed_s ? f : kNone;                          // unplaced: queued for good
                 decided = placed_w && placed_s && f != kNone;
             }
@@ -209,7 +226,10 @@ __global__ __launch_bounds__(kStreamThreads) void stream_accum_kernel(StreamArgs
     acc.flush();
 }
 
-__global__ __launch_bounds__(kStreamThreads) void stream_retire_kernel(StreamArgs a) {
+// TRADE: dt_series_kernel cuts the call into tiles of dt_series_tile(N + nv[c]) samples, nv[c] the
+// cluster's virtual rows in this call (it grows when the cluster receives a virtual node between calls).
+template <bool TRADE>
+__global__ __launch_bounds__(kStreamThreads) void stream_retire_kernel(StreamArgsOf<TRADE> a) {
     __shared__ unsigned long long s_scan, s_ret, s_ab;
     __shared__ uint32_t s_first;
     const uint32_t c = blockIdx.x;
@@ -223,7 +243,11 @@ __global__ __launch_bounds__(kStreamThreads) void stream_retire_kernel(StreamArg
     const uint2* __restrict__ summ = a.summ + bi;
     const unsigned long long* __restrict__ bsum = a.bsum + bi;
     const bool wait = a.rec != nullptr;
-    const uint32_t TS = series_tile(N);
+    uint32_t TS;
+    if constexpr (TRADE)
+        TS = dt_series_tile(N + a.nv[c]);
+    else
+        TS = series_tile(N);
     const StreamCluster st = a.cl[c];
     if (tid == 0) {
         s_scan = s_ret = s_ab = 0ull;
@@ -286,7 +310,14 @@ __global__ __launch_bounds__(kStreamThreads) void stream_move_kernel(StreamMoveA
 hipError_t launch_stream_prep(const StreamArgs& a, hipStream_t s) {
     if (a.s.n_clusters == 0) return hipSuccess;
     if (!a.s.job_cnt) return hipErrorInvalidValue;  // a stream reads an online session's segments
-    hipLaunchKernelGGL(stream_prep_kernel, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
+    hipLaunchKernelGGL(stream_prep_kernel<false>, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_trade_stream_prep(const StreamArgs& a, hipStream_t s) {
+    if (a.s.n_clusters == 0) return hipSuccess;
+    if (!a.s.job_cnt) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_prep_kernel<true>, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -300,7 +331,14 @@ hipError_t launch_stream_accum(const StreamArgs& a, hipStream_t s) {
 hipError_t launch_stream_retire(const StreamArgs& a, hipStream_t s) {
     if (a.s.n_clusters == 0) return hipSuccess;
     if (!a.s.job_cnt || a.chunk == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stream_retire_kernel, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
+    hipLaunchKernelGGL(stream_retire_kernel<false>, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_trade_stream_retire(const TradeStreamArgs& a, hipStream_t s) {
+    if (a.s.n_clusters == 0) return hipSuccess;
+    if (!a.s.job_cnt || a.chunk == 0 || !a.nv) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_retire_kernel<true>, dim3(a.s.n_clusters), dim3(kStreamThreads), 0, s, a);
     return hipGetLastError();
 }
 

@@ -167,6 +167,22 @@ class mcs_stream_stats(C.Structure):
     ]
 
 
+class mcs_trade_stream_stats(C.Structure):
+    _fields_ = [
+        ("n_written", C.c_uint32),
+        ("t_first", C.c_uint32),
+        ("t_next", C.c_uint32),
+        ("pending", C.c_uint32),
+        ("rows_scanned", C.c_uint64),
+        ("rows_retired", C.c_uint64),
+        ("foreign_scanned", C.c_uint32),
+        ("foreign_live", C.c_uint32),
+        ("rebuilt", C.c_uint32),
+        ("frontier", C.c_uint32),
+        ("kernel_ms", C.c_double),
+    ]
+
+
 class mcs_level1_sample(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("len", "cores", "mem", "fast_time_s", "small_time_s", "head")]
 
@@ -291,6 +307,10 @@ SIGNATURES = [
     ("mcs_stream_next", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
                                   C.c_uint32, C.POINTER(mcs_stream_stats)]),
     ("mcs_stream_close", C.c_int, [vp]),
+    ("mcs_trade_stream_open", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("mcs_trade_stream_next", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
+                                        C.c_uint32, C.POINTER(mcs_trade_stream_stats)]),
+    ("mcs_trade_stream_close", C.c_int, [vp]),
     ("mcs_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),
                                     C.c_uint32, C.POINTER(C.c_double)]),
     ("mcs_online_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),

@@ -617,6 +617,45 @@ class Engine:
         """mcs_stream_close: end the subscription and free what it kept on the device."""
         self._c(L.lib().mcs_stream_close(self._h))
 
+    def trade_stream_open(self, t0_s: int, period_s: int, with_wait: bool = True):
+        """mcs_trade_stream_open: subscribe to the current trading session (policy DELAY with trader) at
+        the cadence t0_s + k * period_s.  One stream per engine; it may be opened mid-session, and the
+        first trade_stream_next then catches up over the history once.  A drain, the run after it and
+        a capacity escalation's replay leave it open."""
+        for v in (t0_s, period_s):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise L.MCSError(L.MCS_E_INVALID, "t0_s and period_s are uint32")
+        self._c(L.lib().mcs_trade_stream_open(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
+        self._trade_stream_wait = bool(with_wait)
+
+    def trade_stream_next(self, max_samples: int):
+        """mcs_trade_stream_next: the decided samples the stream has not handed out yet, at most
+        max_samples of them: every second t_next + k * period_s below the frontier (the largest finite
+        horizon so far; after a drain, the last executed tick + 1), each bit for bit what
+        trade_session_state_series returns for it.  Returns (samples, wait, stats) as stream_next does,
+        stats holding the mcs_trade_stream_stats fields (foreign_scanned, foreign_live, rebuilt and
+        frontier among them).  MCSError (MCS_E_STATE) once the engine closed the stream: the message
+        names the cause; reopen."""
+        if not 0 < int(max_samples) <= 0xFFFFFFFF:
+            raise L.MCSError(L.MCS_E_INVALID, "max_samples is a positive uint32")
+        n = self.num_clusters
+        m = int(max_samples)
+        with_wait = getattr(self, "_trade_stream_wait", False)
+        samples = np.zeros((n, m), CLUSTER_SAMPLE_DTYPE)
+        wait = np.zeros((n, m), WAIT_SAMPLE_DTYPE) if with_wait else None
+        st = L.mcs_trade_stream_stats()
+        self._c(L.lib().mcs_trade_stream_next(
+            self._h, m, samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
+            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None, n, C.byref(st)))
+        k = int(st.n_written)
+        stats = {f: getattr(st, f) for f, _ in L.mcs_trade_stream_stats._fields_}
+        return (np.ascontiguousarray(samples[:, :k]), np.ascontiguousarray(wait[:, :k]) if with_wait else None,
+                stats)
+
+    def trade_stream_close(self):
+        """mcs_trade_stream_close: end the subscription and free what it kept on the device."""
+        self._c(L.lib().mcs_trade_stream_close(self._h))
+
     def _level1(self, fn, t0_s, period_s, n_samples, with_time):
         for v in (t0_s, period_s, n_samples):
             if not 0 <= int(v) <= 0xFFFFFFFF:
