@@ -495,7 +495,8 @@ int mcs_stream_next(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sample* o
                     mcs_stream_stats* stats /* may be NULL */);
 
 /* Ends the subscription and frees what it kept.  MCS_E_STATE when no stream was opened or the stream
- * was closed already by this call. */
+ * was closed already by this call.  Closes a stream of either kind (mcs_stream_open,
+ * mcs_stream_open_level1). */
 int mcs_stream_close(mcs_engine* eng);
 
 /* ---- the Level1 list over time: what ProvideJobs hands the trader ---------------------------- */
@@ -551,6 +552,29 @@ int mcs_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_
  * appended behind a drain.  Nothing is kept between calls. */
 int mcs_online_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t n_samples,
                              mcs_level1_sample* out, uint32_t n_clusters, double* kernel_ms);
+
+/* Level1 samples on the cursor: both halves of ResourceChannel at a slice's cost.  A stream opened with
+ * mcs_stream_open_level1 (a DELAY session; MCS_E_INVALID under FIFO, which has no Level1; everything else
+ * as mcs_stream_open, with_wait included) also hands out, at its own cadence, the mcs_level1_sample
+ * (above) of every second it hands out: mcs_stream_next_level1 fills level1[c * max_samples + k], k <
+ * n_written, for the same seconds as out, each bit for bit what mcs_online_level1_series returns for
+ * that second on the same session at that moment; out and wait are exactly mcs_stream_next's.  There is
+ * still one stream per engine and one cadence: a trader that reads ProvideJobs every 10 s and Start
+ * every 5 s subscribes at 5 and ignores every other list.  Between calls the engine then also keeps
+ * the per-row records whether or not with_wait is set (16 B per row), one uint32 per batch of 256 rows
+ * (the batch's Level1 summary, final once the batch is) and 8 B per cluster (the two scan bounds, which
+ * only move up: DESIGN.md §14); a call scans the batches between the bounds that still hold a member.
+ * level1 must be non-NULL exactly when the stream was opened with Level1, in either next call
+ * (MCS_E_INVALID otherwise: mcs_stream_next on a Level1 stream is refused).  stats and l1stats may be
+ * NULL.  Frontier, closing causes and relayouts are the cursor's own. */
+typedef struct mcs_level1_stream_stats {
+    uint64_t rows_scanned;  /* rows whose record this call's Level1 scans loaded, counted on the device */
+    double kernel_ms;       /* device time of the Level1 launches of this call (also inside stats->kernel_ms) */
+} mcs_level1_stream_stats;
+int mcs_stream_open_level1(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t with_wait);
+int mcs_stream_next_level1(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sample* out,
+                           mcs_wait_sample* wait /* NULL unless with_wait */, mcs_level1_sample* level1,
+                           uint32_t n_clusters, mcs_stream_stats* stats, mcs_level1_stream_stats* l1stats);
 
 /* ProvideJobs at one second: the rows of Level1(t_s) of one cluster in list order, as indices into
  * the cluster's stream (row r is job job_offsets[cluster] + r of mcs_read_jobs, which has its

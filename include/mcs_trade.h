@@ -321,7 +321,8 @@ int mcs_trade_session_level1_series(mcs_engine* eng, uint32_t t0_s, uint32_t per
  * A segment relayout by mcs_append_jobs does not close it.  One stream per engine; t0_s may lie far below
  * the frontier, and the first call then catches up once.  MCS_E_STATE without a trading session (a session
  * without trading subscribes with mcs_stream_open, which keeps refusing a trading session).  Level1
- * samples are not part of a cursor (mcs_trade_session_level1_series), nor is the record at t0_s. */
+ * samples come with a cursor opened by mcs_trade_stream_open_level1 (below); the record at t0_s is not
+ * part of a cursor. */
 typedef struct mcs_trade_stream_stats {
     uint32_t n_written, t_first, t_next, pending; /* as mcs_stream_stats                                  */
     uint64_t rows_scanned, rows_retired;          /* as mcs_stream_stats, counted on the device           */
@@ -338,6 +339,17 @@ int mcs_trade_stream_next(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sam
                           mcs_wait_sample* wait /* NULL unless with_wait */, uint32_t n_clusters,
                           mcs_trade_stream_stats* stats /* may be NULL */);
 int mcs_trade_stream_close(mcs_engine* eng);
+/* mcs_stream_open_level1 / mcs_stream_next_level1 (mcs.h) for a trading session: the cursor also hands
+ * out, for the same seconds as out, the Level1 samples, each bit for bit what
+ * mcs_trade_session_level1_series returns for that second on the same session at that moment (below F*
+ * also where that call refuses: after jobs appended behind a drain).  level1 must be non-NULL exactly
+ * when the stream was opened with Level1, in either next call.  A replay (rebuilt = 1) drops the
+ * carried scan bounds with everything else kept; mcs_trade_stream_close closes either kind. */
+int mcs_trade_stream_open_level1(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, uint32_t with_wait);
+int mcs_trade_stream_next_level1(mcs_engine* eng, uint32_t max_samples, mcs_cluster_sample* out,
+                                 mcs_wait_sample* wait /* NULL unless with_wait */, mcs_level1_sample* level1,
+                                 uint32_t n_clusters, mcs_trade_stream_stats* stats,
+                                 mcs_level1_stream_stats* l1stats);
 
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,

@@ -266,6 +266,15 @@ struct mcs_engine {
     mcs_cluster_sample* d_st_out = nullptr;  // the call's samples on the device, st_out_cap per cluster
     mcs_wait_sample* d_st_wout = nullptr;
     uint64_t st_out_cap = 0;
+    // Level1 samples on the stream (mcs_stream_open_level1 / mcs_trade_stream_open_level1): the records
+    // are then kept whether or not st_wait is set
+    bool st_l1 = false;
+    bool st_l1_fresh = false;          // nothing is carried: the next call that writes samples starts from row 0
+    uint32_t* d_st_l1s = nullptr;      // per batch: the kept Level1 summary
+    uint2* d_st_l1c = nullptr;         // [C] the carried scan bounds {lo, hi}
+    mcs_level1_sample* d_st_l1out = nullptr;  // the call's Level1 samples, st_out_cap per cluster
+    unsigned long long* d_st_l1rows = nullptr;  // rows this call's Level1 scans loaded
+    hipEvent_t st_l1ev[2] = {nullptr, nullptr};
     // a trading session's stream (mcs_trade_stream_*, mcs_dtrade.cpp) shares the fields above: plain and
     // trading sessions exclude each other.  st_h is then the frontier F* (DESIGN.md §14).
     bool st_trade = false;             // the stream (or the one last closed) is a trading session's

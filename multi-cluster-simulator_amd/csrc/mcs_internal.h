@@ -306,7 +306,7 @@ struct StreamArgs {
     uint32_t* flags;           // per batch
     uint2* summ;               // per batch: SeriesArgs::summ
     unsigned long long* bsum;  // per final batch: sum of s - a over its rows
-    uint4* rec;                // per row {h, m, s, arrival}; null without the wait statistics
+    uint4* rec;                // per row {h, m, s, arrival}; null without the wait statistics and Level1
     mcs_wait_sample* wout;     // [s.n_clusters][n_samples] accumulators (stream_accum_kernel)
     unsigned long long* tot;   // [0] rows this call loaded, [1] rows in retired batches
     uint32_t hor;              // the last finite horizon: d below it is final
@@ -338,11 +338,33 @@ struct StreamMoveArgs {
     uint2* summ_n;
     const unsigned long long* bsum_o;
     unsigned long long* bsum_n;
-    const uint4* rec_o;  // null without the wait statistics
+    const uint4* rec_o;  // null without the records (neither wait statistics nor Level1)
     uint4* rec_n;
+    const uint32_t* l1s_o;  // null without Level1: StreamLevel1Args::l1s
+    uint32_t* l1s_n;
     uint32_t n_clusters;
 };
 hipError_t launch_stream_move(const StreamMoveArgs& a, hipStream_t s);
+// Level1 samples on a cursor (mcs_stream_open_level1; DESIGN.md §14 "Level1 on the cursors"): per batch
+// the kept Level1 summary (the largest s among the rows that move, as level1_summary_kernel defines it;
+// a final batch keeps it), per cluster the scan bounds {lo, hi} of level1_series_kernel carried from the
+// call's last sample to the next call's first.  The records are the stream's kept ones.
+struct StreamLevel1Args {
+    const uint4* jobs;
+    const uint64_t* job_off;
+    const uint32_t* job_cnt;
+    const StreamCluster* cl;   // first_live: every batch below it is retired and holds no member
+    const uint32_t* flags;     // summary refresh: the batches prep loaded in this call (kStreamLoaded)
+    const uint4* rec;
+    uint32_t* l1s;             // per batch, indexed as the other kept arrays
+    uint2* carry;              // [n_clusters] {lo, hi}
+    mcs_level1_sample* out;    // [n_clusters][n_samples], cluster-major
+    unsigned long long* rows;  // rows with lo <= j < hi inside the scanned batches, added per wave
+    uint32_t t0, period, n_samples, n_clusters;
+    uint32_t fresh;            // 1: nothing is carried (after open or a rebuild): hi by bisection from row 0
+};
+hipError_t launch_stream_level1_summ(const StreamLevel1Args& a, hipStream_t s);  // once per call, after prep
+hipError_t launch_stream_level1(const StreamLevel1Args& a, hipStream_t s);       // one chunk of samples
 
 // The Level1 list over time (mcs_level1.hip): len(Level1), both contract sizes and the head row after
 // the Delay iteration at the seconds t0 + k * period, k < n_samples, of the first n_clusters clusters,

@@ -3,8 +3,10 @@
 //
 // The engine owns the kept arrays: per batch of kSeriesBatch rows a flag word, the summary pair and the
 // sum of s - a (indexed as the series summaries are: by segment start, over segment capacity), per row
-// the wait record (a stream with wait statistics), per cluster a StreamCluster.  They are freed when
-// the stream closes and at destroy, and follow the segments through a relayout (stream_relayout).
+// the wait record (a stream with wait statistics or with Level1), per cluster a StreamCluster; a stream
+// opened with Level1 (mcs_stream_open_level1) adds per batch the Level1 summary and per cluster the
+// carried scan bounds.  They are freed when the stream closes and at destroy, and follow the segments
+// through a relayout (stream_relayout).
 // A trading session's cursor (mcs_trade_stream_open / next / close, mcs_trade.h) shares all of it, since
 // plain and trading sessions exclude each other, and adds the two Foreign lists, the log position and
 // the row counts of the current call; its frontier F* and its hooks in dtrade_session_run are below.
@@ -32,6 +34,15 @@ void stream_free(mcs_engine* e) {
     dfree(e->d_st_fl[1]);
     dfree(e->d_st_fl_n);
     dfree(e->d_st_nv);
+    dfree(e->d_st_l1s);
+    dfree(e->d_st_l1c);
+    dfree(e->d_st_l1out);
+    dfree(e->d_st_l1rows);
+    for (hipEvent_t& ev : e->st_l1ev) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    e->st_l1 = e->st_l1_fresh = false;
     e->st_fl_cap = e->st_fl_n = e->st_seen = 0;
     e->st_out_cap = 0;
     e->st_open = false;
@@ -41,13 +52,15 @@ namespace {
 
 // the kept arrays for the segment layout `off` (capacity off[C]); the flags start at 0: nothing known
 int stream_alloc(mcs_engine* e, const std::vector<uint64_t>& off, uint32_t** flags, uint2** summ,
-                 unsigned long long** bsum, uint4** rec) {
+                 unsigned long long** bsum, uint4** rec, uint32_t** l1s) {
     const size_t nbat = series_summ_size(off[e->C], e->C);
     HIPCHK(e, hipMalloc(flags, nbat * sizeof(uint32_t)));
     HIPCHK(e, hipMemsetAsync(*flags, 0, nbat * sizeof(uint32_t), e->stream));
     HIPCHK(e, hipMalloc(summ, nbat * sizeof(uint2)));
     HIPCHK(e, hipMalloc(bsum, nbat * sizeof(unsigned long long)));
-    if (e->st_wait) HIPCHK(e, hipMalloc(rec, (size_t)(off[e->C] ? off[e->C] : 1) * sizeof(uint4)));
+    // the records serve the wait statistics and Level1 alike
+    if (e->st_wait || e->st_l1) HIPCHK(e, hipMalloc(rec, (size_t)(off[e->C] ? off[e->C] : 1) * sizeof(uint4)));
+    if (e->st_l1) HIPCHK(e, hipMalloc(l1s, nbat * sizeof(uint32_t)));
     return MCS_OK;
 }
 
@@ -62,15 +75,25 @@ int stream_reset_kept(mcs_engine* e) {
     std::vector<StreamCluster> cl(C, StreamCluster{-1, 0ull, 0u, 0u});
     HIPCHK(e, hipMemcpy(e->d_st_cl, cl.data(), C * sizeof(StreamCluster), hipMemcpyHostToDevice));
     e->st_retired = 0;
+    if (e->st_l1) {  // the carried bounds are dropped with the rest
+        HIPCHK(e, hipMemset(e->d_st_l1c, 0, C * sizeof(uint2)));
+        e->st_l1_fresh = true;
+    }
     return MCS_OK;
 }
 
 int stream_alloc_kept(mcs_engine* e, const char* call) {
-    int rc = stream_alloc(e, e->job_off, &e->d_st_flags, &e->d_st_summ, &e->d_st_bsum, &e->d_st_rec);
+    int rc = stream_alloc(e, e->job_off, &e->d_st_flags, &e->d_st_summ, &e->d_st_bsum, &e->d_st_rec, &e->d_st_l1s);
     const size_t C = e->C ? e->C : 1;
     hipError_t st = hipSuccess;
     if (rc == MCS_OK) st = hipMalloc(&e->d_st_cl, C * sizeof(StreamCluster));
     if (rc == MCS_OK && st == hipSuccess) st = hipMalloc(&e->d_st_tot, 2 * sizeof(unsigned long long));
+    if (rc == MCS_OK && st == hipSuccess && e->st_l1) {
+        st = hipMalloc(&e->d_st_l1c, C * sizeof(uint2));
+        if (st == hipSuccess) st = hipMalloc(&e->d_st_l1rows, sizeof(unsigned long long));
+        for (hipEvent_t& ev : e->st_l1ev)
+            if (st == hipSuccess) st = hipEventCreate(&ev);
+    }
     if (rc == MCS_OK && st != hipSuccess) rc = fail(e, MCS_E_HIP, std::string(call) + ": " + hipGetErrorString(st));
     if (rc == MCS_OK) rc = stream_reset_kept(e);
     if (rc != MCS_OK) stream_free(e);
@@ -153,7 +176,8 @@ int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_
     uint2* summ = nullptr;
     unsigned long long* bsum = nullptr;
     uint4* rec = nullptr;
-    int rc = stream_alloc(e, new_off, &flags, &summ, &bsum, &rec);
+    uint32_t* l1s = nullptr;
+    int rc = stream_alloc(e, new_off, &flags, &summ, &bsum, &rec, &l1s);
     if (rc == MCS_OK) {
         StreamMoveArgs m{};
         m.old_off = d_old_off;
@@ -167,6 +191,8 @@ int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_
         m.bsum_n = bsum;
         m.rec_o = e->d_st_rec;
         m.rec_n = rec;
+        m.l1s_o = e->d_st_l1s;
+        m.l1s_n = l1s;
         m.n_clusters = e->C;
         hipError_t st = launch_stream_move(m, e->stream);
         if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
@@ -177,6 +203,7 @@ int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_
         dfree(summ);
         dfree(bsum);
         dfree(rec);
+        dfree(l1s);
         const std::string msg = e->err;
         stream_shut(e, "a segment relayout that failed");
         e->err = msg;
@@ -186,6 +213,8 @@ int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_
     dfree(e->d_st_summ);
     dfree(e->d_st_bsum);
     dfree(e->d_st_rec);
+    dfree(e->d_st_l1s);
+    e->d_st_l1s = l1s;
     e->d_st_flags = flags;
     e->d_st_summ = summ;
     e->d_st_bsum = bsum;
@@ -195,10 +224,8 @@ int stream_relayout(mcs_engine* e, const uint64_t* d_old_off, const uint64_t* d_
 
 }  // namespace mcs
 
-extern "C" {
-
-int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
-    if (int st = check_engine(e)) return st;
+// mcs_stream_open and mcs_stream_open_level1 behind check_engine
+static int stream_open_impl(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait, bool level1) {
     if (int st = mcs::refuse_trade_session(e, "mcs_stream_open")) return st;
     if (!e->online)
         return fail(e, MCS_E_STATE, "mcs_stream_open subscribes to an online session (mcs_run with a horizon, "
@@ -209,8 +236,11 @@ int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t wi
     if (period_s == 0) return fail(e, MCS_E_INVALID, "period_s must be positive");
     if (with_wait && e->cfg.policy != MCS_POLICY_DELAY)
         return fail(e, MCS_E_INVALID, "the wait statistics need a DELAY session: only \"/delay\" feeds WaitTime");
+    if (level1 && e->cfg.policy != MCS_POLICY_DELAY)
+        return fail(e, MCS_E_INVALID, "Level1 samples need a DELAY session: Scheduler.Fifo has no Level1");
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->st_wait = with_wait != 0;
+    e->st_l1 = level1;
     e->st_cause.clear();
     e->st_trade = false;
     if (int rc = mcs::stream_alloc_kept(e, "mcs_stream_open")) return rc;
@@ -223,6 +253,18 @@ int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t wi
     return MCS_OK;
 }
 
+extern "C" {
+
+int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    return stream_open_impl(e, t0_s, period_s, with_wait, false);
+}
+
+int mcs_stream_open_level1(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    return stream_open_impl(e, t0_s, period_s, with_wait, true);
+}
+
 }  // extern "C"
 
 // The body of mcs_stream_next and mcs_trade_stream_next behind their state checks.  A trading session's
@@ -230,13 +272,17 @@ int mcs_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t wi
 // summaries and the kept Foreign list in place of series_kernel, and the TRADE instantiations of the prep
 // and the retire kernel (StreamArgs::nv).
 static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs_cluster_sample* out,
-                            mcs_wait_sample* wait, uint32_t n_clusters, mcs_trade_stream_stats* stats) {
+                            mcs_wait_sample* wait, mcs_level1_sample* level1, uint32_t n_clusters,
+                            mcs_trade_stream_stats* stats, mcs_level1_stream_stats* l1stats) {
     const std::string call = trade ? "mcs_trade_stream_next" : "mcs_stream_next";
     if (n_clusters != e->C)
         return fail(e, MCS_E_INVALID, "n_clusters must equal mcs_num_clusters: the frontier is common to all clusters");
     if (!out || max_samples == 0) return fail(e, MCS_E_INVALID, "bad output");
     if ((wait != nullptr) != e->st_wait)
         return fail(e, MCS_E_INVALID, "wait must be given exactly when the stream was opened with_wait");
+    if ((level1 != nullptr) != e->st_l1)
+        return fail(e, MCS_E_INVALID, "level1 must be given exactly when the stream was opened with Level1 "
+                                      "(mcs_stream_open_level1, mcs_trade_stream_open_level1; their next calls)");
     const uint32_t period = e->st_period, t0 = e->st_next, h = e->st_h;
     const uint64_t decided = t0 < h ? ((uint64_t)(h - t0) + period - 1) / period : 0ull;  // samples below h
     const uint32_t n = (uint32_t)std::min<uint64_t>(decided, max_samples);
@@ -253,12 +299,13 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
         e->st_next = t_after;
         return MCS_OK;
     }
-    if (e->st_wait)
+    if (e->st_wait || e->st_l1)
         for (uint32_t c = 0; c < e->C; ++c)  // job indices within a cluster are 32-bit on the device
             if (e->job_cnt[c] > 0xFFFFFFFEull) return fail(e, MCS_E_INVALID, "a cluster holds more than 2^32 - 2 jobs");
     if (int st = mcs::ensure_job_records(e)) return st;
     // samples per launch: the device buffers stay within 256 MiB (MCS_SERIES_CHUNK overrides the count)
-    uint64_t chunk = (256ull << 20) / ((sizeof(mcs_cluster_sample) + sizeof(mcs_wait_sample)) * (uint64_t)n_clusters);
+    uint64_t chunk = (256ull << 20) / ((sizeof(mcs_cluster_sample) + sizeof(mcs_wait_sample) +
+                                        (e->st_l1 ? sizeof(mcs_level1_sample) : 0)) * (uint64_t)n_clusters);
     if (const char* env = getenv("MCS_SERIES_CHUNK"))
         if (atoll(env) > 0) chunk = (uint64_t)atoll(env);
     if (chunk < 1) chunk = 1;
@@ -266,10 +313,12 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
     if (e->st_out_cap < chunk) {
         dfree(e->d_st_out);
         dfree(e->d_st_wout);
+        dfree(e->d_st_l1out);
         e->st_out_cap = 0;
         const uint64_t cap = std::max<uint64_t>(chunk, 16);
         HIPCHK(e, hipMalloc(&e->d_st_out, (size_t)n_clusters * cap * sizeof(mcs_cluster_sample)));
         if (e->st_wait) HIPCHK(e, hipMalloc(&e->d_st_wout, (size_t)n_clusters * cap * sizeof(mcs_wait_sample)));
+        if (e->st_l1) HIPCHK(e, hipMalloc(&e->d_st_l1out, (size_t)n_clusters * cap * sizeof(mcs_level1_sample)));
         e->st_out_cap = cap;
     }
     mcs::DtStreamView v{};
@@ -378,9 +427,23 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
     wa.max_wait = e->cfg.max_wait_s;
     wa.period = period;
     wa.n_clusters = n_clusters;
-    double total_ms = 0.0;
-    unsigned long long tot[2] = {0ull, 0ull};
+    mcs::StreamLevel1Args la{};
+    la.jobs = e->d_jobs;
+    la.job_off = e->d_job_off;
+    la.job_cnt = e->d_job_cnt;
+    la.cl = e->d_st_cl;
+    la.flags = e->d_st_flags;
+    la.rec = e->d_st_rec;
+    la.l1s = e->d_st_l1s;
+    la.carry = e->d_st_l1c;
+    la.out = e->d_st_l1out;
+    la.rows = e->d_st_l1rows;
+    la.period = period;
+    la.n_clusters = n_clusters;
+    double total_ms = 0.0, l1_ms = 0.0;
+    unsigned long long tot[2] = {0ull, 0ull}, l1_rows = 0ull;
     hipError_t st = hipMemsetAsync(e->d_st_tot, 0, sizeof(unsigned long long), e->stream);  // [0]: this call's rows
+    if (st == hipSuccess && e->st_l1) st = hipMemsetAsync(e->d_st_l1rows, 0, sizeof(unsigned long long), e->stream);
     for (uint64_t k0 = 0; st == hipSuccess && k0 < n; k0 += chunk) {
         const uint32_t nk = (uint32_t)(n - k0 < chunk ? n - k0 : chunk);
         const bool last = k0 + nk == n;
@@ -397,16 +460,35 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
             if (st == hipSuccess) st = mcs::launch_stream_accum(a, e->stream);
             if (st == hipSuccess) st = mcs::launch_wait_finish(wa, e->stream);
         }
+        if (st == hipSuccess && e->st_l1) {  // before the retire kernel: first_live is the last call's
+            la.t0 = a.t0;
+            la.n_samples = nk;
+            la.fresh = e->st_l1_fresh && k0 == 0 ? 1u : 0u;
+            st = hipEventRecord(e->st_l1ev[0], e->stream);
+            if (st == hipSuccess && k0 == 0) st = mcs::launch_stream_level1_summ(la, e->stream);
+            if (st == hipSuccess) st = mcs::launch_stream_level1(la, e->stream);
+            if (st == hipSuccess) st = hipEventRecord(e->st_l1ev[1], e->stream);
+        }
         if (st == hipSuccess && last) {  // the whole call's samples against the new frontier
-            a.t0 = t0;
-            a.n_samples = n;
-            st = trade ? mcs::launch_trade_stream_retire(a, e->stream) : mcs::launch_stream_retire(a, e->stream);
+            mcs::TradeStreamArgs ra = a;
+            ra.t0 = t0;
+            ra.n_samples = n;
+            if (!e->st_wait) ra.rec = nullptr;  // records kept for Level1 alone: no accum kernel loaded them
+            st = trade ? mcs::launch_trade_stream_retire(ra, e->stream) : mcs::launch_stream_retire(ra, e->stream);
         }
         if (st == hipSuccess) st = hipEventRecord(e->ev1, e->stream);
         if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
         float ms = 0.0f;
         if (st == hipSuccess) st = hipEventElapsedTime(&ms, e->ev0, e->ev1);
         total_ms += ms;
+        if (st == hipSuccess && e->st_l1) {
+            st = hipEventElapsedTime(&ms, e->st_l1ev[0], e->st_l1ev[1]);
+            l1_ms += ms;
+            if (st == hipSuccess)
+                st = hipMemcpy2D(level1 + k0, (size_t)max_samples * sizeof(mcs_level1_sample), e->d_st_l1out,
+                                 (size_t)nk * sizeof(mcs_level1_sample), (size_t)nk * sizeof(mcs_level1_sample),
+                                 n_clusters, hipMemcpyDeviceToHost);
+        }
         if (st == hipSuccess)  // the chunk's columns of every cluster's row
             st = hipMemcpy2D(out + k0, (size_t)max_samples * sizeof(mcs_cluster_sample), e->d_st_out,
                              (size_t)nk * sizeof(mcs_cluster_sample), (size_t)nk * sizeof(mcs_cluster_sample),
@@ -417,6 +499,7 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
                              hipMemcpyDeviceToHost);
     }
     if (st == hipSuccess) st = hipMemcpy(tot, e->d_st_tot, sizeof(tot), hipMemcpyDeviceToHost);
+    if (st == hipSuccess && e->st_l1) st = hipMemcpy(&l1_rows, e->d_st_l1rows, sizeof(l1_rows), hipMemcpyDeviceToHost);
     uint32_t fl_n = 0;
     if (st == hipSuccess && trade) st = hipMemcpy(&fl_n, e->d_st_fl_n, sizeof(fl_n), hipMemcpyDeviceToHost);
     if (st != hipSuccess) {
@@ -428,6 +511,11 @@ static int stream_next_impl(mcs_engine* e, bool trade, uint32_t max_samples, mcs
     }
     e->st_next = a.frontier;
     e->st_retired = tot[1];
+    e->st_l1_fresh = false;  // the carried bounds are those of this call's last sample
+    if (l1stats) {
+        l1stats->rows_scanned = l1_rows;
+        l1stats->kernel_ms = l1_ms;
+    }
     if (trade) {  // the new list is the kept one; the log is taken up to n_log
         e->st_fl_cur ^= 1;
         e->st_fl_n = std::min(fl_n, e->st_fl_cap);
@@ -451,8 +539,15 @@ extern "C" {
 
 int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
                     uint32_t n_clusters, mcs_stream_stats* stats) {
+    return mcs_stream_next_level1(e, max_samples, out, wait, nullptr, n_clusters, stats, nullptr);
+}
+
+int mcs_stream_next_level1(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
+                           mcs_level1_sample* level1, uint32_t n_clusters, mcs_stream_stats* stats,
+                           mcs_level1_stream_stats* l1stats) {
     if (int st = check_engine(e)) return st;
     if (stats) *stats = mcs_stream_stats{};
+    if (l1stats) *l1stats = mcs_level1_stream_stats{};
     if (e->st_trade && (e->st_open || !e->st_cause.empty()))
         return fail(e, MCS_E_STATE, "the engine's stream is a trading session's (mcs_trade_stream_next, "
                                     "mcs_trade_stream_close)");
@@ -461,7 +556,7 @@ int mcs_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out
         return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_stream_open)");
     }
     mcs_trade_stream_stats ts{};
-    const int rc = stream_next_impl(e, false, max_samples, out, wait, n_clusters, &ts);
+    const int rc = stream_next_impl(e, false, max_samples, out, wait, level1, n_clusters, &ts, l1stats);
     if (stats) {
         stats->n_written = ts.n_written;
         stats->t_first = ts.t_first;
@@ -496,8 +591,7 @@ static int no_trade_session(mcs_engine* e, const char* call) {
                                     "there is no trading session (in a session without trading: mcs_stream_open)");
 }
 
-int mcs_trade_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
-    if (int st = check_engine(e)) return st;
+static int trade_stream_open_impl(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait, bool level1) {
     if (!mcs::is_trade_session(e)) return no_trade_session(e, "mcs_trade_stream_open");
     if (e->st_open)
         return fail(e, MCS_E_STATE, "a stream is open already: one stream per engine (mcs_trade_stream_close)");
@@ -518,6 +612,7 @@ int mcs_trade_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint3
     if (period_s == 0) return fail(e, MCS_E_INVALID, "period_s must be positive");
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->st_wait = with_wait != 0;
+    e->st_l1 = level1;  // (a trading session is a DELAY session: it has Level1)
     e->st_cause.clear();
     e->st_trade = true;
     if (int rc = mcs::stream_alloc_kept(e, "mcs_trade_stream_open")) return rc;
@@ -533,10 +628,27 @@ int mcs_trade_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint3
     return MCS_OK;
 }
 
+int mcs_trade_stream_open(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    return trade_stream_open_impl(e, t0_s, period_s, with_wait, false);
+}
+
+int mcs_trade_stream_open_level1(mcs_engine* e, uint32_t t0_s, uint32_t period_s, uint32_t with_wait) {
+    if (int st = check_engine(e)) return st;
+    return trade_stream_open_impl(e, t0_s, period_s, with_wait, true);
+}
+
 int mcs_trade_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
                           uint32_t n_clusters, mcs_trade_stream_stats* stats) {
+    return mcs_trade_stream_next_level1(e, max_samples, out, wait, nullptr, n_clusters, stats, nullptr);
+}
+
+int mcs_trade_stream_next_level1(mcs_engine* e, uint32_t max_samples, mcs_cluster_sample* out, mcs_wait_sample* wait,
+                                 mcs_level1_sample* level1, uint32_t n_clusters, mcs_trade_stream_stats* stats,
+                                 mcs_level1_stream_stats* l1stats) {
     if (int st = check_engine(e)) return st;
     if (stats) *stats = mcs_trade_stream_stats{};
+    if (l1stats) *l1stats = mcs_level1_stream_stats{};
     if (!mcs::is_trade_session(e) && !(e->st_trade && !e->st_cause.empty()))
         return no_trade_session(e, "mcs_trade_stream_next");
     if (!e->st_open || !e->st_trade) {
@@ -544,7 +656,7 @@ int mcs_trade_stream_next(mcs_engine* e, uint32_t max_samples, mcs_cluster_sampl
             return fail(e, MCS_E_STATE, "no stream is open (mcs_trade_stream_open)");
         return fail(e, MCS_E_STATE, "the stream was closed by " + e->st_cause + ": reopen it (mcs_trade_stream_open)");
     }
-    const int rc = stream_next_impl(e, true, max_samples, out, wait, n_clusters, stats);
+    const int rc = stream_next_impl(e, true, max_samples, out, wait, level1, n_clusters, stats, l1stats);
     if (stats) stats->frontier = e->st_h;
     return rc;
 }

@@ -27,6 +27,9 @@
 //                         the call loaded from the flags and the summaries (series_kernel reads the
 //                         batches that its tiles hit: arrival_min <= t_last and end_max > t_first).
 // stream_move_kernel carries the kept arrays over a segment relayout.
+// A stream opened with Level1 (mcs_stream_open_level1) adds two kernels, stated where they stand below:
+//   stream_level1_summ_kernel  after the prep kernel: the Level1 summary of every batch prep loaded.
+//   stream_level1_kernel       the call's Level1 samples, one wave per cluster, from the carried bounds.
 // A trading session's stream (mcs_trade_stream_next) runs the TRADE instantiations of the prep and the
 // retire kernel, dt_series_kernel in place of series_kernel and, before them, dt_stream_foreign_kernel
 // (mcs_state.hip): the two differences are stated at the templates.  The plain instantiations are the
@@ -35,6 +38,7 @@
 #include <type_traits>
 
 #include "mcs_internal.h"
+#include "mcs_level1_dev.h"
 #include "mcs_wait_dev.h"
 #include "mcs_wave.h"
 
@@ -300,9 +304,125 @@ __global__ __launch_bounds__(kStreamThreads) void stream_move_kernel(StreamMoveA
         a.summ_n[bn + b] = a.summ_o[bo + b];
         a.bsum_n[bn + b] = a.bsum_o[bo + b];
     }
+    if (a.l1s_n)
+        for (uint64_t b = (uint64_t)blockIdx.x * kStreamThreads + threadIdx.x; b < nb; b += step)
+            a.l1s_n[bn + b] = a.l1s_o[bo + b];
     if (a.rec_n)
         for (uint64_t i = (uint64_t)blockIdx.x * kStreamThreads + threadIdx.x; i < J; i += step)
             a.rec_n[n0 + i] = a.rec_o[o0 + i];
+}
+
+// ---- Level1 samples on the cursor (mcs_stream_next_level1) --------------------------
+//
+// level1_summary_kernel's word for the batches stream_prep_kernel loaded in this call: one wave per
+// batch, four rows per lane.  A batch that was final before the call is not loaded and keeps its word
+// (its rows are decided: no s changes); one that became final in this call gets its last word here.
+__global__ __launch_bounds__(kStreamThreads) void stream_level1_summ_kernel(StreamLevel1Args a) {
+    const uint32_t c = blockIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t j0 = a.job_off[c];
+    const uint64_t J = a.job_cnt[c];
+    const uint64_t nb = (J + kSeriesBatch - 1) / kSeriesBatch;
+    const uint64_t bi = j0 / kSeriesBatch + c;
+    const uint32_t* __restrict__ flags = a.flags + bi;
+    const uint4* __restrict__ rec = a.rec + j0;
+    uint32_t* __restrict__ l1s = a.l1s + bi;
+    for (uint64_t b = (uint64_t)a.cl[c].first_live + wave; b < nb; b += kStreamThreads / kWave) {
+        if ((flags[b] & kStreamLoaded) == 0u) continue;  // uniform over the wave
+        uint32_t v = 0u;
+#pragma unroll
+        for (uint32_t u = 0; u < kSeriesBatch / kWave; ++u) {
+            const uint64_t j = b * kSeriesBatch + u * kWave + lane;
+            if (j < J) {
+                const uint4 r = rec[j];
+                if (r.z > r.y && r.z > v) v = r.z;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t w = __shfl_xor(v, o);
+            v = w > v ? w : v;
+        }
+        if (lane == 0u) l1s[b] = v;
+    }
+}
+
+// level1_series_kernel's samples with one wave per cluster, four clusters per workgroup: a call has
+// few samples and many clusters, so the parallelism is over clusters, and a sample costs no barrier
+// and no LDS.  The wave walks the chunk's samples in order from the carried pair {lo, hi} (both only
+// move up, across calls as along a tile: DESIGN.md §14), scans the batches between them whose kept
+// summary exceeds t, four rows per lane, and reduces with shuffles.  Batches below first_live are
+// passed over unread: a retired batch has every start <= finish < F <= t, so it holds no member and
+// its summary lies below every later sample.  Waves of a workgroup never wait for each other.
+constexpr uint32_t kStreamL1Clusters = kStreamThreads / kWave;
+__global__ __launch_bounds__(kStreamThreads) void stream_level1_kernel(StreamLevel1Args a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c = blockIdx.x * kStreamL1Clusters + (threadIdx.x >> 6);
+    if (c >= a.n_clusters) return;  // the whole wave
+    const uint64_t j0 = a.job_off[c];
+    const uint32_t J = a.job_cnt[c];
+    const uint4* __restrict__ rec = a.rec + j0;
+    const uint4* __restrict__ jobs = a.jobs + j0;
+    const uint32_t* __restrict__ summ = a.l1s + (j0 / kSeriesBatch + c);
+    const uint32_t first_live = a.cl[c].first_live;
+    mcs_level1_sample* const row = a.out + (size_t)c * a.n_samples;
+    const uint2 cr = a.carry[c];
+    uint32_t lo = a.fresh ? 0u : cr.x, hi = a.fresh ? 0u : cr.y;
+    unsigned long long rows = 0ull;  // uniform over the wave
+    for (uint32_t k = 0; k < a.n_samples; ++k) {
+        const uint32_t t = a.t0 + k * a.period;  // fits: the last sample is at most 0xFFFFFFFE
+        hi = a.fresh && k == 0u ? level1_hi(rec, 0u, J, t) : level1_hi_next(rec, hi, J, t, lane);
+        uint32_t len = 0u, sc = 0u, sm = 0u, dmax = 0u, first = kNone, last = 0u;
+        if (lo < hi) {
+            const uint32_t b1 = (hi - 1u) / kSeriesBatch;
+            uint32_t b = lo / kSeriesBatch;
+            if (b < first_live) b = first_live;
+            for (; b <= b1; ++b) {
+                if (summ[b] <= t) continue;  // the batch has wholly left Level1
+                const uint64_t r0 = (uint64_t)b * kSeriesBatch;
+                const uint64_t x0 = r0 > lo ? r0 : lo, x1 = r0 + kSeriesBatch < hi ? r0 + kSeriesBatch : hi;
+                rows += x1 - x0;  // (x0 < x1: lo's batch at the least holds lo, every other starts below hi)
+#pragma unroll
+                for (uint32_t u = 0; u < kSeriesBatch / kWave; ++u) {
+                    const uint64_t j = r0 + u * kWave + lane;
+                    if (j >= x0 && j < x1 && is_member(rec[j], t)) {
+                        const uint4 q = jobs[j];  // {arrival, dur, cores, mem}
+                        ++len;
+                        sc += q.z;
+                        sm += q.w;
+                        dmax = q.y > dmax ? q.y : dmax;
+                        first = (uint32_t)j < first ? (uint32_t)j : first;
+                        last = (uint32_t)j;  // rows rise along both loops
+                    }
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            len += __shfl_xor(len, o);
+            sc += __shfl_xor(sc, o);
+            sm += __shfl_xor(sm, o);
+            const uint32_t xd = __shfl_xor(dmax, o), xf = __shfl_xor(first, o), xl = __shfl_xor(last, o);
+            dmax = xd > dmax ? xd : dmax;
+            first = xf < first ? xf : first;
+            last = xl > last ? xl : last;
+        }
+        uint32_t small = 0u;
+        if (len != 0u && len % 20u == 0u) small = level1_small_time(rec, jobs, summ, first, last, t, lane);
+        if (lane == 0u) {
+            mcs_level1_sample s;
+            s.len = len;
+            s.cores = sc;
+            s.mem = sm;
+            s.fast_time_s = dmax;
+            s.small_time_s = small;
+            s.head = first;
+            row[k] = s;
+        }
+        lo = len ? first : hi;  // no row below the head, and none below hi of an empty list, comes back
+    }
+    if (lane == 0u) {
+        a.carry[c] = make_uint2(lo, hi);
+        if (rows) atomicAdd(a.rows, rows);
+    }
 }
 
 }  // namespace
@@ -345,6 +465,21 @@ hipError_t launch_trade_stream_retire(const TradeStreamArgs& a, hipStream_t s) {
 hipError_t launch_stream_move(const StreamMoveArgs& a, hipStream_t s) {
     if (a.n_clusters == 0) return hipSuccess;
     hipLaunchKernelGGL(stream_move_kernel, dim3(8, a.n_clusters), dim3(kStreamThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_level1_summ(const StreamLevel1Args& a, hipStream_t s) {
+    if (a.n_clusters == 0) return hipSuccess;
+    if (!a.job_cnt || !a.rec || !a.l1s || !a.flags || !a.cl) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_level1_summ_kernel, dim3(a.n_clusters), dim3(kStreamThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_level1(const StreamLevel1Args& a, hipStream_t s) {
+    if (a.n_clusters == 0 || a.n_samples == 0) return hipSuccess;
+    if (!a.job_cnt || !a.rec || !a.l1s || !a.cl || !a.carry || !a.out || !a.rows) return hipErrorInvalidValue;
+    const uint32_t grid = (a.n_clusters + kStreamL1Clusters - 1u) / kStreamL1Clusters;
+    hipLaunchKernelGGL(stream_level1_kernel, dim3(grid), dim3(kStreamThreads), 0, s, a);
     return hipGetLastError();
 }
 

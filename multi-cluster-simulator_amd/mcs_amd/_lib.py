@@ -187,6 +187,10 @@ class mcs_level1_sample(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("len", "cores", "mem", "fast_time_s", "small_time_s", "head")]
 
 
+class mcs_level1_stream_stats(C.Structure):
+    _fields_ = [("rows_scanned", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 class mcs_delay_cluster_stats(C.Structure):
     _fields_ = [
         ("total_wait_ms", C.c_int64),
@@ -307,10 +311,19 @@ SIGNATURES = [
     ("mcs_stream_next", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
                                   C.c_uint32, C.POINTER(mcs_stream_stats)]),
     ("mcs_stream_close", C.c_int, [vp]),
+    ("mcs_stream_open_level1", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("mcs_stream_next_level1", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
+                                         C.POINTER(mcs_level1_sample), C.c_uint32, C.POINTER(mcs_stream_stats),
+                                         C.POINTER(mcs_level1_stream_stats)]),
     ("mcs_trade_stream_open", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("mcs_trade_stream_next", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample), C.POINTER(mcs_wait_sample),
                                         C.c_uint32, C.POINTER(mcs_trade_stream_stats)]),
     ("mcs_trade_stream_close", C.c_int, [vp]),
+    ("mcs_trade_stream_open_level1", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("mcs_trade_stream_next_level1", C.c_int, [vp, C.c_uint32, C.POINTER(mcs_cluster_sample),
+                                               C.POINTER(mcs_wait_sample), C.POINTER(mcs_level1_sample), C.c_uint32,
+                                               C.POINTER(mcs_trade_stream_stats),
+                                               C.POINTER(mcs_level1_stream_stats)]),
     ("mcs_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),
                                     C.c_uint32, C.POINTER(C.c_double)]),
     ("mcs_online_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mcs_level1_sample),

@@ -576,17 +576,21 @@ class Engine:
             first.ctypes.data_as(C.POINTER(L.mcs_cluster_state)), n, C.byref(ms)))
         return (samples, wait, first, ms.value) if with_time else (samples, wait, first)
 
-    def stream_open(self, t0_s: int, period_s: int, with_wait: Optional[bool] = None):
+    def stream_open(self, t0_s: int, period_s: int, with_wait: Optional[bool] = None, with_level1: bool = False):
         """mcs_stream_open: subscribe to the current online session at the cadence t0_s + k * period_s.
         with_wait None: the wait statistics under DELAY, none under FIFO.  One stream per engine; it
-        may be opened mid-session, and the first stream_next then catches up over the history once."""
+        may be opened mid-session, and the first stream_next then catches up over the history once.
+        with_level1 (mcs_stream_open_level1, a DELAY session): stream_next also returns the Level1
+        samples of the same seconds."""
         for v in (t0_s, period_s):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise L.MCSError(L.MCS_E_INVALID, "t0_s and period_s are uint32")
         if with_wait is None:
             with_wait = self.policy == "DELAY"
-        self._c(L.lib().mcs_stream_open(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
+        fn = L.lib().mcs_stream_open_level1 if with_level1 else L.lib().mcs_stream_open
+        self._c(fn(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
         self._stream_wait = bool(with_wait)
+        self._stream_level1 = bool(with_level1)
 
     def stream_next(self, max_samples: int):
         """mcs_stream_next: the decided samples the stream has not handed out yet, at most
@@ -595,38 +599,59 @@ class Engine:
         (num_clusters, n) of CLUSTER_SAMPLE_DTYPE, the same shape of WAIT_SAMPLE_DTYPE (None for a
         stream without wait statistics) and the mcs_stream_stats fields as a dict (n may be 0).
         The cost follows the slice and the jobs still alive, not the session's age.  MCSError
-        (MCS_E_STATE) once the engine closed the stream: the message names the cause; reopen."""
+        (MCS_E_STATE) once the engine closed the stream: the message names the cause; reopen.
+        A stream opened with_level1 returns (samples, wait, level1, stats): level1 is (num_clusters, n)
+        of LEVEL1_SAMPLE_DTYPE, each sample bit for bit what online_level1_series returns for it, and
+        stats also holds level1_rows_scanned and level1_kernel_ms (mcs_level1_stream_stats)."""
         if not 0 < int(max_samples) <= 0xFFFFFFFF:
             raise L.MCSError(L.MCS_E_INVALID, "max_samples is a positive uint32")
         n = self.num_clusters
         m = int(max_samples)
         with_wait = getattr(self, "_stream_wait", False)
+        return self._stream_next(L.lib().mcs_stream_next, L.lib().mcs_stream_next_level1, L.mcs_stream_stats, n, m,
+                                 with_wait, getattr(self, "_stream_level1", False))
+
+    def _stream_next(self, fn, fn_level1, stats_type, n, m, with_wait, with_level1):
         # a cluster's row has max_samples columns, of which the first n_written are filled
         samples = np.zeros((n, m), CLUSTER_SAMPLE_DTYPE)
         wait = np.zeros((n, m), WAIT_SAMPLE_DTYPE) if with_wait else None
-        st = L.mcs_stream_stats()
-        self._c(L.lib().mcs_stream_next(
-            self._h, m, samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
-            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None, n, C.byref(st)))
+        st = stats_type()
+        p_out = samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample))
+        p_wait = wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None
+        if not with_level1:
+            self._c(fn(self._h, m, p_out, p_wait, n, C.byref(st)))
+        else:
+            level1 = np.zeros((n, m), LEVEL1_SAMPLE_DTYPE)
+            l1 = L.mcs_level1_stream_stats()
+            self._c(fn_level1(self._h, m, p_out, p_wait, level1.ctypes.data_as(C.POINTER(L.mcs_level1_sample)), n,
+                              C.byref(st), C.byref(l1)))
         k = int(st.n_written)
-        stats = {f: getattr(st, f) for f, _ in L.mcs_stream_stats._fields_}
-        return (np.ascontiguousarray(samples[:, :k]), np.ascontiguousarray(wait[:, :k]) if with_wait else None,
-                stats)
+        stats = {f: getattr(st, f) for f, _ in stats_type._fields_}
+        s_out = np.ascontiguousarray(samples[:, :k])
+        w_out = np.ascontiguousarray(wait[:, :k]) if with_wait else None
+        if not with_level1:
+            return s_out, w_out, stats
+        stats["level1_rows_scanned"] = int(l1.rows_scanned)
+        stats["level1_kernel_ms"] = float(l1.kernel_ms)
+        return s_out, w_out, np.ascontiguousarray(level1[:, :k]), stats
 
     def stream_close(self):
         """mcs_stream_close: end the subscription and free what it kept on the device."""
         self._c(L.lib().mcs_stream_close(self._h))
 
-    def trade_stream_open(self, t0_s: int, period_s: int, with_wait: bool = True):
+    def trade_stream_open(self, t0_s: int, period_s: int, with_wait: bool = True, with_level1: bool = False):
         """mcs_trade_stream_open: subscribe to the current trading session (policy DELAY with trader) at
         the cadence t0_s + k * period_s.  One stream per engine; it may be opened mid-session, and the
         first trade_stream_next then catches up over the history once.  A drain, the run after it and
-        a capacity escalation's replay leave it open."""
+        a capacity escalation's replay leave it open.  with_level1 (mcs_trade_stream_open_level1):
+        trade_stream_next also returns the Level1 samples of the same seconds."""
         for v in (t0_s, period_s):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise L.MCSError(L.MCS_E_INVALID, "t0_s and period_s are uint32")
-        self._c(L.lib().mcs_trade_stream_open(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
+        fn = L.lib().mcs_trade_stream_open_level1 if with_level1 else L.lib().mcs_trade_stream_open
+        self._c(fn(self._h, int(t0_s), int(period_s), 1 if with_wait else 0))
         self._trade_stream_wait = bool(with_wait)
+        self._trade_stream_level1 = bool(with_level1)
 
     def trade_stream_next(self, max_samples: int):
         """mcs_trade_stream_next: the decided samples the stream has not handed out yet, at most
@@ -635,22 +660,16 @@ class Engine:
         trade_session_state_series returns for it.  Returns (samples, wait, stats) as stream_next does,
         stats holding the mcs_trade_stream_stats fields (foreign_scanned, foreign_live, rebuilt and
         frontier among them).  MCSError (MCS_E_STATE) once the engine closed the stream: the message
-        names the cause; reopen."""
+        names the cause; reopen.  A stream opened with_level1 returns (samples, wait, level1, stats)
+        as stream_next does, each Level1 sample bit for bit trade_session_level1_series' for it."""
         if not 0 < int(max_samples) <= 0xFFFFFFFF:
             raise L.MCSError(L.MCS_E_INVALID, "max_samples is a positive uint32")
         n = self.num_clusters
         m = int(max_samples)
         with_wait = getattr(self, "_trade_stream_wait", False)
-        samples = np.zeros((n, m), CLUSTER_SAMPLE_DTYPE)
-        wait = np.zeros((n, m), WAIT_SAMPLE_DTYPE) if with_wait else None
-        st = L.mcs_trade_stream_stats()
-        self._c(L.lib().mcs_trade_stream_next(
-            self._h, m, samples.ctypes.data_as(C.POINTER(L.mcs_cluster_sample)),
-            wait.ctypes.data_as(C.POINTER(L.mcs_wait_sample)) if with_wait else None, n, C.byref(st)))
-        k = int(st.n_written)
-        stats = {f: getattr(st, f) for f, _ in L.mcs_trade_stream_stats._fields_}
-        return (np.ascontiguousarray(samples[:, :k]), np.ascontiguousarray(wait[:, :k]) if with_wait else None,
-                stats)
+        return self._stream_next(L.lib().mcs_trade_stream_next, L.lib().mcs_trade_stream_next_level1,
+                                 L.mcs_trade_stream_stats, n, m, with_wait,
+                                 getattr(self, "_trade_stream_level1", False))
 
     def trade_stream_close(self):
         """mcs_trade_stream_close: end the subscription and free what it kept on the device."""
