@@ -248,7 +248,12 @@ int mcs_dtrade_state_series(mcs_engine* eng, uint32_t t0_s, uint32_t period_s, u
  * mcs_online_state_series, mcs_online_level1_series, mcs_stream_open, mcs_cluster_states,
  * mcs_cluster_state_series, mcs_wait_time_series): a trading session's Start stream is read with
  * mcs_trade_session_state_series and mcs_trade_session_level1_series below, and subscribed to with
- * mcs_trade_stream_open / next / close. */
+ * mcs_trade_stream_open / next / close.
+ * External traders (further below): mcs_trade_external switches the built-in trader rounds off, and the
+ * caller issues ProvideVirtualNode and ReceiveVirtualNode itself between two slices
+ * (mcs_trade_session_provide_vnodes, mcs_trade_session_receive_vnodes).  mcs_run(h), h finite, then always
+ * ends with a tick at h - 1, so the guarantee reads: slicing changes no decision and no grant outcome, but
+ * it may change ticks_total; and a replay for a capacity escalation re-applies the grants. */
 typedef struct mcs_trade_session {
     uint32_t t_horizon;      /* last finite horizon (0: none yet)                                      */
     uint32_t t_last;         /* last executed tick                                                     */
@@ -350,6 +355,92 @@ int mcs_trade_stream_next_level1(mcs_engine* eng, uint32_t max_samples, mcs_clus
                                  mcs_wait_sample* wait /* NULL unless with_wait */, mcs_level1_sample* level1,
                                  uint32_t n_clusters, mcs_trade_stream_stats* stats,
                                  mcs_level1_stream_stats* l1stats);
+
+/* ---- external traders: ProvideVirtualNode and ReceiveVirtualNode in a trading session ------------- */
+/* The scheduler's ResourceChannel service (pkg/scheduler/trader_server.go) has four RPCs.  Start and
+ * ProvideJobs are the series and cursors above; the other two are how a trader acts on a scheduler:
+ * ProvideVirtualNode (trader_server.go:57-67 -> AllocateVirtualNodeResources, cluster.go:87-125) and
+ * ReceiveVirtualNode (trader_server.go:49-55 -> AddVirtualNode, cluster.go:65-85).  With the built-in
+ * trader rounds switched off (external mode) the caller issues them itself between two slices, in
+ * batches, on the GPU (DESIGN.md §14 "External traders").
+ *
+ * mcs_trade_external(eng, on): on != 0 switches the built-in trader rounds off (the lock-step system
+ * without rounds, the oracle's dtrade_run(trader = 0)); 0 switches them back on.  It needs
+ * MCS_POLICY_DELAY with cfg.trader = 1 and cfg.borrow = 0 on rank 0 of world 1 without a communicator,
+ * after mcs_load_clusters, and is accepted while no lock-step tick of the current session has run
+ * (before the first mcs_run, right after mcs_rewind, right after a new submit).  MCS_E_STATE, with the
+ * cause in mcs_last_error: once a tick has run, under FIFO or cfg.trader = 0, on a sharded engine, and
+ * during a caller-driven run (mcs_trade_begin).  The setting survives mcs_rewind and mcs_submit_jobs;
+ * mcs_load_clusters resets it to 0.  With the switch on every run takes the replayed kernels, a batch
+ * run included.
+ *   The forced last tick.  The lock-step loop skips seconds in which nothing is queued, and a grant acts
+ * on the node state the last executed tick left.  In external mode mcs_run(h), h finite, therefore always
+ * ends with a tick at h - 1: it does the releases due and, on a multiple of sample_period_s, the sample,
+ * and it decides nothing (ticks are consecutive while any job is queued).  Slicing then changes no
+ * decision and no grant outcome, but it may change mcs_trade_session.ticks_total.  A drain forces
+ * nothing. */
+int mcs_trade_external(mcs_engine* eng, uint32_t on);
+
+typedef struct mcs_vnode_request {
+    uint32_t responder, requester; /* local cluster indices (world 1: global)                          */
+    uint32_t cores, memory, time_s; /* the contract (trader.proto:20-27)                                */
+    uint32_t pad;
+} mcs_vnode_request;
+typedef struct mcs_vnode_result {
+    int32_t ok;          /* 1: both halves ended at 0; 0: "couldn't schedule enough resources" (the Foreign
+                            jobs launched on the way stay, cluster.go:119-121)                          */
+    uint32_t visited;    /* rows walked: a prefix of the responder's rows                               */
+    uint32_t left_cores, left_memory; /* what remained of the request                                   */
+} mcs_vnode_result;
+typedef struct mcs_vnode_stats {
+    uint32_t n, n_ok;       /* entries of the call; provide: those with ok = 1 (receive: n)            */
+    uint32_t foreign_added; /* Foreign records the call appended                                        */
+    uint32_t replayed;      /* 1: the call overflowed a pool and replayed the session from t = 0        */
+    double kernel_ms;
+} mcs_vnode_stats;
+/* AllocateVirtualNodeResources for each request, in array order, as a trader round at the session's last
+ * executed tick T = t_last would run it: the walk over the responder's rows (the physical nodes, then
+ * the virtual nodes received so far) stops at a row once both halves of the request are 0; the float64
+ * absolute differences against the row's free counters (Go uint64: the sign-extended u32 halves); a half
+ * becomes 0 when its difference exceeds it, else shrinks by uint32(diff); every visited row gets a
+ * Foreign job {uint(core_diff), uint(mem_diff)} from T to T + time_s (time_s = 0: logged, holds nothing,
+ * takes no running slot; else the row's counter is reduced and may wrap, and a running slot is taken).
+ * The records go to the Foreign log in array order, in row order within a request (mcs_read_foreign, an
+ * open cursor's "appended since"); nothing goes to the contract log.  The second of two requests to one
+ * responder sees the first one's commits.  n == 0 is MCS_OK.  One upload, two launches, one
+ * synchronisation, whatever n is.
+ *   MCS_E_INVALID: n > 4096, a null pointer, responder or requester not below mcs_num_clusters, t_last +
+ * time_s > 0xFFFFFFFE.  MCS_E_STATE, with the cause in mcs_last_error: no trading session; external mode
+ * off; no tick executed yet; the session failed; the run's flags carry a log or virtual-node overflow, as
+ * the series calls refuse.  MCS_FLAG_T_MAX does not refuse: the tick at t_max_s raises it, the reference's
+ * traders run their rounds at that tick too, and the clock then stays there (the grant reaches the logs
+ * and the counters and no later decision).
+ *   Capacity.  A call that overflows the running-slot pool (receive: the virtual-node pool) escalates as
+ * mcs_run does (slots grow by half, virtual nodes x 4) and replays the session from t = 0: the engine
+ * keeps every accepted call with the t_last it acted at, and a replay runs up to t + 1, applies that
+ * tick's calls in order, and so on, then applies the call that triggered it (restarts counts the replay,
+ * stats->replayed = 1, an open cursor rebuilds once).  With a fixed cfg.slot_pool or at the pools'
+ * limits: MCS_E_CAPACITY and the session is failed until mcs_rewind.  mcs_rewind, a new submit and
+ * mcs_load_clusters drop the kept calls. */
+int mcs_trade_session_provide_vnodes(mcs_engine* eng, const mcs_vnode_request* req, uint32_t n,
+                                     mcs_vnode_result* res, mcs_vnode_stats* stats /* may be NULL */);
+
+typedef struct mcs_vnode_grant {
+    uint32_t cluster, cores, memory, pad;
+} mcs_vnode_grant;
+/* AddVirtualNode for each entry, in array order: the cluster gets the row {cores, memory} with capacity
+ * = free = the node's, behind its physical nodes and the virtual nodes received so far; {0, 0} is legal
+ * (the zero contract).  The row takes part in the next tick's first fit; mcs_read_virtual_node_caps,
+ * the series and the cursors show it.  Limits, refusals and capacity as mcs_trade_session_provide_vnodes
+ * (MCS_E_CAPACITY at 256 virtual nodes per cluster). */
+int mcs_trade_session_receive_vnodes(mcs_engine* eng, const mcs_vnode_grant* node, uint32_t n,
+                                     mcs_vnode_stats* stats /* may be NULL */);
+/* The live free counters of a cluster's rows (physical, then virtual) as the last executed tick and the
+ * grants since left them, as Go uint64 (sign-extended): what an outside trader builds a NodeObject from.
+ * *n = the row count (may exceed cap: then only cap rows are written).  Either mode of a trading session;
+ * MCS_E_STATE without one, before its first tick and after it failed. */
+int mcs_trade_session_read_nodes(mcs_engine* eng, uint32_t cluster, uint64_t* free_cores,
+                                 uint64_t* free_memory, uint32_t cap, uint32_t* n);
 
 /* ---- single-call mirror of the approval rule ---------------------------------------------------- */
 /* Trader.ApproveTrade (pkg/trader/trader.go:141-167) with the reference's approvePolicy{0.8, 0.8, -1,

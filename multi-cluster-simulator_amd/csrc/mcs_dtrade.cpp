@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "mcs_dtrade_grant.h"
 #include "mcs_dtrade_internal.h"
 #include "mcs_engine_impl.h"
 
@@ -57,6 +58,11 @@ struct DtradeDev {
     bool rgraph_tried = false;
     uint32_t loop_form = kLoopGraph;
     bool begun = false;  // caller-driven lock-step in progress
+    // external traders' calls (mcs_dtrade_grant.hip): the call's arguments and results, the walk's stash
+    unsigned char* gbuf = nullptr;
+    size_t gbuf_bytes = 0;
+    unsigned long long* gstash = nullptr;
+    size_t gstash_rows = 0;
     std::chrono::steady_clock::time_point w0{};
 };
 
@@ -133,7 +139,7 @@ int dtrade_alloc(mcs_engine* e) {
     a.blk = blk;
     a.xb = d->xb;
     a.nv_all = d->nv_all;
-    a.period = e->cfg.trader_period_s;
+    a.period = e->dt_external ? 0u : e->cfg.trader_period_s;  // (external traders: a system without rounds)
     a.ok_sleep = e->cfg.trade_ok_sleep_s;
     a.fail_sleep = e->cfg.trade_fail_sleep_s;
     a.lock_s = e->cfg.lock_s;
@@ -249,6 +255,7 @@ int dt_run_once(mcs_engine* e, double* kernel_ms) {
 bool dt_res_ok(mcs_engine* e) {
     const char* env = getenv("MCS_DT_RESIDENT");
     if ((env && atoi(env) == 0) || e->tr_no_resident || e->comm || e->world != 1) return false;
+    if (e->dt_external) return false;  // (the system without rounds runs on the replayed kernels)
     const DtArgs& a = e->dtd->a;
     return a.Ct == a.C && a.C <= kDtResMaxClusters && e->max_n + a.V <= kDtResMaxNN && a.S <= kDtResMaxSlots &&
            a.S % 64u == 0u;
@@ -383,6 +390,8 @@ int dt_clusters(mcs_engine* e, std::vector<DtCluster>& cl) {
 // lock-step state is in HBM as the last tick left it; the host only re-plans the control block: the
 // resume tick min(parked tick, earliest arrival appended since), the rounds due at it, the horizon.
 // Short slices run eagerly (8 ticks, then 32, each with one poll); longer ones through the graph.
+int dts_resume(mcs_engine* e, uint32_t t_res, uint32_t any_due, uint32_t t_hor, double* kernel_ms);
+
 int dts_slice(mcs_engine* e, uint32_t t_hor, double* kernel_ms) {
     DtradeDev* d = e->dtd;
     *kernel_ms = 0.0;
@@ -396,14 +405,31 @@ int dts_slice(mcs_engine* e, uint32_t t_hor, double* kernel_ms) {
         any_due = t_res == e->ts_t_next ? e->ts_any_due : 0u;  // (below the parked tick no round is due)
     }
     if (t_hor != MCS_TIME_NONE) {
-        if (t_res >= t_hor) return MCS_OK;
-    } else {
-        std::vector<DtCluster> cl;
-        if (int s = dt_clusters(e, cl)) return s;
-        uint64_t decided = 0;
-        for (uint32_t k = 0; k < e->C; ++k) decided += cl[k].decided;
-        if (decided == e->total_jobs) return MCS_OK;  // a drain with nothing undecided executes no tick
+        if (t_res < t_hor)
+            if (int s = dts_resume(e, t_res, any_due, t_hor, kernel_ms)) return s;
+        // External traders (DESIGN.md §14 "External traders"): a grant acts on the node state the last
+        // executed tick left, so a finite horizon always ends with a tick at h - 1.  Where the next-tick
+        // rule parked below it, the run is resumed once at T = h - 1 and parks again: that tick does the
+        // releases due and, on a multiple of the sample period, the sample; it decides nothing (ticks are
+        // consecutive while any job is queued), and no arrival lies below h (the rule would have chosen it).
+        if (e->dt_external && t_hor != 0u && c.ticks != 0u && !(c.flags & (MCS_FLAG_T_MAX | MCS_FLAG_OVERFLOW)) &&
+            c.T < t_hor - 1u)
+            if (int s = dts_resume(e, t_hor - 1u, 0u, t_hor, kernel_ms)) return s;
+        return MCS_OK;
     }
+    std::vector<DtCluster> cl;
+    if (int s = dt_clusters(e, cl)) return s;
+    uint64_t decided = 0;
+    for (uint32_t k = 0; k < e->C; ++k) decided += cl[k].decided;
+    if (decided == e->total_jobs) return MCS_OK;  // a drain with nothing undecided executes no tick
+    return dts_resume(e, t_res, any_due, t_hor, kernel_ms);
+}
+
+// the session from tick t_res until it parks or ends under the horizon t_hor; adds to *kernel_ms and to
+// the ticks of the run
+int dts_resume(mcs_engine* e, uint32_t t_res, uint32_t any_due, uint32_t t_hor, double* kernel_ms) {
+    DtradeDev* d = e->dtd;
+    DtCtl& c = d->h_ctl[0];
     const uint32_t ticks0 = c.ticks;
     DtCtl& p = d->h_ctl[3];
     p = c;
@@ -432,8 +458,8 @@ int dts_slice(mcs_engine* e, uint32_t t_hor, double* kernel_ms) {
         if (int s = dt_graph_loop(e, &end_ev)) return s;
     float ms = 0.0f;
     HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, end_ev));
-    *kernel_ms = ms;
-    e->ts_ticks_last = c.ticks - ticks0;
+    *kernel_ms += ms;
+    e->ts_ticks_last += c.ticks - ticks0;
     e->ts_ticks_total = c.ticks;
     e->ts_t_last = c.T;
     e->ts_pend_min = MCS_TIME_NONE;  // every arrival held was known to the last tick's next-tick rule
@@ -453,6 +479,7 @@ void dtrade_session_reset(mcs_engine* e) {
     e->ts_any_due = 1u;
     e->ts_pend_min = MCS_TIME_NONE;
     e->ts_ticks_last = e->ts_ticks_total = e->ts_restarts = 0u;
+    e->ts_grants.clear();  // (the external traders' timeline starts over)
 }
 
 bool dtrade_stream_view(mcs_engine* e, DtStreamView* v) {
@@ -496,51 +523,145 @@ int dtrade_session_run(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     return st;
 }
 
+// ---- external traders: one grant call on the device (mcs_dtrade_grant.hip) -------------------------
+// The call's entries, stably grouped by the cluster they act on, go up in one copy with the zeroed
+// status; the results and the status come back in one copy behind one synchronisation: the launches and
+// synchronisations of a call do not depend on n.  *flags: MCS_FLAG_OVERFLOW / MCS_FLAG_VNODE_OVERFLOW
+// when a pool overflowed (the device state is then partly written: the caller escalates and replays).
+static int dt_grant_apply(mcs_engine* e, const DtGrantCall& call, mcs_vnode_result* res, uint32_t* flags,
+                          uint32_t* added, double* kernel_ms) {
+    DtradeDev* d = e->dtd;
+    const bool provide = !call.req.empty();
+    const uint32_t n = (uint32_t)(provide ? call.req.size() : call.node.size());
+    *flags = 0u;
+    *added = 0u;
+    *kernel_ms = 0.0;
+    if (n == 0) return MCS_OK;
+    std::vector<uint32_t> order(n), inv(n), soff(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    auto key = [&](uint32_t i) { return provide ? call.req[i].responder : call.node[i].cluster; };
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
+    std::vector<DtGrantGroup> groups;
+    uint64_t rows = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = key(order[i]);
+        inv[order[i]] = i;
+        if (groups.empty() || groups.back().cluster != c) groups.push_back(DtGrantGroup{c, i, i, 0u});
+        groups.back().end = i + 1u;
+        soff[i] = (uint32_t)rows;  // (at most 4096 * (1024 + 256) rows)
+        if (provide) rows += (e->node_off[c + 1] - e->node_off[c]) + d->a.V;
+    }
+    const uint32_t ng = (uint32_t)groups.size();
+    // [results | status | entries | order | inv | soff | groups | counts]: the upload is [status, counts),
+    // the download [results, entries)
+    const size_t esz = provide ? sizeof(mcs_vnode_request) : sizeof(mcs_vnode_grant);
+    const size_t o_res = 0, o_status = o_res + (size_t)n * sizeof(mcs_vnode_result);
+    const size_t o_ent = o_status + sizeof(DtGrantStatus), o_order = o_ent + (size_t)n * esz;
+    const size_t o_inv = o_order + (size_t)n * 4, o_soff = o_inv + (size_t)n * 4, o_groups = o_soff + (size_t)n * 4;
+    const size_t o_cnt = o_groups + (size_t)ng * sizeof(DtGrantGroup), total = o_cnt + (size_t)n * 4;
+    static_assert(sizeof(mcs_vnode_result) == 16 && sizeof(DtGrantStatus) == 16 && sizeof(DtGrantGroup) == 16 &&
+                      sizeof(mcs_vnode_request) % 8 == 0 && sizeof(mcs_vnode_grant) == 16,
+                  "grant buffer layout");
+    if (d->gbuf_bytes < total) {
+        dfree(d->gbuf);
+        d->gbuf_bytes = 0;
+        HIPCHK(e, hipMalloc(&d->gbuf, total * 2));
+        d->gbuf_bytes = total * 2;
+    }
+    if (provide && d->gstash_rows < rows) {
+        dfree(d->gstash);
+        d->gstash_rows = 0;
+        HIPCHK(e, hipMalloc(&d->gstash, rows * 2 * 16));
+        d->gstash_rows = rows * 2;
+    }
+    std::vector<unsigned char> up(o_cnt - o_status, 0), down(o_ent - o_res);
+    unsigned char* u = up.data() - o_status;  // (indexed by the buffer's offsets)
+    for (uint32_t i = 0; i < n; ++i) {
+        if (provide) std::memcpy(u + o_ent + (size_t)i * esz, &call.req[order[i]], esz);
+        else std::memcpy(u + o_ent + (size_t)i * esz, &call.node[order[i]], esz);
+    }
+    std::memcpy(u + o_order, order.data(), (size_t)n * 4);
+    std::memcpy(u + o_inv, inv.data(), (size_t)n * 4);
+    std::memcpy(u + o_soff, soff.data(), (size_t)n * 4);
+    std::memcpy(u + o_groups, groups.data(), (size_t)ng * sizeof(DtGrantGroup));
+    DtGrantArgs g{};
+    g.req = provide ? reinterpret_cast<const mcs_vnode_request*>(d->gbuf + o_ent) : nullptr;
+    g.node = provide ? nullptr : reinterpret_cast<const mcs_vnode_grant*>(d->gbuf + o_ent);
+    g.order = reinterpret_cast<const uint32_t*>(d->gbuf + o_order);
+    g.inv = reinterpret_cast<const uint32_t*>(d->gbuf + o_inv);
+    g.soff = reinterpret_cast<const uint32_t*>(d->gbuf + o_soff);
+    g.groups = reinterpret_cast<const DtGrantGroup*>(d->gbuf + o_groups);
+    g.res = reinterpret_cast<mcs_vnode_result*>(d->gbuf + o_res);
+    g.cnt = reinterpret_cast<uint32_t*>(d->gbuf + o_cnt);
+    g.stash = d->gstash;
+    g.status = reinterpret_cast<DtGrantStatus*>(d->gbuf + o_status);
+    g.n_foreign = d->h_ctl->n_foreign;
+    g.n = n;
+    g.n_groups = ng;
+    g.T = e->ts_t_last;
+    HIPCHK(e, hipMemcpyAsync(d->gbuf + o_status, up.data(), up.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipEventRecord(e->ev0, e->stream));
+    const hipError_t st = provide ? launch_dtrade_grant_provide(d->a, g, e->stream)
+                                  : launch_dtrade_grant_receive(d->a, g, e->stream);
+    if (st != hipSuccess) return dt_hip_fail(e, "external traders' grant", st);
+    HIPCHK(e, hipEventRecord(e->ev1, e->stream));
+    HIPCHK(e, hipMemcpyAsync(down.data(), d->gbuf + o_res, down.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (the call's one synchronisation)
+    float ms = 0.0f;
+    HIPCHK(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    *kernel_ms = ms;
+    DtGrantStatus status;
+    std::memcpy(&status, down.data() + o_status, sizeof(status));
+    *flags = status.flags;
+    if (status.flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW)) return MCS_OK;
+    if (provide) {
+        if (res) std::memcpy(res, down.data() + o_res, (size_t)n * sizeof(mcs_vnode_result));
+        *added = status.added;
+        d->h_ctl->n_foreign = status.n_foreign;  // (the host's copy of the control block follows the device's)
+        if (status.flags & MCS_FLAG_LOG_OVERFLOW) d->h_ctl->flags |= MCS_FLAG_LOG_OVERFLOW;
+    }
+    return MCS_OK;
+}
+
+// A replay of a session that holds grants (after a capacity escalation): slice by slice, up to t + 1 with
+// its forced tick, then the calls kept for tick t in order, and so on; then the slice to the horizon.
+// *gflags: a pool overflow of a re-applied call (the caller escalates again).
+static int dts_replay(mcs_engine* e, uint32_t t_hor, double* kernel_ms, uint32_t* gflags) {
+    uint32_t ticks = 0;
+    for (size_t i = 0; i < e->ts_grants.size();) {
+        const uint32_t t = e->ts_grants[i].t;
+        double ms = 0.0;
+        if (int s = dts_slice(e, t + 1u, &ms)) return s;
+        *kernel_ms += ms;
+        ticks += e->ts_ticks_last;
+        if (e->dtd->h_ctl->flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW)) return MCS_OK;
+        if (e->ts_t_last != t)
+            return fail(e, MCS_E_STATE, "the replay of a trading session did not reach a kept grant's tick");
+        for (; i < e->ts_grants.size() && e->ts_grants[i].t == t; ++i) {
+            uint32_t fl = 0, added = 0;
+            if (int s = dt_grant_apply(e, e->ts_grants[i], nullptr, &fl, &added, &ms)) return s;
+            *kernel_ms += ms;
+            if (fl & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW)) {
+                *gflags |= fl;
+                return MCS_OK;
+            }
+        }
+    }
+    double ms = 0.0;
+    if (int s = dts_slice(e, t_hor, &ms)) return s;
+    *kernel_ms += ms;
+    e->ts_ticks_last += ticks;
+    return MCS_OK;
+}
+
+static int dts_run_loop(mcs_engine* e, uint32_t t_hor, double* kms_out, uint32_t* escalations_out);
+
 static int dtrade_session_run_body(mcs_engine* e, uint32_t t_hor, mcs_stats* stats) {
     const auto w0 = std::chrono::steady_clock::now();
     e->on_series_ok = false;  // until this run has ended well (mcs_trade_session_state_series)
     uint32_t escalations = 0;
     double kms = 0.0;
-    for (;;) {
-        if (!e->ts_begun || !e->dtd) {  // from t = 0: the session's first run, or a replay after an escalation
-            if (!e->ts_begun) {  // (the capacities the last run of these inputs escalated to)
-                e->tr_slots = e->dt_learn_s;
-                e->dt_vnodes = e->dt_learn_v;
-            }
-            e->dt_ns = 0;
-            if (e->dtd) dtrade_free(e);
-            if (int s = dtrade_alloc(e)) return s;
-            const hipError_t st = launch_dtrade_init(e->dtd->a, e->stream);
-            if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading init", st);
-            if (int s = dt_poll(e)) return s;
-            e->ts_begun = true;
-            e->ts_t_last = e->ts_t_next = 0u;
-            e->ts_any_due = 1u;
-            e->ts_ticks_total = 0u;
-        }
-        double ms = 0.0;
-        if (int s = dts_slice(e, t_hor, &ms)) return s;
-        kms += ms;
-        const uint32_t flags = e->dtd->h_ctl->flags;
-        const uint32_t S = e->dtd->a.S, V = e->dtd->a.V;
-        const bool grow_s = (flags & MCS_FLAG_OVERFLOW) != 0, grow_v = (flags & MCS_FLAG_VNODE_OVERFLOW) != 0;
-        if (!grow_s && !grow_v) break;
-        if ((grow_s && (e->cfg.slot_pool || S >= kDtMaxSlots)) || (grow_v && V >= kDtMaxVnodes)) {
-            e->ts_failed = true;
-            return fail(e, MCS_E_CAPACITY, "DELAY trading capacity exhausted (slots or virtual nodes): the session "
-                                           "is failed until mcs_rewind or a new submit");
-        }
-        // as dtrade_run escalates; the session is replayed from t = 0 up to this horizon over every job
-        // held, which the slicing guarantee makes the state a session with these capacities would hold
-        const uint32_t ns = grow_s ? std::min<uint32_t>((S + S / 2u + 63u) / 64u * 64u, kDtMaxSlots) : S,
-                       nv = grow_v ? std::min<uint32_t>(V * 4u, kDtMaxVnodes) : V;
-        dtrade_free(e);
-        e->tr_slots = ns;
-        e->dt_vnodes = nv;
-        ++escalations;
-        ++e->ts_restarts;
-        trade_stream_restart(e);  // (an open stream keeps t_next and rebuilds once)
-    }
+    if (int s = dts_run_loop(e, t_hor, &kms, &escalations)) return s;
     e->dt_learn_s = e->cfg.slot_pool ? 0u : e->dtd->a.S;
     e->dt_learn_v = e->dtd->a.V;
     e->dtd->kernel_ms = kms;
@@ -573,6 +694,139 @@ static int dtrade_session_run_body(mcs_engine* e, uint32_t t_hor, mcs_stats* sta
         st.online = 1u;
         *stats = st;
     }
+    return MCS_OK;
+}
+
+// a slot-pool or virtual-node overflow (flags) in a slice or a grant: the pools grow as dtrade_run's do and
+// the lock-step state is dropped, so that the next slice replays the session from t = 0 over every job held
+// (which the slicing guarantee makes the state a session with these capacities would hold); or, with the
+// capacity exhausted, the session fails
+static int dts_escalate(mcs_engine* e, uint32_t flags) {
+    const uint32_t S = e->dtd->a.S, V = e->dtd->a.V;
+    const bool grow_s = (flags & MCS_FLAG_OVERFLOW) != 0, grow_v = (flags & MCS_FLAG_VNODE_OVERFLOW) != 0;
+    if ((grow_s && (e->cfg.slot_pool || S >= kDtMaxSlots)) || (grow_v && V >= kDtMaxVnodes)) {
+        e->ts_failed = true;
+        return fail(e, MCS_E_CAPACITY, "DELAY trading capacity exhausted (slots or virtual nodes): the session "
+                                       "is failed until mcs_rewind or a new submit");
+    }
+    const uint32_t ns = grow_s ? std::min<uint32_t>((S + S / 2u + 63u) / 64u * 64u, kDtMaxSlots) : S,
+                   nv = grow_v ? std::min<uint32_t>(V * 4u, kDtMaxVnodes) : V;
+    dtrade_free(e);
+    e->tr_slots = ns;
+    e->dt_vnodes = nv;
+    ++e->ts_restarts;
+    trade_stream_restart(e);  // (an open stream keeps t_next and rebuilds once)
+    return MCS_OK;
+}
+
+// the slices of one run (or of a grant's replay) with the capacity escalation around them: on a slot-pool
+// or virtual-node overflow the pools grow and the session is replayed from t = 0, its grants included
+static int dts_run_loop(mcs_engine* e, uint32_t t_hor, double* kms_out, uint32_t* escalations_out) {
+    uint32_t escalations = 0;
+    double kms = 0.0;
+    for (;;) {
+        bool from0 = false;
+        if (!e->ts_begun || !e->dtd) {  // from t = 0: the session's first run, or a replay after an escalation
+            from0 = true;
+            if (!e->ts_begun) {  // (the capacities the last run of these inputs escalated to)
+                e->tr_slots = e->dt_learn_s;
+                e->dt_vnodes = e->dt_learn_v;
+            }
+            e->dt_ns = 0;
+            if (e->dtd) dtrade_free(e);
+            if (int s = dtrade_alloc(e)) return s;
+            const hipError_t st = launch_dtrade_init(e->dtd->a, e->stream);
+            if (st != hipSuccess) return dt_hip_fail(e, "DELAY trading init", st);
+            if (int s = dt_poll(e)) return s;
+            e->ts_begun = true;
+            e->ts_t_last = e->ts_t_next = 0u;
+            e->ts_any_due = 1u;
+            e->ts_ticks_total = 0u;
+        }
+        double ms = 0.0;
+        uint32_t gflags = 0u;
+        if (from0 && !e->ts_grants.empty()) {  // (external traders: a replay re-applies the grants)
+            if (int s = dts_replay(e, t_hor, &ms, &gflags)) return s;
+        } else {
+            if (int s = dts_slice(e, t_hor, &ms)) return s;
+        }
+        kms += ms;
+        const uint32_t flags = e->dtd->h_ctl->flags | gflags;
+        if (!(flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))) break;
+        if (int s = dts_escalate(e, flags)) return s;
+        ++escalations;
+    }
+    *kms_out += kms;
+    *escalations_out += escalations;
+    return MCS_OK;
+}
+
+// what both grant calls check before their arguments
+static int dt_grant_check(mcs_engine* e, const char* call) {
+    const std::string c(call);
+    if (!is_trade_session(e))
+        return fail(e, MCS_E_STATE, c + " acts on a trading session (online mode with MCS_POLICY_DELAY and "
+                                        "cfg.trader): there is no trading session");
+    if (!e->dt_external)
+        return fail(e, MCS_E_STATE, c + " needs external mode (mcs_trade_external): the built-in trader rounds are "
+                                        "on, and they share no locks with a trader outside the engine");
+    if (e->ts_failed)
+        return fail(e, MCS_E_STATE, c + ": the trading session failed (capacity exhausted, MCS_E_CAPACITY): "
+                                        "mcs_rewind or submit again, then run");
+    if (!e->ts_begun || !e->dtd || e->ts_ticks_total == 0u)
+        return fail(e, MCS_E_STATE, c + " acts on the state the last executed tick left: no tick has been executed "
+                                        "yet (mcs_run first)");
+    const DtCtl& ctl = *e->dtd->h_ctl;
+    // (MCS_FLAG_T_MAX does not refuse: the tick at t_max_s raises it, and the reference's traders run their
+    // rounds at that tick too (DT-KAT1 and DT-KAT6b end with one); the clock then stays there, so such a
+    // grant reaches the logs and the counters and no later decision)
+    if (ctl.flags & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))
+        return fail(e, MCS_E_STATE, c + ": a slot-pool or virtual-node overflow (MCS_FLAG_VNODE_OVERFLOW) cut the "
+                                        "run short");
+    if ((ctl.flags & MCS_FLAG_LOG_OVERFLOW) || ctl.n_foreign > e->dtd->a.foreign_cap ||
+        ctl.n_trades > e->dtd->a.trade_cap)
+        return fail(e, MCS_E_STATE, c + ": the Foreign or contract log overflowed (MCS_FLAG_LOG_OVERFLOW): records "
+                                        "were dropped");
+    return MCS_OK;
+}
+
+// an accepted grant call: applied to the device state; on a pool overflow the session escalates, is
+// replayed from t = 0 up to the tick the call acts at (its earlier grants re-applied) and the call is
+// applied again; then it joins the kept calls
+static int dt_grant_call(mcs_engine* e, DtGrantCall&& call, mcs_vnode_result* res, mcs_vnode_stats* stats) {
+    mcs_vnode_stats st{};
+    const uint32_t t = e->ts_t_last;
+    call.t = t;
+    st.n = (uint32_t)(call.req.size() + call.node.size());
+    for (;;) {
+        uint32_t fl = 0, added = 0;
+        double ms = 0.0;
+        if (int s = dt_grant_apply(e, call, res, &fl, &added, &ms)) return s;
+        st.kernel_ms += ms;
+        st.foreign_added = added;
+        if (!(fl & (MCS_FLAG_OVERFLOW | MCS_FLAG_VNODE_OVERFLOW))) break;
+        int s = dts_escalate(e, fl);
+        uint32_t esc = 0;
+        double kms = 0.0;
+        if (s == MCS_OK) s = dts_run_loop(e, t + 1u, &kms, &esc);
+        if (s != MCS_OK) {  // (as a run that failed: an open stream closes)
+            trade_stream_run_end(e, t + 1u, s);
+            return s;
+        }
+        st.kernel_ms += kms;
+        st.replayed = 1u;
+        e->dt_learn_s = e->cfg.slot_pool ? 0u : e->dtd->a.S;
+        e->dt_learn_v = e->dtd->a.V;
+        e->dtrade_run = true;  // (dtrade_free dropped it with the state)
+        if (e->ts_t_last != t)
+            return fail(e, MCS_E_STATE, "the replay of a trading session did not reach the grant's tick");
+    }
+    if (res)
+        for (uint32_t i = 0; i < st.n; ++i) st.n_ok += res[i].ok ? 1u : 0u;
+    else
+        st.n_ok = st.n;
+    e->ts_grants.push_back(std::move(call));
+    if (stats) *stats = st;
     return MCS_OK;
 }
 
@@ -648,6 +902,8 @@ void dtrade_free(mcs_engine* e) {
     dfree(d->gx);
     dfree(d->gu);
     dfree(d->ops);
+    dfree(d->gbuf);
+    dfree(d->gstash);
     if (d->h_ctl) (void)hipHostFree(d->h_ctl);
     for (hipEvent_t& ev : d->pev)
         if (ev) (void)hipEventDestroy(ev);
@@ -953,6 +1209,95 @@ int mcs_trade_session_info(mcs_engine* e, mcs_trade_session* out) {
     s.drained = e->ts_drained ? 1u : 0u;
     s.failed = e->ts_failed ? 1u : 0u;
     *out = s;
+    return MCS_OK;
+}
+
+// ---- external traders (DESIGN.md §14 "External traders") ------------------------------------------
+int mcs_trade_external(mcs_engine* e, uint32_t on) {
+    if (int st = check_engine(e)) return st;
+    if (!e->has_clusters) return fail(e, MCS_E_STATE, "mcs_trade_external: mcs_load_clusters first");
+    if (!mcs::is_dtrade(e) || e->cfg.borrow)
+        return fail(e, MCS_E_STATE, "mcs_trade_external needs a DELAY trading system (MCS_POLICY_DELAY with "
+                                    "cfg.trader = 1 and cfg.borrow = 0): FIFO trading and systems without "
+                                    "traders have no virtual nodes to grant");
+    if (e->world != 1 || e->rank != 0 || e->comm)
+        return fail(e, MCS_E_STATE, "mcs_trade_external needs one engine that holds the whole system (rank 0 of "
+                                    "world 1, no communicator): a sharded engine runs the built-in traders");
+    if (e->dtd && e->dtd->begun)
+        return fail(e, MCS_E_STATE, "mcs_trade_external: a caller-driven lock-step run is in progress "
+                                    "(mcs_trade_end first)");
+    if (e->online && e->ts_begun && e->ts_ticks_total != 0u)
+        return fail(e, MCS_E_STATE, "mcs_trade_external: a lock-step tick of the current session has run (switch "
+                                    "before the first mcs_run, right after mcs_rewind or after a new submit)");
+    e->dt_external = on != 0u;
+    if (e->dtd) {  // (a captured graph holds the kernels' arguments by value)
+        mcs::dtrade_release_graphs(e);
+        e->dtd->a.period = e->dt_external ? 0u : e->cfg.trader_period_s;
+    }
+    return MCS_OK;
+}
+
+int mcs_trade_session_provide_vnodes(mcs_engine* e, const mcs_vnode_request* req, uint32_t n,
+                                     mcs_vnode_result* res, mcs_vnode_stats* stats) {
+    if (int st = check_engine(e)) return st;
+    if (stats) *stats = mcs_vnode_stats{};
+    if (int st = mcs::dt_grant_check(e, "mcs_trade_session_provide_vnodes")) return st;
+    if (n == 0) return MCS_OK;
+    if (!req || !res) return fail(e, MCS_E_INVALID, "null requests or results");
+    if (n > 4096u) return fail(e, MCS_E_INVALID, "more than 4096 requests in one call");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (req[i].responder >= e->C || req[i].requester >= e->C)
+            return fail(e, MCS_E_INVALID, "request " + std::to_string(i) + ": responder or requester out of range");
+        if ((uint64_t)e->ts_t_last + req[i].time_s > 0xFFFFFFFEull)
+            return fail(e, MCS_E_INVALID, "request " + std::to_string(i) + ": t_last + time_s lies past second "
+                                              "0xFFFFFFFE");
+    }
+    mcs::DtGrantCall call;
+    call.req.assign(req, req + n);
+    return mcs::dt_grant_call(e, std::move(call), res, stats);
+}
+
+int mcs_trade_session_receive_vnodes(mcs_engine* e, const mcs_vnode_grant* node, uint32_t n, mcs_vnode_stats* stats) {
+    if (int st = check_engine(e)) return st;
+    if (stats) *stats = mcs_vnode_stats{};
+    if (int st = mcs::dt_grant_check(e, "mcs_trade_session_receive_vnodes")) return st;
+    if (n == 0) return MCS_OK;
+    if (!node) return fail(e, MCS_E_INVALID, "null nodes");
+    if (n > 4096u) return fail(e, MCS_E_INVALID, "more than 4096 nodes in one call");
+    for (uint32_t i = 0; i < n; ++i)
+        if (node[i].cluster >= e->C)
+            return fail(e, MCS_E_INVALID, "node " + std::to_string(i) + ": cluster index out of range");
+    mcs::DtGrantCall call;
+    call.node.assign(node, node + n);
+    return mcs::dt_grant_call(e, std::move(call), nullptr, stats);
+}
+
+int mcs_trade_session_read_nodes(mcs_engine* e, uint32_t cluster, uint64_t* free_cores, uint64_t* free_memory,
+                                 uint32_t cap, uint32_t* n) {
+    if (int st = check_engine(e)) return st;
+    if (!n || (cap && (!free_cores || !free_memory))) return fail(e, MCS_E_INVALID, "bad output");
+    if (!mcs::is_trade_session(e))
+        return fail(e, MCS_E_STATE, "mcs_trade_session_read_nodes reads a trading session (online mode with "
+                                    "MCS_POLICY_DELAY and cfg.trader): there is no trading session");
+    if (e->ts_failed)
+        return fail(e, MCS_E_STATE, "mcs_trade_session_read_nodes: the trading session failed (capacity exhausted)");
+    if (!e->ts_begun || !e->dtd || e->ts_ticks_total == 0u)
+        return fail(e, MCS_E_STATE, "mcs_trade_session_read_nodes reads the state the last executed tick left: no "
+                                    "tick has been executed yet (mcs_run first)");
+    if (cluster >= e->C) return fail(e, MCS_E_INVALID, "cluster index out of range");
+    mcs::DtradeDev* d = e->dtd;
+    mcs::DtCluster k{};
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemcpy(&k, d->cl + cluster, sizeof(k), hipMemcpyDeviceToHost));
+    const uint32_t N = e->node_off[cluster + 1] - e->node_off[cluster], nv = std::min(k.nv, d->a.V);
+    std::vector<unsigned long long> v((size_t)N + nv + 1u);
+    if (N) HIPCHK(e, hipMemcpy(v.data(), d->tn + e->node_off[cluster], (size_t)N * 8, hipMemcpyDeviceToHost));
+    if (nv) HIPCHK(e, hipMemcpy(v.data() + N, d->vn + (size_t)cluster * d->a.V, (size_t)nv * 8, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < N + nv && i < cap; ++i) {  // Go uint64: the sign-extended u32 halves
+        free_cores[i] = (uint64_t)(int64_t)(int32_t)(uint32_t)v[i];
+        free_memory[i] = (uint64_t)(int64_t)(int32_t)(uint32_t)(v[i] >> 32);
+    }
+    *n = N + nv;
     return MCS_OK;
 }
 

@@ -763,6 +763,29 @@ __device__ __forceinline__ void dt_contracts(const bool due, const uint32_t lane
     }
 }
 
+// AllocateVirtualNodeResources' visit of one row (cluster.go:93-116), the one text of its arithmetic for
+// the trader rounds (dt_rounds) and the external traders' grants (mcs_dtrade_grant.hip).  v: the row's
+// free counters {cores | memory << 32}, read as Go uint64 (the sign-extended u32 halves); rc_, rm_: what
+// is left of the request before the visit, and after it.  memDiff and coreDiff are the float64 absolute
+// differences against the counters (:94-99); a half becomes 0 when its difference exceeds it and shrinks
+// by uint32(diff) otherwise (:101-111); fc, fm: the Foreign job's {uint(coreDiff), uint(memDiff)} (:113-116).
+__device__ __forceinline__ void dt_vnode_visit(const unsigned long long v, uint32_t& rc_, uint32_t& rm_,
+                                               unsigned long long& fc, unsigned long long& fm) {
+    double mem_diff = 0.0, core_diff = 0.0;
+    if (rm_ > 0u) mem_diff = fabs(__dsub_rn((double)rm_, go_f64((uint32_t)(v >> 32))));
+    if (rc_ > 0u) core_diff = fabs(__dsub_rn((double)rc_, go_f64((uint32_t)v)));
+    if (mem_diff > (double)rm_)
+        rm_ = 0u;
+    else
+        rm_ -= (uint32_t)mem_diff;
+    if (core_diff > (double)rc_)
+        rc_ = 0u;
+    else
+        rc_ -= (uint32_t)core_diff;
+    fc = go_f64_to_u64(core_diff);
+    fm = go_f64_to_u64(mem_diff);
+}
+
 // Phase D's trader rounds of tick T in cluster order over the whole system, on the records of the
 // tick (srec) and the replicated trader state (trs); appr, nvs, nfr: per-cluster scratch, virtual
 // node and free slot counts (LDS).  The replayed form commits a local cluster's side effects to its
@@ -867,18 +890,8 @@ __device__ __forceinline__ DtCounts dt_rounds(const DtArgs& a, const uint32_t la
                         if (rm_ == 0u && rc_ == 0u) break;  // :90-92
                         unsigned long long* sp = nd < rN ? &rs[nd] : &rs[a.NS + (nd - rN)];
                         const unsigned long long v = ld64(sp);
-                        double mem_diff = 0.0, core_diff = 0.0;
-                        if (rm_ > 0u) mem_diff = fabs(__dsub_rn((double)rm_, go_f64((uint32_t)(v >> 32))));
-                        if (rc_ > 0u) core_diff = fabs(__dsub_rn((double)rc_, go_f64((uint32_t)v)));
-                        if (mem_diff > (double)rm_)
-                            rm_ = 0u;
-                        else
-                            rm_ -= (uint32_t)mem_diff;
-                        if (core_diff > (double)rc_)
-                            rc_ = 0u;
-                        else
-                            rc_ -= (uint32_t)core_diff;
-                        const unsigned long long fc = go_f64_to_u64(core_diff), fm = go_f64_to_u64(mem_diff);
+                        unsigned long long fc, fm;
+                        dt_vnode_visit(v, rc_, rm_, fc, fm);
                         if (lane == 0) {
                             if (n_for < a.foreign_cap) {
                                 mcs_foreign_rec fr;

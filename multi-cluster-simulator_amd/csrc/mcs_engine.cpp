@@ -280,6 +280,8 @@ int mcs_load_clusters(mcs_engine* e, const uint32_t* cap_c, const uint32_t* cap_
     mcs::dtrade_free(e);
     e->has_clusters = e->has_jobs = e->has_run = false;
     e->dt_learn_s = e->dt_learn_v = 0;
+    e->dt_external = false;  // (mcs_trade_external: the switch belongs to the clusters it was set for)
+    e->ts_grants.clear();
     e->tr_agreed = false;  // (an agreed block layout belongs to the clusters it was agreed for)
     e->tr_ns = e->dt_ns = 0;
     e->C = n_clusters;
@@ -349,6 +351,7 @@ static int alloc_jobs(mcs_engine* e, const uint64_t* job_offsets, bool records) 
     free_jobs(e);
     mcs::trade_free(e);
     mcs::dtrade_free(e);
+    e->ts_grants.clear();  // (the external traders' timeline starts over with the jobs)
     e->has_jobs = e->has_run = false;
     e->dt_learn_s = e->dt_learn_v = 0;
     e->job_off.assign(job_offsets, job_offsets + e->C + 1);

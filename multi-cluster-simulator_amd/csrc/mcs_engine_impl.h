@@ -114,6 +114,13 @@ bool dtrade_stream_view(mcs_engine* e, DtStreamView* v);
 void trade_stream_restart(mcs_engine* e);
 void trade_stream_run_end(mcs_engine* e, uint32_t t_hor, int status);
 
+// one accepted mcs_trade_session_provide_vnodes (req) or mcs_trade_session_receive_vnodes (node) call
+struct DtGrantCall {
+    uint32_t t;  // the session's last executed tick when the call acted
+    std::vector<mcs_vnode_request> req;
+    std::vector<mcs_vnode_grant> node;
+};
+
 // Lock-step tick loops: mcs_trade_stats.loop_form
 constexpr uint32_t kLoopGraph = 0;      // one engine, ticks replayed from a captured hipGraph
 constexpr uint32_t kLoopRcclEager = 1;  // RCCL all-gather per tick, launches enqueued eagerly
@@ -247,6 +254,11 @@ struct mcs_engine {
     uint32_t ts_any_due = 1;           // ... and whether a trader round is due at it
     uint32_t ts_pend_min = 0xFFFFFFFFu;  // earliest arrival appended since the last executed tick
     uint32_t ts_ticks_last = 0, ts_ticks_total = 0, ts_restarts = 0;
+    // external traders (mcs_trade_external, DESIGN.md §14 "External traders"): the built-in trader rounds
+    // are off (DtArgs.period = 0) and the caller grants between slices; every accepted grant call is kept
+    // with the tick it acted at, for the replays of a capacity escalation
+    bool dt_external = false;
+    std::vector<mcs::DtGrantCall> ts_grants;
     // mcs_trade_session_state_series: compact the Foreign log per call (dt_foreign_live_kernel).
     // -1: when the direct scan would take at least kDtForeignFilterMinRounds rounds (mcs_dtrade.cpp);
     // MCS_DT_FOREIGN_FILTER at mcs_create: 0 never, any other value always

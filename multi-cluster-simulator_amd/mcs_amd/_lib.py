@@ -251,6 +251,23 @@ class mcs_trade_session(C.Structure):
                                           "restarts", "drained", "failed")]
 
 
+class mcs_vnode_request(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("responder", "requester", "cores", "memory", "time_s", "pad")]
+
+
+class mcs_vnode_result(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("visited", C.c_uint32), ("left_cores", C.c_uint32), ("left_memory", C.c_uint32)]
+
+
+class mcs_vnode_stats(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("n_ok", C.c_uint32), ("foreign_added", C.c_uint32), ("replayed", C.c_uint32),
+                ("kernel_ms", C.c_double)]
+
+
+class mcs_vnode_grant(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("cluster", "cores", "memory", "pad")]
+
+
 class mcs_approve_query(C.Structure):
     _fields_ = [("total_cores", C.c_uint32), ("total_memory", C.c_uint32), ("core_util", C.c_float),
                 ("mem_util", C.c_float), ("cores", C.c_uint32), ("memory", C.c_uint32), ("time_s", C.c_uint32),
@@ -356,6 +373,12 @@ SIGNATURES = [
                                                  C.POINTER(mcs_cluster_state), C.c_uint32, C.POINTER(C.c_double)]),
     ("mcs_trade_session_level1_series", C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(mcs_level1_sample), C.c_uint32, C.POINTER(C.c_double)]),
+    ("mcs_trade_external", C.c_int, [vp, C.c_uint32]),
+    ("mcs_trade_session_provide_vnodes", C.c_int, [vp, C.POINTER(mcs_vnode_request), C.c_uint32,
+                                                   C.POINTER(mcs_vnode_result), C.POINTER(mcs_vnode_stats)]),
+    ("mcs_trade_session_receive_vnodes", C.c_int, [vp, C.POINTER(mcs_vnode_grant), C.c_uint32,
+                                                   C.POINTER(mcs_vnode_stats)]),
+    ("mcs_trade_session_read_nodes", C.c_int, [vp, C.c_uint32, u64p, u64p, C.c_uint32, u32p]),
 ]
 
 _lib = None

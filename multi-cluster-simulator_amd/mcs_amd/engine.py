@@ -157,6 +157,11 @@ CONTRACT_DTYPE = np.dtype([("t", "<u4"), ("requester", "<u4"), ("winner", "<i4")
 FOREIGN_DTYPE = np.dtype([("requester", "<u4"), ("responder", "<u4"), ("node", "<u4"), ("start", "<u4"),
                           ("finish", "<u4"), ("pad", "<u4"), ("c", "<u8"), ("m", "<u8")])
 
+VNODE_REQUEST_DTYPE = np.dtype([("responder", "<u4"), ("requester", "<u4"), ("cores", "<u4"), ("memory", "<u4"),
+                                ("time_s", "<u4"), ("pad", "<u4")])
+VNODE_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("visited", "<u4"), ("left_cores", "<u4"), ("left_memory", "<u4")])
+VNODE_GRANT_DTYPE = np.dtype([("cluster", "<u4"), ("cores", "<u4"), ("memory", "<u4"), ("pad", "<u4")])
+
 LENT_DTYPE = np.dtype([("lender", "<u4"), ("borrower", "<u4"), ("job", "<u8"), ("node", "<u4"),
                        ("start", "<u4"), ("finish", "<u4"), ("pad", "<u4")])
 TRADE_DTYPE = np.dtype([("t", "<u4"), ("requester", "<u4"), ("winner", "<i4"), ("approvals", "<u4")])
@@ -321,6 +326,59 @@ class Engine:
         ts = L.mcs_trade_session()
         self._c(L.lib().mcs_trade_session_info(self._h, C.byref(ts)))
         return {k: getattr(ts, k) for k, _ in L.mcs_trade_session._fields_}
+
+    # -- external traders (DESIGN.md §14 "External traders") ------------------------------------
+    def trade_external(self, on: bool = True) -> None:
+        """mcs_trade_external: switch the built-in trader rounds of a DELAY trading system off (on) or
+        back on; accepted while no lock-step tick of the current session has run."""
+        self._c(L.lib().mcs_trade_external(self._h, 1 if on else 0))
+
+    @staticmethod
+    def _vnode_stats(st) -> dict:
+        return {k: getattr(st, k) for k, _ in L.mcs_vnode_stats._fields_}
+
+    def provide_virtual_nodes(self, requests):
+        """mcs_trade_session_provide_vnodes: ProvideVirtualNode (AllocateVirtualNodeResources) for each
+        request, in order, at the session's last executed tick.  requests: a VNODE_REQUEST_DTYPE array,
+        or rows (responder, requester, cores, memory, time_s).  Returns (results, stats): a
+        VNODE_RESULT_DTYPE array (ok, visited, left_cores, left_memory) and the call's stats."""
+        if isinstance(requests, np.ndarray) and requests.dtype == VNODE_REQUEST_DTYPE:
+            req = np.ascontiguousarray(requests)
+        else:
+            req = np.zeros(len(requests), VNODE_REQUEST_DTYPE)
+            for i, r in enumerate(requests):
+                req[i] = tuple(int(x) for x in r) + (0,)
+        res = np.zeros(len(req), VNODE_RESULT_DTYPE)
+        st = L.mcs_vnode_stats()
+        self._c(L.lib().mcs_trade_session_provide_vnodes(
+            self._h, req.ctypes.data_as(C.POINTER(L.mcs_vnode_request)), len(req),
+            res.ctypes.data_as(C.POINTER(L.mcs_vnode_result)), C.byref(st)))
+        return res, self._vnode_stats(st)
+
+    def receive_virtual_nodes(self, nodes) -> dict:
+        """mcs_trade_session_receive_vnodes: ReceiveVirtualNode (AddVirtualNode) for each entry, in
+        order.  nodes: a VNODE_GRANT_DTYPE array, or rows (cluster, cores, memory).  Returns the stats."""
+        if isinstance(nodes, np.ndarray) and nodes.dtype == VNODE_GRANT_DTYPE:
+            nd = np.ascontiguousarray(nodes)
+        else:
+            nd = np.zeros(len(nodes), VNODE_GRANT_DTYPE)
+            for i, r in enumerate(nodes):
+                nd[i] = tuple(int(x) for x in r) + (0,)
+        st = L.mcs_vnode_stats()
+        self._c(L.lib().mcs_trade_session_receive_vnodes(
+            self._h, nd.ctypes.data_as(C.POINTER(L.mcs_vnode_grant)), len(nd), C.byref(st)))
+        return self._vnode_stats(st)
+
+    def trade_session_nodes(self, cluster: int):
+        """mcs_trade_session_read_nodes: (free_cores, free_memory) of a cluster's rows (physical, then
+        virtual) as the last executed tick and the grants since left them, uint64 (Go's wrapped uint)."""
+        n = C.c_uint32()
+        self._c(L.lib().mcs_trade_session_read_nodes(self._h, cluster, None, None, 0, C.byref(n)))
+        c = np.zeros(max(n.value, 1), np.uint64)
+        m = np.zeros(max(n.value, 1), np.uint64)
+        self._c(L.lib().mcs_trade_session_read_nodes(self._h, cluster, L.ptr(c, C.c_uint64), L.ptr(m, C.c_uint64),
+                                                     n.value, C.byref(n)))
+        return c[:n.value], m[:n.value]
 
     def lent(self) -> np.ndarray:
         """Lent runs of this engine's clusters (LENT_DTYPE), sorted by (start, lender, borrower, job)."""
